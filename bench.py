@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- beam-element-steps/s of the fused RK4 beam stepper on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config configX] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config configX] [--scaling weak|strong] [--dump-outputs DIR]
 
 One "step" = one classical RK4 time step (dt = 2e-5 s) of the whole batch.  Workload at N = 1 is
 BASELINE.json's metric configuration (configs[2]): 4096 beams x 256 nonlinear Euler-Bernoulli
@@ -20,8 +20,13 @@ beams) and shards them, raggedly if need be.
 Prints ONE JSON line on rank 0 (contract in the task statement): metric/value/unit, ms_per_step,
 `roofline` (algorithmic HBM bytes = 96 B per element-step; config5: fp64 MFMA flop of the
 feedback GEMM) and `cpu_baseline` (the C oracle -- a port of the reference path -- on this box's host cores,
-all cores and one core, bounded samples).  The timed region is K steps bracketed by barrier + synchronize; when
-that region is shorter than 50 ms it is repeated (state reset untimed in between) and the MEDIAN is reported.
+all cores and one core, bounded samples).  The timed region is exactly K steps bracketed by barrier + synchronize;
+`--repeats R` times it R times (state reset untimed in between) and reports the MEDIAN.
+
+`--dump-outputs DIR` writes what the last timed rollout returned as DIR/<name>.npy: `state` (the terminal states in the
+reference's reduced ordering [B, 2n], all ranks' beams gathered, in the run's dtype) and `clock` (the time the stepper
+returned).  Above 64 MB the state is a seeded sample of beams, whose indices are written as `state_rows`.  Inputs are
+fixed by the arguments, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -40,7 +45,7 @@ MFMA_F64_PEAK_TF = 78.6        # MI355X fp64 matrix peak (public spec, SURVEY §
 MFMA_F32_PEAK_TF = 157.3       # MI355X_MICROARCH.md: f32-input MFMA = f32 vector peak
 VALU_CLOCK_HZ = 2.4e9          # nominal engine clock (the chip holds ~2.2 GHz under this fp64 load)
 BYTES_PER_ELEM_STEP = {"f64": 96.0, "f32": 48.0}
-MIN_TIMED_S = 0.05             # shorter timed regions are repeated and the median reported
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: at most this much in all
 
 CONFIGS = {
     # BASELINE configs[0], the reference's own CPU-runnable case: ONE 10-element linear cantilever under gravity
@@ -86,8 +91,10 @@ def parse(argv=None):
     ap.add_argument("--gather-chunks", type=int, default=0,
                     help="N > 1: split each rank's shard into this many chunks and all-gather chunk c asynchronously while "
                          "chunk c+1 is stepped (0 = 4 when the shard allows it, 1 = one blocking exchange at the end)")
-    ap.add_argument("--repeats", type=int, default=0,
-                    help="timed repeats of the K-step rollout (0 = as many as a 50 ms timed region needs)")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="timed repeats of the K-step rollout (the median is reported)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed rollout as DIR/<name>.npy (at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--verify-all", action="store_true",
                     help="after timing, compare EVERY beam of rank 0 with the oracle (open-loop configs; tens of CPU-seconds)")
@@ -103,8 +110,8 @@ def parse(argv=None):
         args.scaling = cfg["scaling"]
     if args.launch_steps is None:
         args.launch_steps = 0 if cfg.get("implicit") else 100
-    if args.gpus < 1 or args.steps < 1 or args.warmup < 0:
-        ap.error("--gpus >= 1, --steps >= 1, --warmup >= 0")
+    if args.gpus < 1 or args.steps < 1 or args.warmup < 0 or args.repeats < 1:
+        ap.error("--gpus >= 1, --steps >= 1, --warmup >= 0, --repeats >= 1")
     return args
 
 
@@ -238,6 +245,27 @@ def source_hash(files):
         with open(os.path.join(ROOT, f), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]
+
+
+def dump_outputs(out_dir, state, clock, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the terminal states [B, 2n] (reduced ordering, the run's dtype) and the clock the stepper returned, as
+    out_dir/<name>.npy.  A state larger than ``limit`` is cut to a fixed sample of beams (seed 0, ascending), whose indices
+    go to state_rows.npy.  Returns {name: shape} of what was written."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    x = state.detach().cpu().numpy()
+    arrays = {"clock": np.array([clock], dtype=np.float64)}
+    row_bytes = x.shape[1] * x.itemsize
+    if x.nbytes > limit - 4096:
+        n_rows = (limit - 4096) // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(0).choice(x.shape[0], size=n_rows, replace=False))
+        x = x[rows]
+        arrays["state_rows"] = rows.astype(np.float64)
+    arrays["state"] = np.ascontiguousarray(x)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def worker(args):
@@ -379,15 +407,25 @@ def worker(args):
         for c in range(n_chunks):
             advance_one(c, k)
 
+    def timed_launch(c, k, into):
+        """One launch of the timed rollout, bracketed by device events (appended to ``into``)."""
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()   # (the stepper launches on torch's current stream: BeamEnsemble._stream)
+        advance_one(c, k)
+        e1.record()
+        into.append((e0, e1, k))
+
     # ---- warmup (untimed), then restore the initial state so the timed K steps are the
     # parity-checked trajectory (the shipped nonlinear element is only stable to ~1000 steps)
     reset()
     # untimed device spin-up before the W warmup steps: a fresh box starts with idle clocks and cold
     # code objects, which 100 steps (4 ms) do not cover (observed once: a first run at half speed)
     t_spin = time.perf_counter()
+    # (through the timed launches' own path: the first device events cost ~50 us, which a single short timed region would carry)
     while time.perf_counter() - t_spin < 0.3:
         reset()
-        advance(per_launch)
+        for c in range(n_chunks):
+            timed_launch(c, per_launch, [])
         torch.cuda.synchronize()
     reset()
     w_done = 0
@@ -423,11 +461,7 @@ def worker(args):
             done = 0
             while done < args.steps:
                 k = min(per_launch, args.steps - done)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()   # (the stepper launches on torch's current stream: BeamEnsemble._stream)
-                advance_one(c, k)
-                e1.record()
-                events.append((e0, e1, k))
+                timed_launch(c, k, events)
                 done += k
 
         # the one exchange: RCCL all-gather of the terminal states in the reference's reduced ordering
@@ -451,12 +485,8 @@ def worker(args):
         return wall, gathered
 
     walls = []
-    wall, gathered = timed_rollout()
-    walls.append(wall)
-    # a region shorter than 50 ms is not a measurement to rank kernels by: repeat it (every rank derives the same
-    # count from the max-reduced first wall; the first repeat is the slowest, hence the 25 % margin) and report the median
-    repeats = args.repeats if args.repeats > 0 else max(1, min(1000, int(np.ceil(1.25 * MIN_TIMED_S / max(wall, 1e-6)))))
-    for _ in range(repeats - 1):
+    repeats = args.repeats
+    for _ in range(repeats):
         wall, gathered = timed_rollout()
         walls.append(wall)
     wall = float(np.median(walls))
@@ -491,6 +521,9 @@ def worker(args):
         gathered = assemble_chunks(gathered, world)
         assert torch.equal(gathered[lo:hi], state), "chunked all-gather does not reproduce this rank's states"
     check = {"finite": finite, "gathered_beams": int(gathered.shape[0]) if gathered is not None else int(state.shape[0])}
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, state if gathered is None else gathered, ens.time)
     if rank == 0:
         b = B - 1
         ob = oracle_beam(params[b] if args.hetero else cols, **okw)
@@ -593,6 +626,7 @@ def worker(args):
                        **({"rehearsal": "all ranks on GPU 0, exchange over gloo: NOT a measurement"} if rehearsal else {})},
             "roofline": roofline,
             "check": check,
+            **({"dumped_outputs": dumped} if dumped is not None else {}),
         }
         if cfg.get("implicit") and world == 1 and not args.hetero:
             # the example's own call on this configuration (examples/example_utilities.py:153-159): 1 s, method="LSODA",

@@ -2508,6 +2508,32 @@ def test_bench_takes_the_rccl_path_with_one_rank():
     assert max(line["check"]["block_err_vs_oracle_last_beam"].values()) < 1e-9
 
 
+def test_bench_dumps_the_outputs_of_its_timed_steps(tmp_path):
+    """`bench.py --dump-outputs DIR` (config 2: seeded random initial states): the terminal states of the timed rollout in
+    reduced ordering and the stepper's clock; a second run with another warmup writes the same outputs."""
+    import json
+    import subprocess
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "CRB_BENCH_FORCE_DIST",
+                                                           "CRB_BENCH_REHEARSAL")}
+    lines, states = [], []
+    for warmup, d in (("5", "a"), ("0", "b")):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--config", "config2", "--steps", "30",
+                              "--warmup", warmup, "--no-cpu-baseline", "--dump-outputs", str(tmp_path / d)],
+                             env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append(json.loads(out.stdout.strip().splitlines()[-1]))
+        states.append(np.load(tmp_path / d / "state.npy"))
+        assert np.load(tmp_path / d / "clock.npy").tolist() == pytest.approx([30 * 2e-5], rel=1e-12)
+    line, x = lines[0], states[0]
+    n = 3 * 64
+    assert line["steps"] == 30 and line["repeats"] == 1 and line["dumped_outputs"]["state"] == [1024, 2 * n]
+    assert x.dtype == np.float64 and np.isfinite(x).all()
+    assert x[-1, n - 2] == line["check"]["tip_w_last_beam"]
+    np.testing.assert_allclose(states[1], x, rtol=0, atol=1e-12 * np.abs(x).max())
+
+
 @pytest.mark.parametrize("n_e,B", [(10, 7), (64, 3), (130, 2)])
 @pytest.mark.parametrize("span", [0.05, 0.78, 3.0, 40.0])
 def test_gravity_rotation_kernels_over_small_and_large_angles(n_e, B, span):

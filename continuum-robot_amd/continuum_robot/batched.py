@@ -337,28 +337,53 @@ class BeamEnsemble:
             with self._on_device():
                 nat.check(self._lib.crb_plan_set_status(self.plan.h, self._ptr(self._status), 0))
 
-    def _impulse(self, desc, keep, impulse_amp, impulse_duration, impulse_index):
-        """Fill the impulse part of a crb_input_desc: amplitudes [B] on reduced position index ``impulse_index`` of
-        EVERY beam (-2 = each beam's own tip w, example_utilities.py:147) while t < impulse_duration."""
-        amp = self._dev(impulse_amp, (self.n_beams,))
-        nodes, dofs = [], []
-        for b in (range(self.n_beams) if self.mixed_topology else (0,)):
-            fi = self.free_index_per_beam[b]
-            idx = impulse_index if impulse_index >= 0 else fi.size + impulse_index
-            if not 0 <= idx < fi.size:
-                raise IndexError("impulse_index out of range")
-            nodes.append(int(fi[idx]) // 3)
-            dofs.append(int(fi[idx]) % 3)
-        if len(set(dofs)) != 1:
-            raise ValueError("impulse_index addresses different DOF kinds (u / w / phi) in different beams")
-        desc.kind, desc.node, desc.dof = nat.CRB_INPUT_IMPULSE, nodes[0], dofs[0]
-        desc.duration = float(impulse_duration)
-        desc.amp = amp.data_ptr()
-        keep.append(amp)
-        if len(set(nodes)) > 1:       # beams of different length / boundary conditions: each forced at its own node
-            node_b = torch.as_tensor(nodes, dtype=torch.int32, device=self.device)
-            desc.node_b = node_b.data_ptr()
-            keep.append(node_b)
+    def _input_desc(self, impulse_amp=None, impulse_duration=0.01, impulse_index=-2, held_force=None):
+        """The crb_input_desc of a call and the device buffers it points to (they must outlive the asynchronous launch):
+        amplitudes [B] on reduced position index ``impulse_index`` of EVERY beam (-2 = each beam's own tip w,
+        example_utilities.py:147) while t < impulse_duration, and the reduced [B, n] ``held_force``."""
+        desc, keep = nat.InputDesc(), []
+        desc.kind = nat.CRB_INPUT_NONE
+        if impulse_amp is not None:
+            amp = self._dev(impulse_amp, (self.n_beams,))
+            nodes, dofs = [], []
+            for b in (range(self.n_beams) if self.mixed_topology else (0,)):
+                fi = self.free_index_per_beam[b]
+                idx = impulse_index if impulse_index >= 0 else fi.size + impulse_index
+                if not 0 <= idx < fi.size:
+                    raise IndexError("impulse_index out of range")
+                nodes.append(int(fi[idx]) // 3)
+                dofs.append(int(fi[idx]) % 3)
+            if len(set(dofs)) != 1:
+                raise ValueError("impulse_index addresses different DOF kinds (u / w / phi) in different beams")
+            desc.kind, desc.node, desc.dof = nat.CRB_INPUT_IMPULSE, nodes[0], dofs[0]
+            desc.duration = float(impulse_duration)
+            desc.amp = amp.data_ptr()
+            keep.append(amp)
+            if len(set(nodes)) > 1:       # beams of different length / boundary conditions: each forced at its own node
+                node_b = torch.as_tensor(nodes, dtype=torch.int32, device=self.device)
+                desc.node_b = node_b.data_ptr()
+                keep.append(node_b)
+        if held_force is not None:
+            held = self.pack_vec(held_force)
+            desc.f_held = held.data_ptr()
+            keep.append(held)
+        return desc, keep
+
+    def _record_desc(self, record, n: int, every: int = 1):
+        """The crb_record_desc of a call and its zeroed buffer of n_samples = n // every samples (n steps, a sample every
+        ``every``-th; or the n points of a t_eval grid): record="all" = whole-state snapshots (every DOF of the reference's
+        sol.y) [n_samples, B, 2, n_node, 4] in device layout (unpack_snapshots() gives the reduced ordering),
+        (node, 'u'|'w'|'phi'|'du_dt'|'dw_dt'|'dphi_dt') = that DOF's series [B, n_samples]; (None, None) for record=None."""
+        if record is None:
+            return None, None
+        n_samples = int(n) // int(every)
+        if isinstance(record, str) and record == "all":
+            samples = torch.zeros((n_samples,) + tuple(self.state.shape), dtype=self.dtype, device=self.device)
+            return nat.RecordDesc(0, -1, 0, int(every), samples.data_ptr()), samples
+        node, param = record
+        vel = param.startswith("d") and param.endswith("_dt")
+        samples = torch.zeros((self.n_beams, n_samples), dtype=self.dtype, device=self.device)
+        return nat.RecordDesc(int(vel), int(node), _PARAM[param[1:-3] if vel else param], int(every), samples.data_ptr()), samples
 
     # ------------------------------------------------------------------ the hot path
     def internal_force(self, q_red) -> torch.Tensor:
@@ -399,31 +424,10 @@ class BeamEnsemble:
         """
         if t0 is not None:
             self.time = float(t0)
-        desc = nat.InputDesc()
-        desc.kind = nat.CRB_INPUT_NONE
-        keep = []
-        if impulse_amp is not None:
-            self._impulse(desc, keep, impulse_amp, impulse_duration, impulse_index)
-        if held_force is not None:
-            held = self.pack_vec(held_force)
-            desc.f_held = held.data_ptr()
-            keep.append(held)
+        desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index, held_force)
+        rec, samples = self._record_desc(record, n_steps, record_every)
+        keep.append(samples)
         t_end = C.c_double(0.0)
-        rec, samples = None, None
-        if isinstance(record, str) and record == "all":
-            # whole-state snapshots (every DOF of the reference's sol.y on the t_eval grid): device layout
-            # [n_rec, B, 2, n_node, 4]; reduced ordering through unpack_snapshots()
-            samples = torch.zeros((int(n_steps) // int(record_every),) + tuple(self.state.shape), dtype=self.dtype,
-                                  device=self.device)
-            rec = nat.RecordDesc(0, -1, 0, int(record_every), samples.data_ptr())
-            keep.append(samples)
-        elif record is not None:
-            node, param = record
-            vel = param.startswith("d") and param.endswith("_dt")
-            samples = torch.zeros((self.n_beams, int(n_steps) // int(record_every)), dtype=self.dtype, device=self.device)
-            rec = nat.RecordDesc(int(vel), int(node), _PARAM[param[1:-3] if vel else param], int(record_every),
-                                 samples.data_ptr())
-            keep.append(samples)
         with self._on_device():
             nat.check(self._lib.crb_step_rk4_rec(self.plan.h, self._ptr(self.state), self.time, float(dt), int(n_steps),
                                                  C.byref(desc), C.byref(rec) if rec is not None else None,
@@ -446,29 +450,10 @@ class BeamEnsemble:
         they do under LSODA's BDF formulas; 0 removes them within a step or two, 1 is the midpoint rule."""
         if t0 is not None:
             self.time = float(t0)
-        desc = nat.InputDesc()
-        desc.kind = nat.CRB_INPUT_NONE
-        keep = []
-        if impulse_amp is not None:
-            self._impulse(desc, keep, impulse_amp, impulse_duration, impulse_index)
-        if held_force is not None:
-            held = self.pack_vec(held_force)
-            desc.f_held = held.data_ptr()
-            keep.append(held)
+        desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index, held_force)
+        rec, samples = self._record_desc(record, n_steps, record_every)
+        keep.append(samples)
         t_end = C.c_double(0.0)
-        rec, samples = None, None
-        if isinstance(record, str) and record == "all":
-            samples = torch.zeros((int(n_steps) // int(record_every),) + tuple(self.state.shape), dtype=self.dtype,
-                                  device=self.device)
-            rec = nat.RecordDesc(0, -1, 0, int(record_every), samples.data_ptr())
-            keep.append(samples)
-        elif record is not None:
-            node, param = record
-            vel = param.startswith("d") and param.endswith("_dt")
-            samples = torch.zeros((self.n_beams, int(n_steps) // int(record_every)), dtype=self.dtype, device=self.device)
-            rec = nat.RecordDesc(int(vel), int(node), _PARAM[param[1:-3] if vel else param], int(record_every),
-                                 samples.data_ptr())
-            keep.append(samples)
         with self._on_device():
             nat.check(self._lib.crb_step_implicit_damped(self.plan.h, self._ptr(self.state), self.time, float(h), int(n_steps),
                                                          int(n_iter), float(rho_inf), C.byref(desc),
@@ -658,15 +643,7 @@ class BeamEnsemble:
             raise ValueError('control must be "all" or "positions"')
         if t0 is not None:
             self.time = float(t0)
-        desc = nat.InputDesc()
-        desc.kind = nat.CRB_INPUT_NONE
-        keep = []
-        if impulse_amp is not None:
-            self._impulse(desc, keep, impulse_amp, impulse_duration, impulse_index)
-        if held_force is not None:
-            held = self.pack_vec(held_force)
-            desc.f_held = held.data_ptr()
-            keep.append(held)
+        desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index, held_force)
         K = None if gain is None else self._dev(gain, (self.n, 2 * self.n))
         ref = None if reference is None else self._dev(reference, (self.n_beams, 2 * self.n))
         n_intervals = int(n_intervals)
@@ -774,30 +751,13 @@ class BeamEnsemble:
         given ``t_eval=np.arange(...)``, example_utilities.py:158)."""
         if t0 is not None:
             self.time = float(t0)
-        desc = nat.InputDesc()
-        desc.kind = nat.CRB_INPUT_NONE
-        keep = []
-        if impulse_amp is not None:
-            self._impulse(desc, keep, impulse_amp, impulse_duration, impulse_index)
-        if held_force is not None:
-            held = self.pack_vec(held_force)
-            desc.f_held = held.data_ptr()
-            keep.append(held)
+        desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index, held_force)
         h = torch.zeros((self.n_beams,), dtype=torch.float64, device=self.device)
         if first_step is not None:
             h += torch.as_tensor(first_step, dtype=torch.float64, device=self.device)
         stats = torch.zeros((self.n_beams, 4), dtype=torch.int32, device=self.device)
-        rec, ys, grid = None, None, (0.0, 0.0, 0)
-        if isinstance(record, str) and record == "all":   # every DOF of sol.y: snapshots [count, B, 2, n_node, 4]
-            grid = (float(t_eval[0]), float(t_eval[1]), int(t_eval[2]))
-            ys = torch.zeros((grid[2],) + tuple(self.state.shape), dtype=self.dtype, device=self.device)
-            rec = nat.RecordDesc(0, -1, 0, 1, ys.data_ptr())
-        elif record is not None:
-            node, param = record
-            vel = param.startswith("d") and param.endswith("_dt")
-            grid = (float(t_eval[0]), float(t_eval[1]), int(t_eval[2]))
-            ys = torch.zeros((self.n_beams, grid[2]), dtype=self.dtype, device=self.device)
-            rec = nat.RecordDesc(int(vel), int(node), _PARAM[param[1:-3] if vel else param], 1, ys.data_ptr())
+        grid = (0.0, 0.0, 0) if record is None else (float(t_eval[0]), float(t_eval[1]), int(t_eval[2]))
+        rec, ys = self._record_desc(record, grid[2])
         with self._on_device():
             nat.check(self._lib.crb_solve_rk45_eval(self.plan.h, self._ptr(self.state), self.time, float(t_end), float(rtol),
                                                     float(atol), C.byref(desc), self._ptr(h), self._ptr(stats),
@@ -843,11 +803,7 @@ class BeamEnsemble:
             return self._step_feedback_grouped(n_steps, dt, gain, reference, impulse_amp, impulse_duration, impulse_index)
         K = self._dev(gain, (self.n, 2 * self.n))
         ref = None if reference is None else self._dev(reference, (self.n_beams, 2 * self.n))
-        desc = nat.InputDesc()
-        desc.kind = nat.CRB_INPUT_NONE
-        keep = []
-        if impulse_amp is not None:
-            self._impulse(desc, keep, impulse_amp, impulse_duration, impulse_index)
+        desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index)
         # the whole loop is one native call (crb_step_rk4_feedback issues every launch)
         work = torch.empty((int(self._lib.crb_feedback_work_bytes(self.plan.h)),), dtype=torch.uint8, device=self.device)
         t_end = C.c_double(0.0)
@@ -887,11 +843,7 @@ class BeamEnsemble:
         one MFMA launch per group and stage (crb_step_rk4_feedback_grouped).  `reference`: [B, 2 n_max] padded reduced states."""
         group_of, mats = self._gain_groups(gains)
         ref = None if reference is None else self._dev(reference, (self.n_beams, 2 * self.n))
-        desc = nat.InputDesc()
-        desc.kind = nat.CRB_INPUT_NONE
-        keep = []
-        if impulse_amp is not None:
-            self._impulse(desc, keep, impulse_amp, impulse_duration, impulse_index)
+        desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index)
         ptrs = (C.c_void_p * len(mats))(*[m.data_ptr() for m in mats])
         work = torch.empty((int(self._lib.crb_feedback_work_bytes(self.plan.h)),), dtype=torch.uint8, device=self.device)
         t_end = C.c_double(0.0)
@@ -955,11 +907,7 @@ class BeamEnsemble:
         """
         if t0 is not None:
             self.time = float(t0)
-        desc = nat.InputDesc()
-        desc.kind = nat.CRB_INPUT_NONE
-        keep = []
-        if impulse_amp is not None:
-            self._impulse(desc, keep, impulse_amp, impulse_duration, impulse_index)
+        desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index)
         acc, bufs = torch.empty_like(self.state), (torch.empty_like(self.state), torch.empty_like(self.state))
         zeros = torch.zeros((self.n_beams, self.n_node, 4), dtype=self.dtype, device=self.device)
         u_held = None if (u is None or callable(u)) else self._dev(u, (self.n_beams, self.n))

@@ -1,0 +1,52 @@
+// crb_host.h -- host-side helpers shared by the launch translation units (crbeam.hip, crb_lean.hip, crb_loop.hip).
+#pragma once
+#include <cstdlib>
+
+namespace crb {
+
+// Runtime switches.  Each is read when the call it steers is made (the tests flip them between calls on one ensemble),
+// CRB_HOST_SPIN_MS alone at plan creation.  (switch: effect -- test of tests/test_gpu_parity.py that sets it)
+//   CRB_DISABLE_LEAN: the general kernels on every path -- test_held_force_on_lean_size_beams,
+//       test_adaptive_rk45_lean_rhs_equals_general_rhs, test_gravity_rotation_kernels_over_small_and_large_angles
+//   CRB_DISABLE_LEAN_STAGE: the general kernel for crb_rk4_stage -- test_lean_stage_kernel_feedback_rollout_matches_oracle
+//   CRB_DISABLE_LEAN_IMPLICIT: the general kernels for the implicit and the controlled implicit steppers --
+//       test_implicit_lean_kernel_equals_the_general_one, test_controlled_implicit_kernel_takes_the_oracles_steps,
+//       test_implicit_reduction_levels_follow_the_step_size
+//   CRB_DISABLE_LEAN_FEEDBACK: the general kernels for the fused and the controlled closed loops --
+//       test_fused_feedback_stepper_matches_the_stage_split_one_and_the_oracle,
+//       test_controlled_closed_loop_kernel_takes_the_oracles_steps
+//   CRB_FUSED_FEEDBACK=0|1: crb_step_rk4_feedback never / whenever the gain fits LDS in its fused form (unset: chosen by
+//       size) -- test_fused_feedback_stepper_matches_the_stage_split_one_and_the_oracle,
+//       test_fused_feedback_stepper_walks_over_groups_of_beams
+//   CRB_LOOP=0|1: crb_step_rk4_feedback never / whenever eligible in its persistent form (unset: 512 beams and more) --
+//       test_persistent_closed_loop_stepper_matches_the_oracle_and_the_stage_split_path,
+//       test_per_beam_status_reports_the_launch_in_which_a_beam_went_non_finite
+//   CRB_LOOP_FENCES=1: release / acquire fences around the persistent stepper's hand-offs --
+//       test_persistent_closed_loop_stepper_with_release_acquire_fences
+//   CRB_LOOP_MAX_GROUPS: groups of workgroups of the persistent stepper (several row blocks per group) --
+//       test_persistent_closed_loop_stepper_matches_the_oracle_and_the_stage_split_path
+//   CRB_LEAN_MAX_GROUPS: workgroups of the lean kernels that walk over beams -- test_workgroups_walking_over_beams_match_one_workgroup_per_beam,
+//       test_implicit_lean_kernel_equals_the_general_one, test_fused_feedback_stepper_walks_over_groups_of_beams
+//   CRB_LEAN_NO_WALK: one workgroup per beam for the lean stepper -- test_workgroups_walking_over_beams_match_one_workgroup_per_beam
+//   CRB_STAGE_GROUPS: workgroups of the lean stage kernel -- test_lean_stage_kernel_feedback_rollout_matches_oracle
+//   CRB_FEEDBACK_TILE=48|32: tile of the feedback GEMM -- test_fused_mfma_feedback_force_matches_matmul,
+//       test_fp32_feedback_force_and_rollout
+//   CRB_STIFF_ALL_LEVELS: the implicit stepper keeps every reduction level of A -- test_implicit_reduction_levels_follow_the_step_size
+//   CRB_LOOP_TIMEOUT_MS: how long a hand-off of the persistent stepper waits before it gives up (default 2000) -- none
+//   CRB_HOST_SPIN_MS: how long a host-vector call spins on its completion flag (default 200) -- none
+inline const char* env(const char* name) { return std::getenv(name); }
+inline bool env_set(const char* name) { return env(name) != nullptr; }
+inline long env_int(const char* name, long unset) {
+    const char* v = env(name);
+    return v ? std::atol(v) : unset;
+}
+
+// Grid of a launch whose workgroups walk over `groups` groups of beams: at most `cap` workgroups (cap <= 0: no limit),
+// the groups split evenly over them (4096 beams on 512 workgroups = 8 each).
+inline int walk_grid(int groups, int cap) {
+    if (cap <= 0 || groups <= cap) return groups;
+    const int rounds = (groups + cap - 1) / cap;
+    return (groups + rounds - 1) / rounds;
+}
+
+}  // namespace crb

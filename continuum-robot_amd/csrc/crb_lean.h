@@ -679,7 +679,7 @@ __global__ void __launch_bounds__(64 << LOGNW, (sizeof(T) == 4 && LOGNW <= 2) ? 
     const T w = (p.stage == 0 || p.stage == 3) ? T(1) : T(2);
     const T cs = (p.stage == 2) ? T(p.dt) : T(0.5 * p.dt);
     const T dt6 = T(p.dt / 6.0);
-    const bool imp_on = stage_time(p) < p.duration;
+    const bool imp_on = p.t0 < p.duration;
 
     ElemCoef<T> ec;
     T dragc = T(0), hm_own = T(0), hm_left = T(0);

@@ -1,6 +1,5 @@
 // crb_lean.hip -- instantiations and launch of crb_step_lean_kernel for ONE dtype (-DCRB_LEAN_T=double|float).
-#include <cstdlib>
-
+#include "crb_host.h"
 #include "crb_lean_launch.h"
 
 #ifndef CRB_LEAN_T
@@ -36,14 +35,9 @@ hipError_t one_held(const KParams<T>& k, int n_beams, hipStream_t st) {
     int grid = groups;
     const bool shared = k.slot_stride == 0 && k.lv_stride == 0 && k.fin_stride == 0;
     static int resident = -1;   // (per instantiation; every device of a node is the same part)
-    if (shared && std::getenv("CRB_LEAN_NO_WALK") == nullptr) {
+    if (shared && !env_set("CRB_LEAN_NO_WALK")) {
         if (resident < 0) resident = resident_groups(kernel, 64 << LOGNW, smem);
-        int cap = resident;
-        if (const char* env = std::getenv("CRB_LEAN_MAX_GROUPS")) cap = std::atoi(env);   // (tests: walk with a handful of beams)
-        if (cap > 0 && groups > cap) {
-            const int rounds = (groups + cap - 1) / cap;
-            grid = (groups + rounds - 1) / rounds;
-        }
+        grid = walk_grid(groups, int(env_int("CRB_LEAN_MAX_GROUPS", resident)));
     }
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 << LOGNW), smem, st, k);
     return hipGetLastError();
@@ -201,12 +195,7 @@ hipError_t one_fb(const KParams<T>& k, int n_beams, hipStream_t st) {
     static int resident = -1;   // (per instantiation)
     if (shared) {   // a workgroup loads its tables and the gain once and walks over several groups of beams
         if (resident < 0) resident = resident_groups(kernel, 64, smem);
-        int cap = resident;
-        if (const char* env = std::getenv("CRB_LEAN_MAX_GROUPS")) cap = std::atoi(env);
-        if (cap > 0 && groups > cap) {
-            const int rounds = (groups + cap - 1) / cap;
-            grid = (groups + rounds - 1) / rounds;
-        }
+        grid = walk_grid(groups, int(env_int("CRB_LEAN_MAX_GROUPS", resident)));
     }
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), smem, st, k);
     return hipGetLastError();

@@ -1,6 +1,5 @@
 // crb_loop.hip -- instantiations and launch of crb_loop_kernel (the persistent closed-loop stepper, crb_loop.h).
-#include <cstdlib>
-
+#include "crb_host.h"
 #include "crb_loop_launch.h"
 
 namespace crb {
@@ -22,8 +21,7 @@ hipError_t one_loop(LoopParams<T> P, const T* gain, hipStream_t st) {
         if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, smem)) != hipSuccess) return e;
         resident = cus * per_cu;
     }
-    int groups = resident / NB;
-    if (const char* env = std::getenv("CRB_LOOP_MAX_GROUPS")) groups = std::atoi(env);   // (tests: several row blocks per group)
+    int groups = int(env_int("CRB_LOOP_MAX_GROUPS", resident / NB));   // (tests: several row blocks per group)
     if (groups > LOOP_MAX_GROUPS) groups = LOOP_MAX_GROUPS;
     if (groups > P.n_rb) groups = P.n_rb;
     if (groups < 1) return hipErrorInvalidConfiguration;

@@ -8,6 +8,7 @@
 #include <cstring>
 #include <ctime>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/crbeam.h"
@@ -15,6 +16,7 @@
 #include "crb_lean_launch.h"
 #include "crb_loop_launch.h"
 #include "crb_ctrl_launch.h"
+#include "crb_host.h"
 
 using namespace crb;
 
@@ -99,7 +101,6 @@ struct crb_plan {
     mutable unsigned long long host_seq = 0;   // sequence number of the last flagged host-path launch
     mutable hipStream_t host_stream = nullptr;
     double host_spin_ms = 200.0;      // CRB_HOST_SPIN_MS at plan creation: how long a host-path call spins on the completion flag
-    bool host_sync = false;           // CRB_HOST_SYNC at plan creation: wait for the stream instead of the flag
     int32_t* d_n_state = nullptr;     // [B] 2 * n_free_b, or null
     std::vector<double> h_levels, h_final, h_norms, h_mass, h_stiff;
     int first_nonlinear = -1;
@@ -112,12 +113,6 @@ struct crb_plan {
     int32_t* d_free_index = nullptr;
     int32_t* d_col_off = nullptr;  // [2n] reduced state index -> offset in a beam's state record
     int32_t* d_row_off = nullptr;  // [n]  reduced position index -> offset in a beam's force record
-    // crb_step_rk4_feedback replays one captured RK4 step (8 launches + clock) as a hipGraph on a stream of
-    // its own (the caller's stream may be the legacy default stream, which cannot be captured)
-    mutable hipStream_t aux_stream = nullptr;
-    mutable hipEvent_t aux_in = nullptr, aux_out = nullptr;
-    mutable hipGraphExec_t step_exec = nullptr;
-    mutable std::vector<uint64_t> step_key;
     // crb_feedback_force_grouped: device tables of the last beam -> group assignment (beam lists, reduced -> layout offsets)
     struct GainGroup { int32_t* beam_idx = nullptr; int32_t* col = nullptr; int32_t* row = nullptr; int n = 0, count = 0; };
     mutable std::vector<GainGroup> gain_groups;
@@ -473,8 +468,7 @@ static int plan_create_impl(crb_plan** out, int device, int dtype, int n_beams, 
 
     crb_plan* p = new crb_plan();
     p->device = device;
-    if (const char* env = std::getenv("CRB_HOST_SPIN_MS")) p->host_spin_ms = std::atof(env);
-    p->host_sync = std::getenv("CRB_HOST_SYNC") != nullptr;
+    if (const char* v = env("CRB_HOST_SPIN_MS")) p->host_spin_ms = std::atof(v);
     p->dtype = dtype;
     p->B = n_beams;
     p->n_elem = ne;
@@ -570,7 +564,6 @@ static int plan_create_impl(crb_plan** out, int device, int dtype, int n_beams, 
         for (int b = 0; b < nd; ++b)
             for (int e = 0; e < d[b].n_elem; ++e) { all_nl = all_nl && d[b].nonlinear[e]; all_lin = all_lin && !d[b].nonlinear[e]; }
         p->elem_mode = all_lin ? EM_LINEAR : (all_nl && !(d->flags & CRB_CORRECTED_AXIAL)) ? EM_NONLINEAR : EM_MIXED;
-        if (std::getenv("CRB_DISABLE_ELEM_MODE")) p->elem_mode = EM_MIXED;
     }
     if (grav) {   // nearest-neighbour gravity (lean kernels) only if EVERY beam that has gravity is the canonical cantilever
         bool canon = true;
@@ -694,11 +687,6 @@ void free_gain_groups(const crb_plan* p);
 extern "C" void crb_plan_destroy(crb_plan* p) {
     if (!p) return;
     if (p->device >= 0) {
-        if (p->aux_stream) (void)hipStreamSynchronize(p->aux_stream);
-        if (p->step_exec) (void)hipGraphExecDestroy(p->step_exec);
-        if (p->aux_in) (void)hipEventDestroy(p->aux_in);
-        if (p->aux_out) (void)hipEventDestroy(p->aux_out);
-        if (p->aux_stream) (void)hipStreamDestroy(p->aux_stream);
         (void)hipFree(p->d_slot);
         (void)hipFree(p->d_levels);
         (void)hipFree(p->d_final);
@@ -869,6 +857,171 @@ int allow_lds(K kernel, size_t bytes) {
     return CRB_OK;
 }
 
+// Calls f(std::integral_constant<int, lv>) for a level count lv of 0 .. MAX (one instantiation of f's body per count);
+// fails with `msg` for any other count
+template <int MAX, int LV = 0, typename F>
+int with_levels(int lv, const char* msg, F&& f) {
+    if (lv == LV) return f(std::integral_constant<int, LV>());
+    if constexpr (LV < MAX) return with_levels<MAX, LV + 1>(lv, msg, f);
+    else return fail(CRB_EUNSUPPORTED, msg);
+}
+
+// ---- decoded inputs and records: the one check of a crb_input_desc / crb_record_desc against the plan
+// The forcing of a launch: amp[b] on DOF `dof` of thread slot `slot` (of node node_b[b] - off per beam when node_b is given)
+// while t < duration; the held force [B][n_node][4] or null.
+struct Forcing {
+    bool impulse = false;
+    int slot = -1, dof = 0;
+    double duration = 0.0;
+    const void* amp = nullptr;
+    const int32_t* node_b = nullptr;
+    const void* held = nullptr;
+};
+int decode_input(const crb_plan* p, const crb_input_desc* in, const char* who, Forcing* f) {
+    *f = Forcing();
+    if (!in) return CRB_OK;
+    f->held = in->f_held;
+    if (in->kind == CRB_INPUT_NONE) return CRB_OK;
+    if (in->kind != CRB_INPUT_IMPULSE) return fail(CRB_EINVAL, std::string(who) + ": unknown input kind");
+    if (in->node < 0 || in->node >= p->n_node || in->dof < 0 || in->dof > 2)
+        return fail(CRB_EINVAL, std::string(who) + ": impulse node/dof out of range");
+    if (!in->amp) return fail(CRB_EINVAL, std::string(who) + ": impulse amplitude array is null");
+    if (!p->any_free[3 * in->node + in->dof])   // (mixed ensembles: a beam in which the DOF is constrained ignores it)
+        return fail(CRB_EINVAL, std::string(who) + ": impulse targets a constrained DOF");
+    f->impulse = true;
+    f->slot = in->node - p->off;
+    f->dof = in->dof;
+    f->duration = in->duration;
+    f->amp = in->amp;
+    f->node_b = in->node_b;
+    return CRB_OK;
+}
+// The recording of a launch: `count` samples of component `comp` (0 .. 5 of {q, v}) of thread slot `slot`, one every `every`
+// steps, into `out`; slot REC_ALL_SLOTS: whole-state snapshots; slot -1: nothing is recorded.
+struct Recording {
+    int slot = -1, comp = 0, every = 1, count = 0;
+    void* out = nullptr;
+};
+// n: the steps of the launch (a sample after every rec->every-th), or with stepped == false the samples of a t_eval grid
+// (crb_solve_rk45_eval: rec->every is unused)
+int decode_record(const crb_plan* p, const crb_record_desc* rec, int n, bool stepped, const char* who, Recording* r) {
+    *r = Recording();
+    if (!rec) return CRB_OK;
+    const bool all = rec->node == CRB_RECORD_ALL;
+    if ((!all && (rec->plane < 0 || rec->plane > 1 || rec->node < 0 || rec->node >= p->n_node || rec->dof < 0 || rec->dof > 2)) ||
+        (stepped && rec->every < 1) || !rec->out)
+        return fail(CRB_EINVAL, std::string(who) + ": bad record description");
+    const int every = stepped ? rec->every : 1;
+    r->count = n / every;
+    if (r->count > 0 && (all || rec->node - p->off >= 0)) {   // (the dropped FIXED node 0 records nothing: it is 0 forever)
+        r->slot = all ? REC_ALL_SLOTS : rec->node - p->off;
+        r->comp = all ? 0 : rec->plane * 3 + rec->dof;
+        r->every = every;
+        r->out = rec->out;
+    }
+    return CRB_OK;
+}
+// the clock a stepper holds after n_steps steps: the same fp64 additions as the kernels and the oracle make
+double clock_after(double t0, double dt, int n_steps) {
+    double t = t0;
+    for (int i = 0; i < n_steps; ++i) t = t + dt;
+    return t;
+}
+// the decoded forcing (and recording) in a launch's parameter block
+template <typename T>
+void set_io(KParams<T>& k, const Forcing& f, const Recording* r = nullptr) {
+    k.u_held = static_cast<const T*>(f.held);
+    k.amp = static_cast<const T*>(f.amp);
+    k.imp_slot = f.slot; k.imp_dof = f.dof; k.duration = f.duration; k.imp_node_b = f.node_b;
+    if (r) { k.rec_out = static_cast<T*>(r->out); k.rec_slot = r->slot; k.rec_comp = r->comp; k.rec_every = r->every; k.rec_n = r->count; }
+}
+
+// ---- which kernel a call runs: the condition of every path, side by side.  The lean kernels (crb_lean.hip, crb_loop.hip,
+// crb_ctrl.hip) are instantiated for these shapes only; every other plan runs the general kernels.
+bool grav_on(const crb_plan* p) { return (p->flags & CRB_FORCE_GRAVITY) != 0; }
+// the lean kernels carry gravity only in the plain cantilever's nearest-neighbour form
+bool lean_grav_ok(const crb_plan* p) { return !grav_on(p) || p->canonical_gravity; }
+// beams of more than 64 slots: only the level counts the truncated reduction lands on are built (crb_lean.hip: by_nw)
+bool lean_levels_ok(const crb_plan* p) {
+    const int lv_long = p->dtype == CRB_F64 ? 5 : 4;
+    return p->lognw == 0 ? (p->levels >= 3 && p->levels <= 6) : (p->levels == lv_long || p->levels == lv_long + 1);
+}
+// crb_step_rk4: one beam per workgroup of up to 8 waves, or beams of fewer than 64 slots packed G > 1 to a wave (the PACK
+// instantiation); a held input has its own instantiation
+bool lean_step_ok(const crb_plan* p) {
+    const bool packed = p->G > 1 && p->lognw == 0 && p->NT == 64;
+    return lean_grav_ok(p) && (p->G == 1 || packed) && p->NT == (64 << p->lognw) && p->lognw <= 3 && lean_levels_ok(p) &&
+           !env_set("CRB_DISABLE_LEAN");
+}
+// crb_rk4_stage: the lean stepper's shapes less the packed one (the stage kernel walks over whole beams)
+bool lean_stage_ok(const crb_plan* p) { return lean_step_ok(p) && p->G == 1 && !env_set("CRB_DISABLE_LEAN_STAGE"); }
+// crb_solve_rk45: the lean RHS has no gravity form at all; one beam per workgroup of up to 4 waves
+bool lean_rk45_ok(const crb_plan* p) {
+    return !grav_on(p) && p->NT == (64 << p->lognw) && p->lognw <= 2 && lean_levels_ok(p) && !env_set("CRB_DISABLE_LEAN");
+}
+// crb_step_implicit, one beam per workgroup of 1 / 2 / 4 waves: the kernels run 5 .. the full level count, and exist for
+// the full count of that width only (33 .. 64 / 65 .. 128 / 129 .. 256 slots)
+bool implicit_group_shape(const crb_plan* p) {
+    return p->G == 1 && p->lognw <= 2 && p->NT == (64 << p->lognw) && p->levels_full == 6 + p->lognw;
+}
+// crb_step_implicit, several beams per wave: the packed kernels exist for 3 .. 5 levels
+bool implicit_pack_shape(const crb_plan* p) {
+    return p->G > 1 && p->lognw == 0 && p->NT == 64 && p->levels_full >= 3 && p->levels_full <= 5;
+}
+bool lean_implicit_enabled() { return !env_set("CRB_DISABLE_LEAN") && !env_set("CRB_DISABLE_LEAN_IMPLICIT"); }
+bool lean_implicit_ok(const crb_plan* p) {
+    return (implicit_group_shape(p) || (implicit_pack_shape(p) && p->stiff_levels >= 3)) && lean_grav_ok(p) && lean_implicit_enabled();
+}
+// crb_solve_controlled: one beam per workgroup of up to 4 waves; the closed loop (fb) in one wave at the levels of M, the
+// implicit scheme at all levels of A
+bool lean_controlled_ok(const crb_plan* p, bool fb) {
+    const bool shape = p->lognw <= 2 && p->NT == (64 << p->lognw) && lean_grav_ok(p) && !env_set("CRB_DISABLE_LEAN");
+    return fb ? (shape && p->lognw == 0 && p->levels >= 1 && p->levels <= 6 && !env_set("CRB_DISABLE_LEAN_FEEDBACK"))
+              : (shape && p->levels_full >= 1 && !env_set("CRB_DISABLE_LEAN_IMPLICIT"));
+}
+// crb_solve_controlled per_wave: beams of 2 .. 32 slots packed G to a wave, implicit scheme through the lean kernel only
+bool controlled_pack_ok(const crb_plan* p, bool fb, bool lean) {
+    return !fb && lean && p->G > 1 && p->lognw == 0 && p->levels_full <= 5;
+}
+// crb_step_rk4_feedback, fused: beams that live in one wave and whose gain fits LDS -- the whole rollout as ONE launch of the
+// general stepper's feedback instantiation (crb_generic.h, FB) instead of eight launches per step
+bool fused_feedback_ok(const crb_plan* p, const void* held) {
+    if (p->lognw != 0 || p->NT != 64 || p->mixed_topology || held) return false;
+    const char* v = env("CRB_FUSED_FEEDBACK");     // 0 = never, 1 = whenever the gain fits LDS, unset = choose
+    if (v && std::atoi(v) == 0) return false;
+    const size_t need = p->dtype == CRB_F64 ? fb_lds_bytes<double>(p->NT, p->G, p->n_free) : fb_lds_bytes<float>(p->NT, p->G, p->n_free);
+    if (need > size_t(144) * 1024) return false;
+    if (v) return true;
+    // a workgroup is ONE wave here: with a gain of more than ~50 KB few of them share a CU, and an ensemble that needs
+    // several rounds of workgroups is faster through the stage-split path (2048 x 27 elements: 125 against 67 us/step;
+    // 64 x 27: 31 against 48; up to 16 elements the fused form wins at every size: 21 against 40 - 48 us/step)
+    const size_t per_cu = (size_t(160) * 1024) / need;
+    const size_t groups = size_t((p->B + p->G - 1) / p->G);
+    return need <= size_t(52) * 1024 || groups <= per_cu * 256;
+}
+// ... and its packed lean form: several beams per wave with 3 .. 5 levels (its right-hand side costs half of the general kernel's)
+template <typename T>
+bool lean_fused_feedback_ok(const crb_plan* p) {
+    return p->G > 1 && lean_step_ok(p) && p->levels >= 3 && p->levels <= 5 && fb_lean_lds_bytes<T>(p->G, p->n_free) <= size_t(144) * 1024 &&
+           !env_set("CRB_DISABLE_LEAN_FEEDBACK");
+}
+// crb_step_rk4_feedback, persistent (crb_loop.h): fp64 plans with one table set and one free-DOF set, beams of 33 .. 128
+// thread-carried nodes, gravity absent or canonical, no held input.  CRB_LOOP=0 / 1: never / whenever eligible; unset:
+// ensembles of at least LOOP_MIN_BEAMS beams (a group of workgroups owns 64 beams: small ensembles leave most of the chip
+// idle and are faster through the stage-split launches).
+constexpr int LOOP_MIN_BEAMS = 512;
+int loop_nb(const crb_plan* p) { return p->lognw == 1 ? 8 : 4; }
+bool loop_shape_ok(const crb_plan* p) {
+    return p->dtype == CRB_F64 && !p->mixed_topology && p->slot_stride == 0 && p->lv_stride == 0 && p->fin_stride == 0 && p->G == 1 &&
+           (p->lognw == 0 || p->lognw == 1) && p->NT == (64 << p->lognw) && p->S > 32 && (p->levels == 5 || p->levels == 6) &&
+           lean_grav_ok(p);
+}
+bool loop_ok(const crb_plan* p, const void* held) {
+    if (!loop_shape_ok(p) || held) return false;
+    if (const char* v = env("CRB_LOOP")) return std::atoi(v) != 0;
+    return p->B >= LOOP_MIN_BEAMS;
+}
+
 template <typename T, int MODE, int LV, bool LEAN>
 int launch_beam_lean(const crb_plan* p, const KParams<T>& k, hipStream_t st) {
     const dim3 grid((p->B + p->G - 1) / p->G), block(p->NT);
@@ -907,34 +1060,12 @@ int launch_beam(const crb_plan* p, const KParams<T>& k, hipStream_t st) {
 #ifdef CRB_FAST_BUILD  // kernel-tuning build (make fast): only the config-3 lean stepper is instantiated
     return fail(CRB_EUNSUPPORTED, "CRB_FAST_BUILD: generic kernels not built");
 #else
-    switch (p->levels) {
-        case 0: return launch_beam_lv<T, MODE, 0>(p, k, st);
-        case 1: return launch_beam_lv<T, MODE, 1>(p, k, st);
-        case 2: return launch_beam_lv<T, MODE, 2>(p, k, st);
-        case 3: return launch_beam_lv<T, MODE, 3>(p, k, st);
-        case 4: return launch_beam_lv<T, MODE, 4>(p, k, st);
-        case 5: return launch_beam_lv<T, MODE, 5>(p, k, st);
-        case 6: return launch_beam_lv<T, MODE, 6>(p, k, st);
-        case 7: return launch_beam_lv<T, MODE, 7>(p, k, st);
-        case 8: return launch_beam_lv<T, MODE, 8>(p, k, st);
-        default: return fail(CRB_EUNSUPPORTED, "unsupported number of cyclic-reduction levels");
-    }
+    return with_levels<8>(p->levels, "unsupported number of cyclic-reduction levels",
+                          [&](auto lv) { return launch_beam_lv<T, MODE, decltype(lv)::value>(p, k, st); });
 #endif
 }
 
-// Fast path of crb_step_rk4: no held input, one beam per workgroup, gravity absent or of the plain
-// cantilever's nearest-neighbour form.  The kernels live in crb_lean.hip (one translation unit per dtype).
-inline bool lean_eligible(const crb_plan* p, const void* held) {
-    const bool grav = (p->flags & CRB_FORCE_GRAVITY) != 0;
-    (void)held;   // (a held input has its own instantiation of the lean stepper)
-    // (G > 1: beams of fewer than 64 slots packed into one wave, the PACK instantiation of the one-wave stepper)
-    const bool packed = p->G > 1 && p->lognw == 0 && p->NT == 64 && std::getenv("CRB_DISABLE_LEAN_PACK") == nullptr;
-    // (beams of more than 64 slots: only the level counts the truncated reduction lands on are built, crb_lean.hip:by_nw)
-    const int lv_long = p->dtype == CRB_F64 ? 5 : 4;
-    const bool levels_ok = p->lognw == 0 ? (p->levels >= 3 && p->levels <= 6) : (p->levels == lv_long || p->levels == lv_long + 1);
-    return (!grav || p->canonical_gravity) && (p->G == 1 || packed) && p->NT == (64 << p->lognw) && p->lognw <= 3 &&
-           levels_ok && std::getenv("CRB_DISABLE_LEAN") == nullptr;
-}
+// the lean stepper (crb_lean.hip, one translation unit per dtype)
 template <typename T>
 int launch_lean(const crb_plan* p, const KParams<T>& k, hipStream_t st) {
 #ifdef CRB_FAST_BUILD   // (make fast: the fp64 config-3 instance only; make fast32: the fp32 config-4 one)
@@ -945,16 +1076,12 @@ int launch_lean(const crb_plan* p, const KParams<T>& k, hipStream_t st) {
 #endif
     else
 #endif
-    HIP_TRY(crb::launch_lean(k, p->B, p->levels, p->lognw, (p->flags & CRB_FORCE_GRAVITY) != 0, p->elem_mode, st));
+    HIP_TRY(crb::launch_lean(k, p->B, p->levels, p->lognw, grav_on(p), p->elem_mode, st));
     return CRB_OK;
 }
 
-// One RK4 stage through the lean machinery (crb_stage_lean_kernel): same eligibility as the lean stepper,
-// except that a per-node input force is part of the stage contract.  Shared-table plans run a bounded
-// number of workgroups, each walking over several beams with the solve tables in registers.
-inline bool stage_lean_eligible(const crb_plan* p) {
-    return lean_eligible(p, nullptr) && p->G == 1 && std::getenv("CRB_DISABLE_LEAN_STAGE") == nullptr;
-}
+// One RK4 stage through the lean machinery (crb_stage_lean_kernel).  Shared-table plans run a bounded number of
+// workgroups, each walking over several beams with the solve tables in registers.
 template <typename T>
 int launch_stage_lean(const crb_plan* p, const KParams<T>& k, hipStream_t st) {
     const bool shared = p->slot_stride == 0 && p->lv_stride == 0 && p->fin_stride == 0;
@@ -963,9 +1090,7 @@ int launch_stage_lean(const crb_plan* p, const KParams<T>& k, hipStream_t st) {
         // one wave per SIMD (256 CUs x 4) / waves per group: measured best at 2048 x 128 (208 us per step
         // against 220 with two waves per SIMD and 236 with one group per beam) -- the table reload per
         // group costs more than the extra latency hiding gains
-        const int resident = 256 * 4 / (1 << p->lognw);
-        const char* env = std::getenv("CRB_STAGE_GROUPS");
-        const int cap = env ? std::atoi(env) : resident;
+        const int cap = int(env_int("CRB_STAGE_GROUPS", 256 * 4 / (1 << p->lognw)));
         if (cap > 0 && groups > cap) groups = cap;
     }
 #ifdef CRB_FAST_BUILD
@@ -976,7 +1101,7 @@ int launch_stage_lean(const crb_plan* p, const KParams<T>& k, hipStream_t st) {
 #endif
     else
 #endif
-    HIP_TRY(crb::launch_stage_lean(k, groups, p->levels, p->lognw, (p->flags & CRB_FORCE_GRAVITY) != 0, p->elem_mode, st));
+    HIP_TRY(crb::launch_stage_lean(k, groups, p->levels, p->lognw, grav_on(p), p->elem_mode, st));
     return CRB_OK;
 }
 
@@ -1061,79 +1186,34 @@ extern "C" int crb_step_rk4(const crb_plan* p, void* x, double t0, double dt, in
     return crb_step_rk4_rec(p, x, t0, dt, n_steps, in, nullptr, t_end, stream);
 }
 
+namespace {
+template <typename T>
+int step_rk4_impl(const crb_plan* p, void* x, double t0, double dt, int n_steps, const Forcing& f, const Recording& r, hipStream_t st) {
+    KParams<T> k = base_params<T>(p);
+    k.x = static_cast<T*>(x);
+    set_io(k, f, &r);
+    k.t0 = t0; k.dt = dt; k.n_steps = n_steps;
+    arm_status(p, k, n_steps);
+    if (lean_step_ok(p)) return launch_lean<T>(p, k, st);
+    return launch_beam<T, MODE_STEP>(p, k, st);
+}
+}  // namespace
+
 extern "C" int crb_step_rk4_rec(const crb_plan* p, void* x, double t0, double dt, int n_steps, const crb_input_desc* in,
                                 const crb_record_desc* rec, double* t_end, void* stream) {
     if (int rc = need_device(p, "crb_step_rk4")) return rc;
-    int rec_slot = -1, rec_comp = 0, rec_every = 1, rec_n = 0;
-    void* rec_out = nullptr;
-    if (rec && rec->node == CRB_RECORD_ALL) {   // whole-state snapshots
-        if (rec->every < 1 || !rec->out) return fail(CRB_EINVAL, "crb_step_rk4_rec: bad record description");
-        rec_n = n_steps / rec->every;
-        if (rec_n > 0) { rec_slot = REC_ALL_SLOTS; rec_every = rec->every; rec_out = rec->out; }
-    } else if (rec) {
-        if (rec->plane < 0 || rec->plane > 1 || rec->node < 0 || rec->node >= p->n_node || rec->dof < 0 || rec->dof > 2 ||
-            rec->every < 1 || !rec->out)
-            return fail(CRB_EINVAL, "crb_step_rk4_rec: bad record description");
-        rec_n = n_steps / rec->every;
-        if (rec->node - p->off >= 0 && rec_n > 0) {  // (the dropped FIXED node 0 records nothing: it is 0 forever)
-            rec_slot = rec->node - p->off; rec_comp = rec->plane * 3 + rec->dof; rec_every = rec->every; rec_out = rec->out;
-        }
-    }
+    Recording r;
+    if (int rc = decode_record(p, rec, n_steps, true, "crb_step_rk4", &r)) return rc;
     if (!x) return fail(CRB_EINVAL, "crb_step_rk4: null state");
     if (n_steps < 0) return fail(CRB_EINVAL, "crb_step_rk4: n_steps must be >= 0");
     if (!(dt > 0)) return fail(CRB_EINVAL, "crb_step_rk4: dt must be positive");
-    int imp_slot = -1, imp_dof = 0;
-    double duration = 0.0;
-    const void* amp = nullptr;
-    const void* held = nullptr;
-    if (in) {
-        held = in->f_held;
-        if (in->kind == CRB_INPUT_IMPULSE) {
-            if (in->node < 0 || in->node >= p->n_node || in->dof < 0 || in->dof > 2)
-                return fail(CRB_EINVAL, "crb_step_rk4: impulse node/dof out of range");
-            if (!in->amp) return fail(CRB_EINVAL, "crb_step_rk4: impulse amplitude array is null");
-            if (!p->any_free[3 * in->node + in->dof])   // (mixed ensembles: a beam in which the DOF is constrained ignores it)
-                return fail(CRB_EINVAL, "crb_step_rk4: impulse targets a constrained DOF");
-            imp_slot = in->node - p->off;
-            imp_dof = in->dof;
-            duration = in->duration;
-            amp = in->amp;
-        } else if (in->kind != CRB_INPUT_NONE) {
-            return fail(CRB_EINVAL, "crb_step_rk4: unknown input kind");
-        }
-    }
-    // the clock the kernel will hold after n_steps additions (same fp64 additions on the host)
-    if (t_end) {
-        double t = t0;
-        for (int i = 0; i < n_steps; ++i) t = t + dt;
-        *t_end = t;
-    }
+    Forcing f;
+    if (int rc = decode_input(p, in, "crb_step_rk4", &f)) return rc;
+    if (t_end) *t_end = clock_after(t0, dt, n_steps);
     if (n_steps == 0) return CRB_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (p->dtype == CRB_F64) {
-        KParams<double> k = base_params<double>(p);
-        k.x = static_cast<double*>(x);
-        k.u_held = static_cast<const double*>(held);
-        k.amp = static_cast<const double*>(amp);
-        k.imp_slot = imp_slot; k.imp_dof = imp_dof; k.duration = duration;
-        k.imp_node_b = (in && in->kind == CRB_INPUT_IMPULSE) ? in->node_b : nullptr;
-        k.t0 = t0; k.dt = dt; k.n_steps = n_steps;
-    arm_status(p, k, n_steps);
-        k.rec_out = static_cast<double*>(rec_out); k.rec_slot = rec_slot; k.rec_comp = rec_comp; k.rec_every = rec_every; k.rec_n = rec_n;
-        if (lean_eligible(p, held)) return launch_lean<double>(p, k, st);
-        return launch_beam<double, MODE_STEP>(p, k, st);
-    }
-    KParams<float> k = base_params<float>(p);
-    k.x = static_cast<float*>(x);
-    k.u_held = static_cast<const float*>(held);
-    k.amp = static_cast<const float*>(amp);
-    k.imp_slot = imp_slot; k.imp_dof = imp_dof; k.duration = duration;
-    k.imp_node_b = (in && in->kind == CRB_INPUT_IMPULSE) ? in->node_b : nullptr;
-    k.t0 = t0; k.dt = dt; k.n_steps = n_steps;
-    arm_status(p, k, n_steps);
-    k.rec_out = static_cast<float*>(rec_out); k.rec_slot = rec_slot; k.rec_comp = rec_comp; k.rec_every = rec_every; k.rec_n = rec_n;
-    if (lean_eligible(p, held)) return launch_lean<float>(p, k, st);
-    return launch_beam<float, MODE_STEP>(p, k, st);
+    return p->dtype == CRB_F64 ? step_rk4_impl<double>(p, x, t0, dt, n_steps, f, r, st)
+                               : step_rk4_impl<float>(p, x, t0, dt, n_steps, f, r, st);
 }
 
 // ------------------------------------------------------------------ host-vector entry points (single-beam closures)
@@ -1203,7 +1283,7 @@ extern "C" int crb_rhs_host(const crb_plan* p, const double* x_red, const double
     k.out = p->d_stage + B * 3 * n;
     k.red_map = p->d_red_map;
     k.n_red = int(n);
-    const bool flagged = (p->B + p->G - 1) / p->G == 1 && !p->host_sync;
+    const bool flagged = (p->B + p->G - 1) / p->G == 1;
     if (flagged) {
         k.done_flag = reinterpret_cast<unsigned long long*>(p->d_stage + B * 5 * n);
         k.done_seq = ++p->host_seq;
@@ -1225,7 +1305,7 @@ extern "C" int crb_internal_force_host(const crb_plan* p, const double* q_red, d
     k.out = p->d_stage + B * 3 * n;
     k.red_map = p->d_red_map;
     k.n_red = int(n);
-    const bool flagged = (p->B + p->G - 1) / p->G == 1 && !p->host_sync;
+    const bool flagged = (p->B + p->G - 1) / p->G == 1;
     if (flagged) {
         k.done_flag = reinterpret_cast<unsigned long long*>(p->d_stage + B * 5 * n);
         k.done_seq = ++p->host_seq;
@@ -1291,17 +1371,14 @@ int stiff_tables(const crb_plan* p, double alpha, hipStream_t st) {
     // for the step sizes the examples use (h = 1e-4: the stride-32 multipliers of a 256-node Nitinol rod are ~1e-19) that is
     // 5 levels instead of 8; large steps (h = 1e-3) keep them all.  One stream synchronisation per new step size.
     int used = lf;
-    if (lf > 0 && std::getenv("CRB_STIFF_ALL_LEVELS") == nullptr) {
+    if (lf > 0 && !env_set("CRB_STIFF_ALL_LEVELS")) {
         std::vector<double> norms(static_cast<size_t>(lf));
         HIP_TRY(hipMemcpyAsync(norms.data(), in.dNormScratch.p, size_t(lf) * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         while (used > 0 && norms[size_t(used) - 1] < std::ldexp(1.0, -53)) --used;
-        // (the lean kernels exist for 5 ... full levels)
-        const bool lean_shape = p->G == 1 && p->lognw <= 2 && p->NT == (64 << p->lognw) && lf == 6 + p->lognw;
-        if (lean_shape && used < 5 && std::getenv("CRB_DISABLE_LEAN") == nullptr && std::getenv("CRB_DISABLE_LEAN_IMPLICIT") == nullptr) used = 5;
-        // (several beams per wave: the packed lean kernels exist for 3 ... 5 levels)
-        const bool pack_shape = p->G > 1 && p->lognw == 0 && p->NT == 64 && lf >= 3 && lf <= 5;
-        if (pack_shape && used < 3) used = 3;
+        // (the lean kernels exist for 5 ... full levels, the packed ones for 3 ... 5)
+        if (implicit_group_shape(p) && used < 5 && lean_implicit_enabled()) used = 5;
+        if (implicit_pack_shape(p) && used < 3) used = 3;
         if (used < lf) {   // the final block inverses after `used` levels
             a.fin_level = used;
             hipLaunchKernelGGL((crb_assemble_kernel<T>), dim3(nd), dim3(in.threads), in.smem, st, a);
@@ -1335,37 +1412,20 @@ int launch_implicit(const crb_plan* p, const KParams<T>& k, const StiffParams<T>
 #ifdef CRB_FAST_BUILD
     return fail(CRB_EUNSUPPORTED, "CRB_FAST_BUILD: implicit stepper not built");
 #else
-    // the lean form: one beam per workgroup of 1 / 2 / 4 waves with ALL its reduction levels, gravity absent or canonical
-    const bool grav = (p->flags & CRB_FORCE_GRAVITY) != 0;
-    const bool one_per_group = p->G == 1 && p->lognw <= 2 && p->NT == (64 << p->lognw) && p->levels_full == 6 + p->lognw;
-    const bool packed = p->G > 1 && p->lognw == 0 && p->NT == 64 && p->levels_full >= 3 && p->levels_full <= 5 && p->stiff_levels >= 3 &&
-                        std::getenv("CRB_DISABLE_LEAN_PACK") == nullptr;
-    if ((one_per_group || packed) && (!grav || p->canonical_gravity) &&
-        std::getenv("CRB_DISABLE_LEAN") == nullptr && std::getenv("CRB_DISABLE_LEAN_IMPLICIT") == nullptr) {
+    if (lean_implicit_ok(p)) {
         // one wave per SIMD (the tables of A fill the register file): 256 CUs x 4 / waves per beam workgroups are resident
-        int groups = (p->B + p->G - 1) / p->G;
+        const bool grav = grav_on(p);
         const bool shared = p->slot_stride == 0 && q.alv_stride == 0 && q.afin_stride == 0;
         int resident = 256 * 4 / (1 << p->lognw) * implicit_lean_minw(p->stiff_levels, grav, p->lognw);   // (waves per SIMD: crb_stiff.h)
-        if (const char* env = std::getenv("CRB_LEAN_MAX_GROUPS")) resident = std::atoi(env) > 0 ? std::atoi(env) : resident;   // (tests)
-        if (shared && groups > resident) {
-            const int rounds = (groups + resident - 1) / resident;
-            groups = (groups + rounds - 1) / rounds;
-        }
-        HIP_TRY(crb::launch_implicit_lean(k, q, groups, p->stiff_levels, p->lognw, grav, p->elem_mode, st));
+        if (const int cap = int(env_int("CRB_LEAN_MAX_GROUPS", 0)); cap > 0) resident = cap;   // (tests)
+        const int groups = (p->B + p->G - 1) / p->G;
+        HIP_TRY(crb::launch_implicit_lean(k, q, shared ? walk_grid(groups, resident) : groups, p->stiff_levels, p->lognw, grav,
+                                          p->elem_mode, st));
         return CRB_OK;
     }
-    switch (p->stiff_levels) {   // (the levels of A whose multipliers matter, stiff_tables)
-        case 0: return launch_implicit_lv<T, 0>(p, k, q, st);
-        case 1: return launch_implicit_lv<T, 1>(p, k, q, st);
-        case 2: return launch_implicit_lv<T, 2>(p, k, q, st);
-        case 3: return launch_implicit_lv<T, 3>(p, k, q, st);
-        case 4: return launch_implicit_lv<T, 4>(p, k, q, st);
-        case 5: return launch_implicit_lv<T, 5>(p, k, q, st);
-        case 6: return launch_implicit_lv<T, 6>(p, k, q, st);
-        case 7: return launch_implicit_lv<T, 7>(p, k, q, st);
-        case 8: return launch_implicit_lv<T, 8>(p, k, q, st);
-        default: return fail(CRB_EUNSUPPORTED, "crb_step_implicit: beams of more than 256 thread-carried nodes are not supported");
-    }
+    // (the levels of A whose multipliers matter, stiff_tables)
+    return with_levels<8>(p->stiff_levels, "crb_step_implicit: beams of more than 256 thread-carried nodes are not supported",
+                          [&](auto lv) { return launch_implicit_lv<T, decltype(lv)::value>(p, k, q, st); });
 #endif
 }
 
@@ -1383,25 +1443,14 @@ int launch_implicit_damped(const crb_plan* p, const KParams<T>& k, const StiffPa
     return fail(CRB_EUNSUPPORTED, "CRB_FAST_BUILD: implicit stepper not built");
 #else
     if (p->NT > 256) return fail(CRB_EUNSUPPORTED, "crb_step_implicit: beams of more than 256 thread-carried nodes are not supported");
-    switch (p->stiff_levels) {
-        case 0: return launch_implicit_damped_lv<T, 0>(p, k, q, st);
-        case 1: return launch_implicit_damped_lv<T, 1>(p, k, q, st);
-        case 2: return launch_implicit_damped_lv<T, 2>(p, k, q, st);
-        case 3: return launch_implicit_damped_lv<T, 3>(p, k, q, st);
-        case 4: return launch_implicit_damped_lv<T, 4>(p, k, q, st);
-        case 5: return launch_implicit_damped_lv<T, 5>(p, k, q, st);
-        case 6: return launch_implicit_damped_lv<T, 6>(p, k, q, st);
-        case 7: return launch_implicit_damped_lv<T, 7>(p, k, q, st);
-        case 8: return launch_implicit_damped_lv<T, 8>(p, k, q, st);
-        default: return fail(CRB_EUNSUPPORTED, "crb_step_implicit: beams of more than 256 thread-carried nodes are not supported");
-    }
+    return with_levels<8>(p->stiff_levels, "crb_step_implicit: beams of more than 256 thread-carried nodes are not supported",
+                          [&](auto lv) { return launch_implicit_damped_lv<T, decltype(lv)::value>(p, k, q, st); });
 #endif
 }
 
 template <typename T>
-int step_implicit_impl(const crb_plan* p, void* x, double t0, double h, int n_steps, int n_iter, double rho, const crb_input_desc* in,
-                       int imp_slot, int imp_dof, double duration, const void* amp, const void* held, void* rec_out,
-                       int rec_slot, int rec_comp, int rec_every, int rec_n, hipStream_t st) {
+int step_implicit_impl(const crb_plan* p, void* x, double t0, double h, int n_steps, int n_iter, double rho, const Forcing& f,
+                       const Recording& rec, hipStream_t st) {
     const bool damped = rho < 1.0;
     // generalised-alpha coefficients (crb_stiff.h: StiffParams); rho = 1 is the midpoint rule with kappa = h^2 / 4
     const double am_ = (2.0 * rho - 1.0) / (rho + 1.0), af_ = rho / (rho + 1.0);
@@ -1410,13 +1459,9 @@ int step_implicit_impl(const crb_plan* p, void* x, double t0, double h, int n_st
     if (int rc = stiff_tables<T>(p, kappa, st)) return rc;
     KParams<T> k = base_params<T>(p);
     k.x = static_cast<T*>(x);
-    k.u_held = static_cast<const T*>(held);
-    k.amp = static_cast<const T*>(amp);
-    k.imp_slot = imp_slot; k.imp_dof = imp_dof; k.duration = duration;
-    k.imp_node_b = (in && in->kind == CRB_INPUT_IMPULSE) ? in->node_b : nullptr;
+    set_io(k, f, &rec);
     k.t0 = t0; k.dt = h; k.n_steps = n_steps;
     arm_status(p, k, n_steps);
-    k.rec_out = static_cast<T*>(rec_out); k.rec_slot = rec_slot; k.rec_comp = rec_comp; k.rec_every = rec_every; k.rec_n = rec_n;
     StiffParams<T> q;
     q.a_levels = static_cast<const T*>(p->d_alevels);
     q.a_final = static_cast<const T*>(p->d_afinal);
@@ -1431,10 +1476,8 @@ int step_implicit_impl(const crb_plan* p, void* x, double t0, double h, int n_st
     {
         KParams<T> r = base_params<T>(p);
         r.x = static_cast<T*>(x);
-        r.u_held = static_cast<const T*>(held);
         r.out = static_cast<T*>(p->d_rhs0);
-        r.amp = static_cast<const T*>(amp);
-        r.imp_slot = imp_slot; r.imp_dof = imp_dof; r.duration = duration; r.imp_node_b = k.imp_node_b;
+        set_io(r, f);
         r.t0 = t0;
         if (int rc = launch_beam<T, MODE_RHS>(p, r, st)) return rc;
     }
@@ -1464,45 +1507,13 @@ extern "C" int crb_step_implicit_damped(const crb_plan* p, void* x, double t0, d
     if (n_iter < 1) return fail(CRB_EINVAL, "crb_step_implicit: n_iter must be >= 1");
     if (p->dtype != CRB_F64)   // cond(M + h^2/4 K0) is 1e6 ... 1e9 at the step sizes this stepper is for
         return fail(CRB_EUNSUPPORTED, "crb_step_implicit: the implicit stepper needs an fp64 plan (the iteration matrix is too ill-conditioned for fp32)");
-    int rec_slot = -1, rec_comp = 0, rec_every = 1, rec_n = 0;
-    void* rec_out = nullptr;
-    if (rec && rec->node == CRB_RECORD_ALL) {
-        if (rec->every < 1 || !rec->out) return fail(CRB_EINVAL, "crb_step_implicit: bad record description");
-        rec_n = n_steps / rec->every;
-        if (rec_n > 0) { rec_slot = REC_ALL_SLOTS; rec_every = rec->every; rec_out = rec->out; }
-    } else if (rec) {
-        if (rec->plane < 0 || rec->plane > 1 || rec->node < 0 || rec->node >= p->n_node || rec->dof < 0 || rec->dof > 2 ||
-            rec->every < 1 || !rec->out)
-            return fail(CRB_EINVAL, "crb_step_implicit: bad record description");
-        rec_n = n_steps / rec->every;
-        if (rec->node - p->off >= 0 && rec_n > 0) {
-            rec_slot = rec->node - p->off; rec_comp = rec->plane * 3 + rec->dof; rec_every = rec->every; rec_out = rec->out;
-        }
-    }
-    int imp_slot = -1, imp_dof = 0;
-    double duration = 0.0;
-    const void* amp = nullptr;
-    const void* held = nullptr;
-    if (in) {
-        held = in->f_held;
-        if (in->kind == CRB_INPUT_IMPULSE) {
-            if (in->node < 0 || in->node >= p->n_node || in->dof < 0 || in->dof > 2 || !in->amp ||
-                !p->any_free[3 * in->node + in->dof])
-                return fail(CRB_EINVAL, "crb_step_implicit: bad impulse description");
-            imp_slot = in->node - p->off; imp_dof = in->dof; duration = in->duration; amp = in->amp;
-        } else if (in->kind != CRB_INPUT_NONE) {
-            return fail(CRB_EINVAL, "crb_step_implicit: unknown input kind");
-        }
-    }
-    if (t_end) {
-        double t = t0;
-        for (int i = 0; i < n_steps; ++i) t = t + h;
-        *t_end = t;
-    }
+    Recording r;
+    if (int rc = decode_record(p, rec, n_steps, true, "crb_step_implicit", &r)) return rc;
+    Forcing f;
+    if (int rc = decode_input(p, in, "crb_step_implicit", &f)) return rc;
+    if (t_end) *t_end = clock_after(t0, h, n_steps);
     if (n_steps == 0) return CRB_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    return step_implicit_impl<double>(p, x, t0, h, n_steps, n_iter, rho_inf, in, imp_slot, imp_dof, duration, amp, held, rec_out, rec_slot,
-                                      rec_comp, rec_every, rec_n, st);
+    return step_implicit_impl<double>(p, x, t0, h, n_steps, n_iter, rho_inf, f, r, static_cast<hipStream_t>(stream));
 }
 
 // ------------------------------------------------------------------ step-size control in the kernel (crb_ctrl.h)
@@ -1579,35 +1590,23 @@ extern "C" int crb_solve_controlled(const crb_plan* p, void* x, double t0, doubl
     const int n_iter = ctl->n_iter > 0 ? ctl->n_iter : 1;
     const int rungs = ctl->max_rungs > 0 ? ctl->max_rungs : 15;   // up to 2^14 fine steps per piece
     if (rungs < 2 || rungs > 24) return fail(CRB_EINVAL, "crb_solve_controlled: max_rungs must be in 2 .. 24");
+    Forcing f;
+    if (int rc = decode_input(p, in, "crb_solve_controlled", &f)) return rc;
     if (fb) {
         if (p->mixed_topology) return fail(CRB_EUNSUPPORTED, "crb_solve_controlled: one gain matrix for the ensemble needs one free-DOF set");
-        if (in && in->f_held) return fail(CRB_EUNSUPPORTED, "crb_solve_controlled: the closed loop runs without a held force");
+        if (f.held) return fail(CRB_EUNSUPPORTED, "crb_solve_controlled: the closed loop runs without a held force");
         if (p->levels > 6) return fail(CRB_EUNSUPPORTED, "crb_solve_controlled: unsupported number of cyclic-reduction levels");
         if (ctrl_lds_bytes<double>(p->NT, true, p->n_free) > size_t(160) * 1024)
             return fail(CRB_EUNSUPPORTED, "crb_solve_controlled: the gain matrix does not fit the LDS (beams of up to ~30 elements); use crb_step_rk4_feedback");
     } else if (ref) {
         return fail(CRB_EINVAL, "crb_solve_controlled: a reference without a gain");
     }
-    int imp_slot = -1, imp_dof = 0;
-    double t_switch = 0.0;
-    bool impulse = false;
-    const void* amp = nullptr;
-    const void* held = nullptr;
-    if (in) {
-        held = in->f_held;
-        if (in->kind == CRB_INPUT_IMPULSE) {
-            if (in->node < 0 || in->node >= p->n_node || in->dof < 0 || in->dof > 2 || !in->amp || !p->any_free[3 * in->node + in->dof])
-                return fail(CRB_EINVAL, "crb_solve_controlled: bad impulse description");
-            imp_slot = in->node - p->off; imp_dof = in->dof; t_switch = in->duration; amp = in->amp;
-            impulse = true;
-        } else if (in->kind != CRB_INPUT_NONE) {
-            return fail(CRB_EINVAL, "crb_solve_controlled: unknown input kind");
-        }
-    }
     if (n_intervals == 0) return CRB_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
 
     // the pieces: whole t_eval intervals, the one the impulse ends in cut at that instant (inside a piece the input is constant)
+    const bool impulse = f.impulse;
+    const double t_switch = f.duration;
     std::vector<crb::CtrlPiece> pieces;
     pieces.reserve(size_t(n_intervals) + 1);
     double lens[crb::CTRL_MAX_LADDERS] = {dt_eval, 0.0, 0.0};
@@ -1682,10 +1681,7 @@ extern "C" int crb_solve_controlled(const crb_plan* p, void* x, double t0, doubl
     KParams<double> k = base_params<double>(p);
     k.G = 1;
     k.x = static_cast<double*>(x);
-    k.u_held = static_cast<const double*>(held);
-    k.amp = static_cast<const double*>(amp);
-    k.imp_slot = imp_slot; k.imp_dof = imp_dof; k.duration = t_switch;
-    k.imp_node_b = impulse ? in->node_b : nullptr;
+    set_io(k, f);
     k.t0 = t0;
     arm_status(p, k, 1);   // (per-beam status, crb_plan_set_status: a controlled launch counts as one step of the ensemble)
     if (fb) {
@@ -1696,50 +1692,144 @@ extern "C" int crb_solve_controlled(const crb_plan* p, void* x, double t0, doubl
         k.fb_ref = static_cast<const double*>(ref);
     }
     const int threads = p->NT;
-    // the lean iteration (crb_stiff.h) where the plan allows it: gravity absent or of the plain cantilever's form
-    const bool grav = (p->flags & CRB_FORCE_GRAVITY) != 0;
-    const bool lean_shape = p->lognw <= 2 && threads == (64 << p->lognw) && (!grav || p->canonical_gravity) && std::getenv("CRB_DISABLE_LEAN") == nullptr;
-    const bool lean = fb ? (lean_shape && p->lognw == 0 && p->levels >= 1 && p->levels <= 6 && std::getenv("CRB_DISABLE_LEAN_FEEDBACK") == nullptr)
-                         : (lean_shape && p->levels_full >= 1 && std::getenv("CRB_DISABLE_LEAN_IMPLICIT") == nullptr);
+    // the lean iteration (crb_stiff.h) where the plan allows it
+    const bool lean = lean_controlled_ok(p, fb);
     const int lean_lognw = lean ? p->lognw : -1;
     // per_wave: short beams packed G to a wave, one step sequence per wave (the worst of its beams decides)
-    const bool pack = ctl->per_wave != 0 && !fb && lean && p->G > 1 && p->lognw == 0 && p->levels_full <= 5;
+    const bool pack = ctl->per_wave != 0 && controlled_pack_ok(p, fb, lean);
     if (ctl->per_wave != 0 && !pack)
         return fail(CRB_EUNSUPPORTED, "crb_solve_controlled: per_wave packs beams of 2 .. 32 thread-carried nodes of the implicit scheme (gravity absent or canonical)");
     if (pack) k.G = p->G;
-    HIP_TRY(crb::launch_controlled(k, q, fb ? p->levels : p->levels_full, fb, lean_lognw, grav, pack, threads,
+    HIP_TRY(crb::launch_controlled(k, q, fb ? p->levels : p->levels_full, fb, lean_lognw, grav_on(p), pack, threads,
                                    ctrl_lds_bytes<double>(threads, fb, p->n_free, fb ? -1 : lean_lognw), st));
     return CRB_OK;
 }
 
-static int rk4_stage_impl(const crb_plan* p, void* x, const void* xs, void* acc, void* xs_next, const void* u_stage, int stage,
-                         double t_stage, const double* t_dev, double dt, const crb_input_desc* in, void* stream);
-
 namespace {
-// The persistent closed-loop stepper (crb_loop.h): fp64 plans with one table set and one free-DOF set, beams of 33 .. 128
-// thread-carried nodes, gravity absent or of the plain cantilever's form, no held input.  CRB_LOOP=0 / 1 in the
-// environment: never / whenever eligible; unset: ensembles of at least LOOP_MIN_BEAMS beams (a group of workgroups owns
-// 64 beams: small ensembles leave most of the chip idle and are faster through the stage-split launches).
-constexpr int LOOP_MIN_BEAMS = 512;
-int loop_nb(const crb_plan* p) { return p->lognw == 1 ? 8 : 4; }
-bool loop_shape_ok(const crb_plan* p) {
-    const bool grav = (p->flags & CRB_FORCE_GRAVITY) != 0;
-    return p->dtype == CRB_F64 && !p->mixed_topology && p->slot_stride == 0 && p->lv_stride == 0 && p->fin_stride == 0 && p->G == 1 &&
-           (p->lognw == 0 || p->lognw == 1) && p->NT == (64 << p->lognw) && p->S > 32 && (p->levels == 5 || p->levels == 6) &&
-           (!grav || p->canonical_gravity);
+// One RK4 stage of the stage-split stepper (crb_rk4_stage) with its input force u_stage, which takes the place of the held
+// force: the forcing's f_held is not read here
+template <typename T>
+int rk4_stage_impl(const crb_plan* p, void* x, const void* xs, void* acc, void* xs_next, const void* u_stage, int stage,
+                   double t_stage, double dt, const Forcing& f, hipStream_t st) {
+    KParams<T> k = base_params<T>(p);
+    k.x = static_cast<T*>(x); k.xs = static_cast<const T*>(xs); k.acc = static_cast<T*>(acc);
+    k.out = static_cast<T*>(xs_next);
+    set_io(k, f);
+    k.u_held = static_cast<const T*>(u_stage);
+    k.stage = stage; k.t0 = t_stage; k.dt = dt;
+    if (stage == 3) arm_status(p, k, 1);
+    if (lean_stage_ok(p)) return launch_stage_lean<T>(p, k, st);
+    return launch_beam<T, MODE_STAGE>(p, k, st);
 }
-bool loop_eligible(const crb_plan* p, const crb_input_desc* in) {
-    if (!loop_shape_ok(p) || (in && in->f_held)) return false;
-    const char* env = std::getenv("CRB_LOOP");
-    if (env) return std::atoi(env) != 0;
-    return p->B >= LOOP_MIN_BEAMS;
+int rk4_stage(const crb_plan* p, void* x, const void* xs, void* acc, void* xs_next, const void* u_stage, int stage, double t_stage,
+              double dt, const Forcing& f, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return p->dtype == CRB_F64 ? rk4_stage_impl<double>(p, x, xs, acc, xs_next, u_stage, stage, t_stage, dt, f, st)
+                               : rk4_stage_impl<float>(p, x, xs, acc, xs_next, u_stage, stage, t_stage, dt, f, st);
+}
+
+// The stage-split closed loop: per RK4 stage the feedback force of the stage state (force(xs, u): one GEMM over the ensemble,
+// or one per gain group) and one stage launch.  work: the accumulator, two stage states and the force.
+template <typename Force>
+int feedback_rollout(const crb_plan* p, void* x, double t0, double dt, int n_steps, const Forcing& f, void* work, Force force,
+                     void* stream) {
+    const size_t state = size_t(p->B) * 2 * p->n_node * 4 * (p->dtype == CRB_F64 ? sizeof(double) : sizeof(float));
+    char* w = static_cast<char*>(work);
+    void* acc = w;
+    void* bufs[2] = {w + state, w + 2 * state};
+    void* u = w + 3 * state;
+    // entries of u that no GEMM writes (constrained DOFs, beams without a gain) must read as zero
+    HIP_TRY(hipMemsetAsync(u, 0, state / 2, static_cast<hipStream_t>(stream)));
+    double t = t0;
+    for (int s = 0; s < n_steps; ++s) {
+        const double th = t + 0.5 * dt, t1 = t + dt;   // same clock convention as crb_step_rk4
+        const double ts[4] = {t, th, th, t1};
+        const void* cur = x;
+        for (int stage = 0; stage < 4; ++stage) {
+            if (int rc = force(cur, u)) return rc;
+            void* nxt = bufs[stage & 1];
+            if (int rc = rk4_stage(p, x, cur, acc, nxt, u, stage, ts[stage], dt, f, stream)) return rc;
+            cur = nxt;
+        }
+        t = t + dt;
+    }
+    return CRB_OK;
+}
+
+template <typename T, int LV>
+int launch_fused_feedback_lv(const crb_plan* p, const KParams<T>& k, hipStream_t st) {
+    const dim3 grid((p->B + p->G - 1) / p->G), block(p->NT);
+    const size_t smem = fb_lds_bytes<T>(p->NT, p->G, p->n_free);
+    if (int rc = allow_lds(crb_beam_kernel<T, MODE_STEP, LV, 64, 1, false, true>, smem)) return rc;
+    hipLaunchKernelGGL((crb_beam_kernel<T, MODE_STEP, LV, 64, 1, false, true>), grid, block, smem, st, k);
+    HIP_TRY(hipGetLastError());
+    return CRB_OK;
+}
+template <typename T>
+int fused_feedback_impl(const crb_plan* p, void* x, double t0, double dt, int n_steps, const void* gain, const void* ref,
+                        const Forcing& f, hipStream_t st) {
+#ifdef CRB_FAST_BUILD
+    return fail(CRB_EUNSUPPORTED, "CRB_FAST_BUILD: generic kernels not built");
+#else
+    if (int rc = ensure_red_map(p)) return rc;
+    KParams<T> k = base_params<T>(p);
+    k.x = static_cast<T*>(x);
+    k.t0 = t0; k.dt = dt; k.n_steps = n_steps;
+    arm_status(p, k, n_steps);
+    const Recording none;
+    set_io(k, f, &none);
+    k.red_map = p->d_red_map;
+    k.n_red = p->n_free;
+    k.fb_gain = static_cast<const T*>(gain);
+    k.fb_ref = static_cast<const T*>(ref);
+    if (lean_fused_feedback_ok<T>(p)) {
+        HIP_TRY(crb::launch_lean_feedback(k, p->B, p->levels, grav_on(p), st));
+        return CRB_OK;
+    }
+    // (a beam inside one wave: at most 6 levels)
+    return with_levels<6>(p->levels, "crb_step_rk4_feedback: unsupported number of cyclic-reduction levels",
+                          [&](auto lv) { return launch_fused_feedback_lv<T, decltype(lv)::value>(p, k, st); });
+#endif
+}
+
+int loop_feedback(const crb_plan* p, void* x, double t0, double dt, int n_steps, const void* gain, const void* ref, const Forcing& f,
+                  void* work, hipStream_t st) {
+    if (int rc = ensure_red_map(p)) return rc;
+    const int nb = loop_nb(p), n_rb = (p->B + 63) / 64;
+    const crb::LoopWork lay = crb::loop_work_layout(nb, n_rb < crb::LOOP_MAX_GROUPS ? n_rb : crb::LOOP_MAX_GROUPS);
+    char* w = static_cast<char*>(work);
+    crb::LoopParams<double> P;
+    std::memset(&P, 0, sizeof(P));
+    P.k = base_params<double>(p);
+    P.k.x = static_cast<double*>(x);
+    P.k.t0 = t0; P.k.dt = dt; P.k.n_steps = n_steps;
+    arm_status(p, P.k, n_steps);
+    set_io(P.k, f);
+    P.ref = static_cast<const double*>(ref);
+    P.red_map = p->d_red_map;
+    P.n_red = p->n_free;
+    P.sync = reinterpret_cast<unsigned*>(w);
+    P.kfrag = reinterpret_cast<const double*>(w + lay.kfrag);
+    P.ebuf = reinterpret_cast<double*>(w + lay.ebuf);
+    P.ubuf = reinterpret_cast<double*>(w + lay.ubuf);
+    P.ownbuf = reinterpret_cast<double*>(w + lay.ownbuf);
+    P.n_rb = n_rb;
+    P.fences = int(env_int("CRB_LOOP_FENCES", 0));
+    P.timeout = (unsigned long long)env_int("CRB_LOOP_TIMEOUT_MS", 2000) * 100000ull;   // 100 MHz ticks
+    // every polled word starts at zero, in every call
+    HIP_TRY(hipMemsetAsync(w, 0, size_t(crb::LOOP_SYNC_WORDS) * sizeof(unsigned), st));
+    const hipError_t e = p->lognw == 1 ? crb::launch_loop_long(P, static_cast<const double*>(gain), p->levels, grav_on(p), p->elem_mode, st)
+                                       : crb::launch_loop_short(P, static_cast<const double*>(gain), p->levels, grav_on(p), p->elem_mode, st);
+    if (e != hipSuccess) return fail(CRB_EHIP, std::string("crb_step_rk4_feedback (persistent stepper): ") + hipGetErrorString(e));
+    p->loop_used = true;
+    return CRB_OK;
 }
 }  // namespace
 
 extern "C" size_t crb_feedback_work_bytes(const crb_plan* p) {
     if (!p) return 0;
     const size_t state = size_t(p->B) * 2 * p->n_node * 4 * (p->dtype == CRB_F64 ? sizeof(double) : sizeof(float)), force = state / 2;
-    size_t need = 3 * state + force + 256;   // + the device clock of the replayed step
+    size_t need = 3 * state + force;
     if (loop_shape_ok(p)) {
         const int n_rb = (p->B + 63) / 64;
         const size_t loop = crb::loop_work_layout(loop_nb(p), n_rb < crb::LOOP_MAX_GROUPS ? n_rb : crb::LOOP_MAX_GROUPS).total;
@@ -1748,11 +1838,10 @@ extern "C" size_t crb_feedback_work_bytes(const crb_plan* p) {
     return need;
 }
 
-static bool fused_feedback_eligible(const crb_plan* p, const crb_input_desc* in);
 extern "C" int crb_feedback_path(const crb_plan* p) {
     if (!p || p->device < 0) return 0;
-    if (loop_eligible(p, nullptr)) return 2;
-    return fused_feedback_eligible(p, nullptr) ? 1 : 0;
+    if (loop_ok(p, nullptr)) return 2;
+    return fused_feedback_ok(p, nullptr) ? 1 : 0;
 }
 
 extern "C" int crb_feedback_status(const crb_plan* p, const void* work, int32_t* status, void* stream) {
@@ -1768,245 +1857,27 @@ extern "C" int crb_feedback_status(const crb_plan* p, const void* work, int32_t*
     return CRB_OK;
 }
 
-namespace {
-// the eight launches of one closed-loop RK4 step; t_dev != nullptr: stage times come from the device clock
-int feedback_step_launches(const crb_plan* p, void* x, void* acc, void* const bufs[2], void* u, const void* gain, const void* ref,
-                           const crb_input_desc* in, double t, const double* t_dev, double dt, void* stream) {
-    const double th = t + 0.5 * dt, t1 = t + dt;   // same clock convention as crb_step_rk4
-    const double ts[4] = {t, th, th, t1};
-    const void* cur = x;
-    for (int stage = 0; stage < 4; ++stage) {
-        if (int rc = crb_feedback_force(p, cur, gain, ref, u, stream)) return rc;
-        void* nxt = bufs[stage & 1];
-        if (int rc = rk4_stage_impl(p, x, cur, acc, nxt, u, stage, ts[stage], t_dev, dt, in, stream)) return rc;
-        cur = nxt;
-    }
-    return CRB_OK;
-}
-}  // namespace
-
-// Beams that live in one wave and whose gain fits LDS: the whole closed-loop rollout as ONE launch of the general
-// stepper's feedback instantiation (crb_generic.h, FB) instead of eight launches per step.
-static bool fused_feedback_eligible(const crb_plan* p, const crb_input_desc* in) {
-    if (p->lognw != 0 || p->NT != 64 || p->mixed_topology || (in && in->f_held)) return false;
-    const char* env = std::getenv("CRB_FUSED_FEEDBACK");     // 0 = never, 1 = whenever the gain fits LDS, unset = choose
-    if (env && std::atoi(env) == 0) return false;
-    const size_t need = p->dtype == CRB_F64 ? fb_lds_bytes<double>(p->NT, p->G, p->n_free) : fb_lds_bytes<float>(p->NT, p->G, p->n_free);
-    if (need > size_t(144) * 1024) return false;
-    if (env) return true;
-    // a workgroup is ONE wave here: with a gain of more than ~50 KB few of them share a CU, and an ensemble that needs
-    // several rounds of workgroups is faster through the stage-split path (2048 x 27 elements: 125 against 67 us/step;
-    // 64 x 27: 31 against 48; up to 16 elements the fused form wins at every size: 21 against 40 - 48 us/step)
-    const size_t per_cu = (size_t(160) * 1024) / need;
-    const size_t groups = size_t((p->B + p->G - 1) / p->G);
-    return need <= size_t(52) * 1024 || groups <= per_cu * 256;
-}
-namespace {
-template <typename T, int LV>
-int launch_fused_feedback_lv(const crb_plan* p, const KParams<T>& k, hipStream_t st) {
-    const dim3 grid((p->B + p->G - 1) / p->G), block(p->NT);
-    const size_t smem = fb_lds_bytes<T>(p->NT, p->G, p->n_free);
-    if (int rc = allow_lds(crb_beam_kernel<T, MODE_STEP, LV, 64, 1, false, true>, smem)) return rc;
-    hipLaunchKernelGGL((crb_beam_kernel<T, MODE_STEP, LV, 64, 1, false, true>), grid, block, smem, st, k);
-    HIP_TRY(hipGetLastError());
-    return CRB_OK;
-}
-template <typename T>
-int fused_feedback_impl(const crb_plan* p, void* x, double t0, double dt, int n_steps, const void* gain, const void* ref,
-                        const crb_input_desc* in, hipStream_t st) {
-#ifdef CRB_FAST_BUILD
-    return fail(CRB_EUNSUPPORTED, "CRB_FAST_BUILD: generic kernels not built");
-#else
-    if (int rc = ensure_red_map(p)) return rc;
-    KParams<T> k = base_params<T>(p);
-    k.x = static_cast<T*>(x);
-    k.t0 = t0; k.dt = dt; k.n_steps = n_steps;
-    arm_status(p, k, n_steps);
-    k.rec_slot = -1; k.rec_every = 1;
-    if (in && in->kind == CRB_INPUT_IMPULSE) {
-        k.amp = static_cast<const T*>(in->amp);
-        k.imp_slot = in->node - p->off; k.imp_dof = in->dof; k.duration = in->duration;
-        k.imp_node_b = in->node_b;
-    }
-    k.red_map = p->d_red_map;
-    k.n_red = p->n_free;
-    k.fb_gain = static_cast<const T*>(gain);
-    k.fb_ref = static_cast<const T*>(ref);
-    // several beams per wave with 3 .. 5 reduction levels, gravity absent or canonical: the packed LEAN stepper with the feedback
-    // inside its stages (its right-hand side costs half of the general kernel's)
-    const bool grav = (p->flags & CRB_FORCE_GRAVITY) != 0;
-    if (p->G > 1 && lean_eligible(p, nullptr) && p->levels >= 3 && p->levels <= 5 &&
-        fb_lean_lds_bytes<T>(p->G, p->n_free) <= size_t(144) * 1024 && std::getenv("CRB_DISABLE_LEAN_FEEDBACK") == nullptr) {
-        HIP_TRY(crb::launch_lean_feedback(k, p->B, p->levels, grav, st));
-        return CRB_OK;
-    }
-    switch (p->levels) {   // (a beam inside one wave: at most 6 levels)
-        case 0: return launch_fused_feedback_lv<T, 0>(p, k, st);
-        case 1: return launch_fused_feedback_lv<T, 1>(p, k, st);
-        case 2: return launch_fused_feedback_lv<T, 2>(p, k, st);
-        case 3: return launch_fused_feedback_lv<T, 3>(p, k, st);
-        case 4: return launch_fused_feedback_lv<T, 4>(p, k, st);
-        case 5: return launch_fused_feedback_lv<T, 5>(p, k, st);
-        case 6: return launch_fused_feedback_lv<T, 6>(p, k, st);
-        default: return fail(CRB_EUNSUPPORTED, "crb_step_rk4_feedback: unsupported number of cyclic-reduction levels");
-    }
-#endif
-}
-}  // namespace
-
 extern "C" int crb_step_rk4_feedback(const crb_plan* p, void* x, double t0, double dt, int n_steps, const void* gain,
                                      const void* ref, const crb_input_desc* in, void* work, double* t_end, void* stream) {
     if (int rc = need_device(p, "crb_step_rk4_feedback")) return rc;
     if (!x || !gain || !work) return fail(CRB_EINVAL, "crb_step_rk4_feedback: null pointer");
     if (n_steps < 0 || !(dt > 0)) return fail(CRB_EINVAL, "crb_step_rk4_feedback: n_steps >= 0 and dt > 0 required");
     p->loop_used = false;
-    if (loop_eligible(p, in)) {
-        if (in && in->kind == CRB_INPUT_IMPULSE &&
-            (in->node < 0 || in->node >= p->n_node || in->dof < 0 || in->dof > 2 || !in->amp || !p->any_free[3 * in->node + in->dof]))
-            return fail(CRB_EINVAL, "crb_step_rk4_feedback: bad impulse description");
-        if (in && in->kind != CRB_INPUT_IMPULSE && in->kind != CRB_INPUT_NONE)
-            return fail(CRB_EINVAL, "crb_step_rk4_feedback: unknown input kind");
-        if (t_end) {
-            double t = t0;
-            for (int i = 0; i < n_steps; ++i) t = t + dt;
-            *t_end = t;
-        }
+    Forcing f;
+    if (int rc = decode_input(p, in, "crb_step_rk4_feedback", &f)) return rc;
+    if (t_end) *t_end = clock_after(t0, dt, n_steps);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (loop_ok(p, f.held)) {
         if (n_steps == 0) return CRB_OK;
-        if (int rc = ensure_red_map(p)) return rc;
-        hipStream_t st = static_cast<hipStream_t>(stream);
-        const int nb = loop_nb(p), n_rb = (p->B + 63) / 64;
-        const crb::LoopWork lay = crb::loop_work_layout(nb, n_rb < crb::LOOP_MAX_GROUPS ? n_rb : crb::LOOP_MAX_GROUPS);
-        char* w = static_cast<char*>(work);
-        crb::LoopParams<double> P;
-        std::memset(&P, 0, sizeof(P));
-        P.k = base_params<double>(p);
-        P.k.x = static_cast<double*>(x);
-        P.k.t0 = t0; P.k.dt = dt; P.k.n_steps = n_steps;
-        arm_status(p, P.k, n_steps);
-        if (in && in->kind == CRB_INPUT_IMPULSE) {
-            P.k.amp = static_cast<const double*>(in->amp);
-            P.k.imp_slot = in->node - p->off; P.k.imp_dof = in->dof; P.k.duration = in->duration;
-            P.k.imp_node_b = in->node_b;
-        }
-        P.ref = static_cast<const double*>(ref);
-        P.red_map = p->d_red_map;
-        P.n_red = p->n_free;
-        P.sync = reinterpret_cast<unsigned*>(w);
-        P.kfrag = reinterpret_cast<const double*>(w + lay.kfrag);
-        P.ebuf = reinterpret_cast<double*>(w + lay.ebuf);
-        P.ubuf = reinterpret_cast<double*>(w + lay.ubuf);
-        P.ownbuf = reinterpret_cast<double*>(w + lay.ownbuf);
-        P.n_rb = n_rb;
-        const char* fenv = std::getenv("CRB_LOOP_FENCES");
-        P.fences = fenv ? std::atoi(fenv) : 0;
-        const char* tenv = std::getenv("CRB_LOOP_TIMEOUT_MS");
-        P.timeout = (unsigned long long)(tenv ? std::atol(tenv) : 2000) * 100000ull;   // 100 MHz ticks
-        // every polled word starts at zero, in every call
-        HIP_TRY(hipMemsetAsync(w, 0, size_t(crb::LOOP_SYNC_WORDS) * sizeof(unsigned), st));
-        const bool grav = (p->flags & CRB_FORCE_GRAVITY) != 0;
-        const hipError_t e = p->lognw == 1 ? crb::launch_loop_long(P, static_cast<const double*>(gain), p->levels, grav, p->elem_mode, st)
-                                           : crb::launch_loop_short(P, static_cast<const double*>(gain), p->levels, grav, p->elem_mode, st);
-        if (e != hipSuccess) return fail(CRB_EHIP, std::string("crb_step_rk4_feedback (persistent stepper): ") + hipGetErrorString(e));
-        p->loop_used = true;
-        return CRB_OK;
+        return loop_feedback(p, x, t0, dt, n_steps, gain, ref, f, work, st);
     }
-    if (fused_feedback_eligible(p, in)) {
-        if (in && in->kind == CRB_INPUT_IMPULSE &&
-            (in->node < 0 || in->node >= p->n_node || in->dof < 0 || in->dof > 2 || !in->amp || !p->any_free[3 * in->node + in->dof]))
-            return fail(CRB_EINVAL, "crb_step_rk4_feedback: bad impulse description");
-        if (in && in->kind != CRB_INPUT_IMPULSE && in->kind != CRB_INPUT_NONE)
-            return fail(CRB_EINVAL, "crb_step_rk4_feedback: unknown input kind");
-        if (t_end) {
-            double t = t0;
-            for (int i = 0; i < n_steps; ++i) t = t + dt;
-            *t_end = t;
-        }
+    if (fused_feedback_ok(p, f.held)) {
         if (n_steps == 0) return CRB_OK;
-        hipStream_t st = static_cast<hipStream_t>(stream);
-        return p->dtype == CRB_F64 ? fused_feedback_impl<double>(p, x, t0, dt, n_steps, gain, ref, in, st)
-                                   : fused_feedback_impl<float>(p, x, t0, dt, n_steps, gain, ref, in, st);
+        return p->dtype == CRB_F64 ? fused_feedback_impl<double>(p, x, t0, dt, n_steps, gain, ref, f, st)
+                                   : fused_feedback_impl<float>(p, x, t0, dt, n_steps, gain, ref, f, st);
     }
-    const size_t state = size_t(p->B) * 2 * p->n_node * 4 * (p->dtype == CRB_F64 ? sizeof(double) : sizeof(float));
-    char* w = static_cast<char*>(work);
-    void* acc = w;
-    void* bufs[2] = {w + state, w + 2 * state};
-    void* u = w + 3 * state;
-    double* t_dev = reinterpret_cast<double*>(w + 3 * state + state / 2);
-    hipStream_t user = static_cast<hipStream_t>(stream);
-    double t = t0;
-    // CRB_USE_GRAPH=1: one step (8 launches + clock) is captured into a hipGraph and replayed; the stage kernels
-    // then read the stage time from a device clock that the graph's last node advances, so that no launch
-    // argument changes from step to step.  Opt-in: on ROCm 7.2 the replay measured SLOWER than the plain
-    // launches (70 vs 65 us per step for 1..256 beams of 64 elements, 218 vs 205 us at 2048 x 128) -- the
-    // small-ensemble loop is bound by the ~7 us of dependent-kernel latency per launch, which a graph of
-    // kernel nodes does not remove.
-    const char* genv = std::getenv("CRB_USE_GRAPH");
-    const bool use_graph = n_steps >= 8 && genv && std::atoi(genv) != 0;
-    if (!use_graph) {
-        // entries of u outside the free DOFs are never written by the GEMM and must read as zero
-        HIP_TRY(hipMemsetAsync(u, 0, state / 2, user));
-        for (int s = 0; s < n_steps; ++s) {
-            if (int rc = feedback_step_launches(p, x, acc, bufs, u, gain, ref, in, t, nullptr, dt, stream)) return rc;
-            t = t + dt;
-        }
-        if (t_end) *t_end = t;
-        return CRB_OK;
-    }
-    if (!p->aux_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&p->aux_stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&p->aux_in, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&p->aux_out, hipEventDisableTiming));
-    }
-    hipStream_t aux = p->aux_stream;
-    HIP_TRY(hipEventRecord(p->aux_in, user));                 // everything the caller queued so far ...
-    HIP_TRY(hipStreamWaitEvent(aux, p->aux_in, 0));           // ... happens before the replayed steps
-    HIP_TRY(hipMemsetAsync(u, 0, state / 2, aux));
-    hipLaunchKernelGGL(crb_clock_kernel<0>, dim3(1), dim3(64), 0, aux, t_dev, dt, t0, 1);
-    HIP_TRY(hipGetLastError());
-    // the captured step depends on every pointer and scalar below: rebuild when one of them changes
-    std::vector<uint64_t> key = {uint64_t(reinterpret_cast<uintptr_t>(x)), uint64_t(reinterpret_cast<uintptr_t>(gain)),
-                                 uint64_t(reinterpret_cast<uintptr_t>(ref)), uint64_t(reinterpret_cast<uintptr_t>(work))};
-    uint64_t dtb;
-    std::memcpy(&dtb, &dt, sizeof(dtb));
-    key.push_back(dtb);
-    if (in) {
-        uint64_t dur;
-        std::memcpy(&dur, &in->duration, sizeof(dur));
-        key.insert(key.end(), {uint64_t(in->kind), uint64_t(in->node), uint64_t(in->dof), dur,
-                               uint64_t(reinterpret_cast<uintptr_t>(in->amp)), uint64_t(reinterpret_cast<uintptr_t>(in->f_held)),
-                               uint64_t(reinterpret_cast<uintptr_t>(in->node_b))});
-    }
-    const char* tile = std::getenv("CRB_FEEDBACK_TILE");
-    key.push_back(tile ? uint64_t(std::atoi(tile)) : 0);
-    if (!p->step_exec || key != p->step_key) {
-        if (p->step_exec) {
-            HIP_TRY(hipStreamSynchronize(aux));                // the old graph may still be running
-            HIP_TRY(hipGraphExecDestroy(p->step_exec));
-            p->step_exec = nullptr;
-        }
-        hipGraph_t graph = nullptr;
-        HIP_TRY(hipStreamBeginCapture(aux, hipStreamCaptureModeThreadLocal));
-        int rc = feedback_step_launches(p, x, acc, bufs, u, gain, ref, in, 0.0, t_dev, dt, aux);
-        if (rc == CRB_OK) {
-            hipLaunchKernelGGL(crb_clock_kernel<0>, dim3(1), dim3(64), 0, aux, t_dev, dt, 0.0, 0);
-            if (hipGetLastError() != hipSuccess) rc = fail(CRB_EHIP, "crb_step_rk4_feedback: clock kernel launch failed");
-        }
-        const hipError_t ec = hipStreamEndCapture(aux, &graph);   // (always: leaves the stream usable)
-        if (rc != CRB_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        HIP_TRY(ec);
-        const hipError_t ei = hipGraphInstantiate(&p->step_exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        HIP_TRY(ei);
-        p->step_key = key;
-    }
-    for (int s = 0; s < n_steps; ++s) {
-        HIP_TRY(hipGraphLaunch(p->step_exec, aux));
-        t = t + dt;
-    }
-    HIP_TRY(hipEventRecord(p->aux_out, aux));
-    HIP_TRY(hipStreamWaitEvent(user, p->aux_out, 0));         // the caller's stream continues after the rollout
-    if (t_end) *t_end = t;
-    return CRB_OK;
+    return feedback_rollout(p, x, t0, dt, n_steps, f, work,
+                            [&](const void* xs, void* u) { return crb_feedback_force(p, xs, gain, ref, u, stream); }, stream);
 }
 
 namespace {
@@ -2031,25 +1902,20 @@ int launch_rk45(const crb_plan* p, const KParams<T>& k, const Rk45Params& q, hip
 #ifdef CRB_FAST_BUILD
     return fail(CRB_EUNSUPPORTED, "CRB_FAST_BUILD: rk45 not built");
 #else
-    // plans without gravity, one beam per workgroup of <= 4 waves: the lean RHS (crb_lean.hip)
-    const int lv_long = p->dtype == CRB_F64 ? 5 : 4;
-    const bool levels_ok = p->lognw == 0 ? (p->levels >= 3 && p->levels <= 6) : (p->levels == lv_long || p->levels == lv_long + 1);
-    if (!(p->flags & CRB_FORCE_GRAVITY) && p->NT == (64 << p->lognw) && p->lognw <= 2 && levels_ok &&
-        std::getenv("CRB_DISABLE_LEAN") == nullptr) {
+    if (lean_rk45_ok(p)) {   // the lean RHS (crb_lean.hip)
         HIP_TRY(crb::launch_rk45_lean(k, q, p->B, p->levels, p->lognw, p->elem_mode, st));
         return CRB_OK;
     }
-    switch (p->levels) {
-        case 0: return launch_rk45_lv<T, 0>(p, k, q, st);
-        case 1: return launch_rk45_lv<T, 1>(p, k, q, st);
-        case 2: return launch_rk45_lv<T, 2>(p, k, q, st);
-        case 3: return launch_rk45_lv<T, 3>(p, k, q, st);
-        case 4: return launch_rk45_lv<T, 4>(p, k, q, st);
-        case 5: return launch_rk45_lv<T, 5>(p, k, q, st);
-        case 6: return launch_rk45_lv<T, 6>(p, k, q, st);
-        default: return fail(CRB_EUNSUPPORTED, "crb_solve_rk45: unsupported number of cyclic-reduction levels");
-    }
+    return with_levels<6>(p->levels, "crb_solve_rk45: unsupported number of cyclic-reduction levels",
+                          [&](auto lv) { return launch_rk45_lv<T, decltype(lv)::value>(p, k, q, st); });
 #endif
+}
+template <typename T>
+int rk45_impl(const crb_plan* p, void* x, const Forcing& f, const Rk45Params& q, hipStream_t st) {
+    KParams<T> k = base_params<T>(p);
+    k.x = static_cast<T*>(x);
+    set_io(k, f);
+    return launch_rk45<T>(p, k, q, st);
 }
 }  // namespace
 
@@ -2062,55 +1928,25 @@ extern "C" int crb_solve_rk45_eval(const crb_plan* p, void* x, double t0, double
                                    const crb_input_desc* in, void* h, void* stats, int max_steps,
                                    const crb_record_desc* rec, double eval_t0, double eval_dt, int n_eval, void* stream) {
     if (int rc = need_device(p, "crb_solve_rk45")) return rc;
-    const bool eval_all = rec && rec->node == CRB_RECORD_ALL;
-    if (rec && n_eval > 0) {
-        if ((!eval_all && (rec->plane < 0 || rec->plane > 1 || rec->node < 0 || rec->node >= p->n_node || rec->dof < 0 ||
-                           rec->dof > 2)) ||
-            !rec->out || !(eval_dt > 0) || eval_t0 < t0)
-            return fail(CRB_EINVAL, "crb_solve_rk45_eval: bad t_eval description");
-    }
+    Recording r;   // (a record with no grid points records nothing and is not checked)
+    if (int rc = decode_record(p, n_eval > 0 ? rec : nullptr, n_eval, false, "crb_solve_rk45", &r)) return rc;
+    if (rec && n_eval > 0 && (!(eval_dt > 0) || eval_t0 < t0)) return fail(CRB_EINVAL, "crb_solve_rk45: bad t_eval description");
     if (!x) return fail(CRB_EINVAL, "crb_solve_rk45: null state");
     if (!(t_end > t0)) return fail(CRB_EINVAL, "crb_solve_rk45: t_end must be greater than t0");
     if (!(rtol > 0) || !(atol >= 0)) return fail(CRB_EINVAL, "crb_solve_rk45: tolerances must be positive");
     // (beams of fewer than 64 slots run one per wave here, not packed: every beam has its own step sequence)
     if (rk45_lds_bytes<double>(p->NT) > 160 * 1024)
         return fail(CRB_EUNSUPPORTED, "crb_solve_rk45: beam too long for the LDS-resident stage storage");
-    int imp_slot = -1, imp_dof = 0;
-    double duration = 0.0;
-    const void* amp = nullptr;
-    const void* held = nullptr;
-    if (in) {
-        held = in->f_held;
-        if (in->kind == CRB_INPUT_IMPULSE) {
-            if (in->node < 0 || in->node >= p->n_node || in->dof < 0 || in->dof > 2 || !in->amp ||
-                !p->any_free[3 * in->node + in->dof])
-                return fail(CRB_EINVAL, "crb_solve_rk45: bad impulse description");
-            imp_slot = in->node - p->off; imp_dof = in->dof; duration = in->duration; amp = in->amp;
-        }
-    }
+    Forcing f;
+    if (int rc = decode_input(p, in, "crb_solve_rk45", &f)) return rc;
     Rk45Params q;
     q.t0 = t0; q.t_end = t_end; q.rtol = rtol; q.atol = atol;
     q.h_io = static_cast<double*>(h); q.stats = static_cast<int32_t*>(stats);
     q.n_state = 2 * p->n_free; q.n_state_b = p->d_n_state; q.max_steps = max_steps > 0 ? max_steps : 100000000;
-    q.eval_out = nullptr; q.eval_t0 = eval_t0; q.eval_dt = eval_dt; q.n_eval = 0; q.eval_slot = -1; q.eval_comp = 0;
-    if (rec && n_eval > 0 && eval_all) {
-        q.eval_out = rec->out; q.n_eval = n_eval; q.eval_slot = REC_ALL_SLOTS;
-    } else if (rec && n_eval > 0 && rec->node - p->off >= 0) {
-        q.eval_out = rec->out; q.n_eval = n_eval; q.eval_slot = rec->node - p->off; q.eval_comp = rec->plane * 3 + rec->dof;
-    }
+    q.eval_t0 = eval_t0; q.eval_dt = eval_dt;
+    q.eval_out = r.out; q.n_eval = r.out ? r.count : 0; q.eval_slot = r.slot; q.eval_comp = r.comp;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (p->dtype == CRB_F64) {
-        KParams<double> k = base_params<double>(p);
-        k.x = static_cast<double*>(x); k.u_held = static_cast<const double*>(held); k.amp = static_cast<const double*>(amp);
-        k.imp_slot = imp_slot; k.imp_dof = imp_dof; k.duration = duration;
-        k.imp_node_b = (in && in->kind == CRB_INPUT_IMPULSE) ? in->node_b : nullptr;
-        return launch_rk45<double>(p, k, q, st);
-    }
-    KParams<float> k = base_params<float>(p);
-    k.x = static_cast<float*>(x); k.u_held = static_cast<const float*>(held); k.amp = static_cast<const float*>(amp);
-    k.imp_slot = imp_slot; k.imp_dof = imp_dof; k.duration = duration;
-    k.imp_node_b = (in && in->kind == CRB_INPUT_IMPULSE) ? in->node_b : nullptr;
-    return launch_rk45<float>(p, k, q, st);
+    return p->dtype == CRB_F64 ? rk45_impl<double>(p, x, f, q, st) : rk45_impl<float>(p, x, f, q, st);
 }
 
 namespace {
@@ -2165,8 +2001,7 @@ int feedback_force_impl(const crb_plan* p, const void* xs, const void* gain, con
     f.x_stride = size_t(2) * p->n_node * 4;
     f.u_stride = size_t(p->n_node) * 4;
     f.beam_idx = nullptr; f.ref_ld = 2 * p->n_free; f.ref_half = p->n_free;
-    const char* force = std::getenv("CRB_FEEDBACK_TILE");
-    if (int rc = launch_feedback<T>(force ? std::atoi(force) : 0, f, static_cast<hipStream_t>(stream))) return rc;
+    if (int rc = launch_feedback<T>(int(env_int("CRB_FEEDBACK_TILE", 0)), f, static_cast<hipStream_t>(stream))) return rc;
     HIP_TRY(hipGetLastError());
     return CRB_OK;
 }
@@ -2252,8 +2087,7 @@ int feedback_force_grouped_impl(const crb_plan* p, const void* xs, int n_groups,
         f.x_stride = size_t(2) * p->n_node * 4;
         f.u_stride = size_t(p->n_node) * 4;
         f.beam_idx = G.beam_idx; f.ref_ld = 2 * p->n_free; f.ref_half = p->n_free;
-        const char* force = std::getenv("CRB_FEEDBACK_TILE");
-        if (int rc = launch_feedback<T>(force ? std::atoi(force) : 0, f, static_cast<hipStream_t>(stream))) return rc;
+        if (int rc = launch_feedback<T>(int(env_int("CRB_FEEDBACK_TILE", 0)), f, static_cast<hipStream_t>(stream))) return rc;
         HIP_TRY(hipGetLastError());
     }
     return CRB_OK;
@@ -2269,9 +2103,6 @@ extern "C" int crb_feedback_force_grouped(const crb_plan* p, const void* xs, int
                                : feedback_force_grouped_impl<float>(p, xs, n_groups, gains, ref, u, stream);
 }
 
-static int rk4_stage_impl(const crb_plan* p, void* x, const void* xs, void* acc, void* xs_next, const void* u_stage, int stage,
-                         double t_stage, const double* t_dev, double dt, const crb_input_desc* in, void* stream);
-
 extern "C" int crb_step_rk4_feedback_grouped(const crb_plan* p, void* x, double t0, double dt, int n_steps, int n_groups,
                                              const int32_t* beam_group, const void* const* gains, const void* ref,
                                              const crb_input_desc* in, void* work, double* t_end, void* stream) {
@@ -2280,73 +2111,24 @@ extern "C" int crb_step_rk4_feedback_grouped(const crb_plan* p, void* x, double 
     if (n_steps < 0 || !(dt > 0)) return fail(CRB_EINVAL, "crb_step_rk4_feedback_grouped: n_steps >= 0 and dt > 0 required");
     if (int rc = ensure_gain_groups(p, n_groups, beam_group)) return rc;
     p->loop_used = false;
-    const size_t state = size_t(p->B) * 2 * p->n_node * 4 * (p->dtype == CRB_F64 ? sizeof(double) : sizeof(float));
-    char* w = static_cast<char*>(work);
-    void* acc = w;
-    void* bufs[2] = {w + state, w + 2 * state};
-    void* u = w + 3 * state;
-    // entries of u that no group writes (constrained DOFs, beams without a gain) must read as zero
-    HIP_TRY(hipMemsetAsync(u, 0, state / 2, static_cast<hipStream_t>(stream)));
-    double t = t0;
-    for (int s = 0; s < n_steps; ++s) {
-        const double th = t + 0.5 * dt, t1 = t + dt;   // same clock convention as crb_step_rk4
-        const double ts[4] = {t, th, th, t1};
-        const void* cur = x;
-        for (int stage = 0; stage < 4; ++stage) {
-            if (int rc = crb_feedback_force_grouped(p, cur, n_groups, beam_group, gains, ref, u, stream)) return rc;
-            void* nxt = bufs[stage & 1];
-            if (int rc = rk4_stage_impl(p, x, cur, acc, nxt, u, stage, ts[stage], nullptr, dt, in, stream)) return rc;
-            cur = nxt;
-        }
-        t = t + dt;
-    }
-    if (t_end) *t_end = t;
-    return CRB_OK;
+    Forcing f;
+    if (int rc = decode_input(p, in, "crb_step_rk4_feedback_grouped", &f)) return rc;
+    if (t_end) *t_end = clock_after(t0, dt, n_steps);
+    return feedback_rollout(p, x, t0, dt, n_steps, f, work, [&](const void* xs, void* u) {
+        return crb_feedback_force_grouped(p, xs, n_groups, beam_group, gains, ref, u, stream);
+    }, stream);
 }
 
 extern "C" int crb_rk4_stage(const crb_plan* p, void* x, const void* xs, void* acc, void* xs_next, const void* u_stage,
                              int stage, double t_stage, double dt, const crb_input_desc* in, void* stream) {
-    return rk4_stage_impl(p, x, xs, acc, xs_next, u_stage, stage, t_stage, nullptr, dt, in, stream);
-}
-static int rk4_stage_impl(const crb_plan* p, void* x, const void* xs, void* acc, void* xs_next, const void* u_stage, int stage,
-                         double t_stage, const double* t_dev, double dt, const crb_input_desc* in, void* stream) {
     if (int rc = need_device(p, "crb_rk4_stage")) return rc;
     if (!x || !xs || !acc) return fail(CRB_EINVAL, "crb_rk4_stage: null pointer");
     if (stage < 0 || stage > 3) return fail(CRB_EINVAL, "crb_rk4_stage: stage must be 0..3");
     if (stage < 3 && (!xs_next || xs_next == xs)) return fail(CRB_EINVAL, "crb_rk4_stage: xs_next must be a distinct buffer");
     if (!(dt > 0)) return fail(CRB_EINVAL, "crb_rk4_stage: dt must be positive");
-    int imp_slot = -1, imp_dof = 0;
-    double duration = 0.0;
-    const void* amp = nullptr;
-    if (in && in->kind == CRB_INPUT_IMPULSE) {
-        if (in->node < 0 || in->node >= p->n_node || in->dof < 0 || in->dof > 2 || !in->amp ||
-            !p->any_free[3 * in->node + in->dof])
-            return fail(CRB_EINVAL, "crb_rk4_stage: bad impulse description");
-        imp_slot = in->node - p->off; imp_dof = in->dof; duration = in->duration; amp = in->amp;
-    }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (p->dtype == CRB_F64) {
-        KParams<double> k = base_params<double>(p);
-        k.x = static_cast<double*>(x); k.xs = static_cast<const double*>(xs); k.acc = static_cast<double*>(acc);
-        k.out = static_cast<double*>(xs_next); k.u_held = static_cast<const double*>(u_stage);
-        k.amp = static_cast<const double*>(amp);
-        k.imp_slot = imp_slot; k.imp_dof = imp_dof; k.duration = duration;
-        k.imp_node_b = (in && in->kind == CRB_INPUT_IMPULSE) ? in->node_b : nullptr;
-        k.stage = stage; k.t0 = t_stage; k.dt = dt; k.t_dev = t_dev;
-    if (stage == 3) arm_status(p, k, 1);
-        if (stage_lean_eligible(p)) return launch_stage_lean<double>(p, k, st);
-        return launch_beam<double, MODE_STAGE>(p, k, st);
-    }
-    KParams<float> k = base_params<float>(p);
-    k.x = static_cast<float*>(x); k.xs = static_cast<const float*>(xs); k.acc = static_cast<float*>(acc);
-    k.out = static_cast<float*>(xs_next); k.u_held = static_cast<const float*>(u_stage);
-    k.amp = static_cast<const float*>(amp);
-    k.imp_slot = imp_slot; k.imp_dof = imp_dof; k.duration = duration;
-    k.imp_node_b = (in && in->kind == CRB_INPUT_IMPULSE) ? in->node_b : nullptr;
-    k.stage = stage; k.t0 = t_stage; k.dt = dt; k.t_dev = t_dev;
-    if (stage == 3) arm_status(p, k, 1);
-    if (stage_lean_eligible(p)) return launch_stage_lean<float>(p, k, st);
-    return launch_beam<float, MODE_STAGE>(p, k, st);
+    Forcing f;
+    if (int rc = decode_input(p, in, "crb_rk4_stage", &f)) return rc;
+    return rk4_stage(p, x, xs, acc, xs_next, u_stage, stage, t_stage, dt, f, stream);
 }
 
 extern "C" int crb_gather_dof(const crb_plan* p, const void* x, int plane, int node, int dof, void* out, void* stream) {

@@ -330,9 +330,7 @@ int crb_rk4_stage(const crb_plan* plan, void* x, const void* xs, void* acc, void
 /* The closed loop of examples/lqr_control.py:95-125 as ONE call: n_steps RK4 steps with u = K (r - x)
  * re-evaluated at every stage (crb_feedback_force, then crb_rk4_stage), all launches issued from here
  * (either dtype).  work: device scratch of crb_feedback_work_bytes(plan) bytes (three state-sized buffers and
- * one force-sized buffer and the device clock; contents need not be initialised).  Returns the accumulated clock
- * in *t_end.  CRB_USE_GRAPH=1 in the environment replays one captured step as a hipGraph on a stream of the
- * plan's own (ordered after / before the caller's stream by events).
+ * one force-sized buffer; contents need not be initialised).  Returns the accumulated clock in *t_end.
  * Beams that live in one wave (fewer than 64 thread-carried nodes: the reference's own LQR example has 6 elements)
  * and whose gain fits LDS take ONE launch for the whole rollout instead: the packed lean stepper (several beams per wave,
  * 3 .. 5 reduction levels, gravity absent or of the plain cantilever's form; the general stepper otherwise) with the gain

@@ -789,7 +789,8 @@ def test_new_entry_points_reject_bad_arguments():
 
 def test_native_feedback_rollout_entry_point_contract():
     """crb_step_rk4_feedback: argument checks, the accumulated clock it returns, and equality with the same
-    loop issued stage by stage through crb_feedback_force + crb_rk4_stage."""
+    loop issued stage by stage through crb_feedback_force + crb_rk4_stage -- also with an impulse that switches off
+    mid-run, across two consecutive calls."""
     import ctypes as C
 
     from continuum_robot import _native as nat
@@ -804,9 +805,9 @@ def test_native_feedback_rollout_entry_point_contract():
     x0 = rng.normal(0.0, 1e-4, (B, 2 * n))
     ens.set_state(x0)
     work = torch.empty((int(lib.crb_feedback_work_bytes(ens.plan.h)),), dtype=torch.uint8, device=ens.device)
-    # (three state-sized buffers, a force-sized one and the device clock for the stage-split loop; plans the persistent stepper
-    #  covers -- this one: 70 thread-carried nodes -- ask for its buffers when those are larger)
-    assert work.numel() >= 3 * ens.state.numel() * 8 + ens.state.numel() * 4 + 256
+    # (three state-sized buffers and a force-sized one for the stage-split loop; plans the persistent stepper covers -- this
+    #  one: 70 thread-carried nodes -- ask for its buffers when those are larger)
+    assert work.numel() >= 3 * ens.state.numel() * 8 + ens.state.numel() * 4
     t_end = C.c_double(-1.0)
     vp = lambda t: C.c_void_p(t.data_ptr())
     # bad arguments
@@ -820,37 +821,35 @@ def test_native_feedback_rollout_entry_point_contract():
     for _ in range(steps):
         t = t + dt
     assert t_end.value == t
-    ref = ensemble(cols, B, dict(enable_gravity=True))
-    ref.set_state(x0)
-    acc, bufs = torch.empty_like(ref.state), (torch.empty_like(ref.state), torch.empty_like(ref.state))
-    u = torch.zeros((B, ref.n_node, 4), dtype=torch.float64, device=ref.device)
-    t = 0.25
-    for _ in range(steps):
-        cur = ref.state
-        for s, ts in enumerate((t, t + 0.5 * dt, t + 0.5 * dt, t + dt)):
-            nat.check(lib.crb_feedback_force(ref.plan.h, vp(cur), vp(gain), None, vp(u), None))
-            nat.check(lib.crb_rk4_stage(ref.plan.h, vp(ref.state), vp(cur), vp(acc), vp(bufs[s & 1]), vp(u), s, ts, dt, None, None))
-            cur = bufs[s & 1]
-        t = t + dt
-    torch.cuda.synchronize()
-    assert torch.equal(ens.state, ref.state)
-    # opt-in hipGraph replay of one captured step (CRB_USE_GRAPH=1; a second rollout reuses the captured step):
-    # an impulse that switches off mid-run is timed by the device clock exactly as by the host loop
+
+    def by_stages(t, n_steps, desc):
+        ref = ensemble(cols, B, dict(enable_gravity=True))
+        ref.set_state(x0)
+        acc, bufs = torch.empty_like(ref.state), (torch.empty_like(ref.state), torch.empty_like(ref.state))
+        u = torch.zeros((B, ref.n_node, 4), dtype=torch.float64, device=ref.device)
+        for _ in range(n_steps):
+            cur = ref.state
+            for s, ts in enumerate((t, t + 0.5 * dt, t + 0.5 * dt, t + dt)):
+                nat.check(lib.crb_feedback_force(ref.plan.h, vp(cur), vp(gain), None, vp(u), None))
+                nat.check(lib.crb_rk4_stage(ref.plan.h, vp(ref.state), vp(cur), vp(acc), vp(bufs[s & 1]), vp(u), s, ts, dt,
+                                            desc, None))
+                cur = bufs[s & 1]
+            t = t + dt
+        torch.cuda.synchronize()
+        return ref.state
+
+    assert torch.equal(ens.state, by_stages(0.25, steps, None))
+    # an impulse that switches off mid-run (5.5 dt), over two consecutive rollouts
     amps = torch.tensor([0.1, 0.2, 0.3], dtype=torch.float64, device=ens.device)
-    finals = []
-    for graph in (True, False):
-        e = ensemble(cols, B, dict(enable_gravity=True))
-        e.set_state(x0)
-        if graph:
-            os.environ["CRB_USE_GRAPH"] = "1"
-        try:
-            e.step_feedback(10, dt, gain, impulse_amp=amps, impulse_duration=5.5 * dt)
-            e.step_feedback(10, dt, gain, impulse_amp=amps, impulse_duration=5.5 * dt)
-        finally:
-            os.environ.pop("CRB_USE_GRAPH", None)
-        assert abs(e.time - 20 * dt) < 1e-15
-        finals.append(e.unpack_state())
-    assert torch.equal(finals[0], finals[1])
+    e = ensemble(cols, B, dict(enable_gravity=True))
+    e.set_state(x0)
+    assert e.feedback_path() == "stage-split"
+    e.step_feedback(10, dt, gain, impulse_amp=amps, impulse_duration=5.5 * dt)
+    e.step_feedback(10, dt, gain, impulse_amp=amps, impulse_duration=5.5 * dt)
+    assert abs(e.time - 20 * dt) < 1e-15
+    desc, keep = e._input_desc(amps, 5.5 * dt)
+    torch.cuda.synchronize()
+    assert torch.equal(e.state, by_stages(0.0, 20, C.byref(desc)))
 
 
 @pytest.mark.parametrize("n_e,kind", [(64, "linear"), (100, "mixed"), (200, "nonlinear")])

@@ -490,12 +490,14 @@ class BeamEnsemble:
         rho_inf  (integer ``substeps`` of the stiff methods) < 1: the damped implicit scheme, see ``step_implicit``.
         controller  where the step-size control of ``substeps="auto"`` runs.  "device": inside the kernel, every beam with its
                  own step sequence, the whole span in ONE launch (``solve_controlled`` / crb_solve_controlled; the closed loop
-                 only for gains that fit the LDS, beams of up to ~30 elements);  "host": the same controller as a host loop
+                 with one gain for a uniform topology: held in LDS up to ~30 elements, streamed from global memory beyond);
+                 "host": the same controller as a host loop
                  over fixed-step launches, the worst beam deciding for the ensemble (``_solve_controlled``; any gain, through
                  ``step_feedback``);  "device-packed" (implicit scheme, beams of 2 .. 32 thread-carried nodes): G = 64 / slots
                  beams share a wave and ONE step sequence, the worst of them deciding -- thousands of short beams fill the
-                 chip with a fifth of the waves;  "auto": the device whenever it can, packed once one workgroup per beam
-                 would need more than two rounds of resident waves (2048).
+                 chip with a fifth of the waves;  "auto": the device whenever it can -- for the closed loop only while the
+                 gain fits the LDS, the host loop beyond --, packed once one workgroup per beam would need more than two rounds
+                 of resident waves (2048).
         Returns an object with ``t`` [n_t] and ``y`` [B, 2n, n_t] (``y[b]`` is the reference's ``sol.y`` of beam b,
         first column = the state at ``t_span[0]``), ``success``, ``method``; the resident state ends at the last
         ``t_eval`` point reached by whole intervals (RK45: at ``t_span[1]``)."""
@@ -608,12 +610,16 @@ class BeamEnsemble:
             controller = "device"
         ok = self.dtype == torch.float64 and int(self.plan.layout.threads) <= 256
         if ok and gain is not None:
-            n2p = (2 * self.n + 7) // 8 * 8
-            lds = 14 * int(self.plan.layout.threads) * 8 + (n2p + n2p * self.n + 32) * 8 + 512
-            ok = not isinstance(gain, (list, tuple)) and not self.mixed_topology and lds <= 160 * 1024
+            ok = not isinstance(gain, (list, tuple)) and not self.mixed_topology
+            if controller == "auto":
+                # (the kernel streams a gain that does not fit the LDS; "auto" keeps the host loop for those until the two are
+                #  compared across ensemble sizes -- profiles/exp_ctrl_large_gain.py)
+                n2p = (2 * self.n + 7) // 8 * 8
+                lds = 14 * int(self.plan.layout.threads) * 8 + (n2p + n2p * self.n + 32) * 8 + 512
+                ok = ok and lds <= 160 * 1024
         if controller == "device" and not ok:
             raise ValueError("controller=\"device\": fp64 plans with beams of up to 256 thread-carried nodes; the closed loop "
-                             "needs one gain that fits the LDS (beams of up to ~30 elements)")
+                             "needs one gain for a uniform topology")
         return ok
 
     def _packs_per_wave(self, controller, gain) -> bool:

@@ -5,7 +5,8 @@
 //
 //   scheme  FB = false: the implicit midpoint rule of crb_stiff.h (order 2), iteration matrix A = M + h^2/4 K0;
 //           FB = true:  classical RK4 with the state feedback u = K (r - x) inside every stage (order 4, the fused
-//                       small-beam form of crb_generic.h: gain in LDS).
+//                       small-beam form of crb_generic.h: gain in LDS; SG: gains too large for the LDS -- beams of more
+//                       than ~30 elements -- are read from a transposed copy in global memory, fb_feedback_streamed).
 //   control step doubling per PIECE (a t_eval interval, cut at the end of the impulse when that falls inside it -- the
 //           host lists the pieces): from the piece's start state m = 2^r steps give the coarse solution, 2m steps the
 //           fine one, (fine - coarse) / (2^order - 1) estimates the fine solution's error, measured like scipy measures
@@ -57,13 +58,73 @@ struct CtrlParams {
     T* y_out;                   // [n_rec][B][2][n_node][4] or nullptr
     T* series_out;              // [B][n_intervals] one DOF per t_eval point, or nullptr
     int series_slot, series_comp;   // its slot (node - off) and component (3 plane + dof)
+    const T* gain_t;            // SG: the gain transposed, [ctrl_sg_rows(2n)][n] in global memory (rows past 2n are 0)
 };
 
+// SG (closed loop, gain too large for the LDS): K e is formed from a transposed copy of the gain in global memory, read in
+// batches of CTRL_SG_BATCH rows (3 x 16 loads in flight per lane: one wave per SIMD, nothing else hides their latency);
+// the error vector e stays in LDS, zero-padded to a whole number of batches like the copy's rows.
+constexpr int CTRL_SG_BATCH = 16;
+__host__ __device__ constexpr int ctrl_sg_rows(int n2) { return (n2 + CTRL_SG_BATCH - 1) / CTRL_SG_BATCH * CTRL_SG_BATCH; }
+
+// stream_gain (fb only): the error vector alone in LDS, the gain read from global memory (SG)
 template <typename T>
-__host__ __device__ constexpr size_t ctrl_lds_bytes(int NT, bool fb, int n, int lean_lognw = -1) {
+__host__ __device__ constexpr size_t ctrl_lds_bytes(int NT, bool fb, int n, int lean_lognw = -1, bool stream_gain = false) {
     return (lean_lognw >= 0 ? implicit_lean_lds_bytes<T>(NT, lean_lognw)
-                            : lds_bytes<T>(NT) + (fb ? (size_t(fb_padded(2 * n)) + size_t(fb_padded(2 * n)) * n + FBM_UPAD) * sizeof(T) : 0)) +
+            : !fb           ? lds_bytes<T>(NT)
+            : stream_gain   ? lds_bytes<T>(NT) + (size_t(ctrl_sg_rows(2 * n)) + FBM_UPAD) * sizeof(T)
+                            : lds_bytes<T>(NT) + (size_t(fb_padded(2 * n)) + size_t(fb_padded(2 * n)) * n + FBM_UPAD) * sizeof(T)) +
            64 * sizeof(double);
+}
+
+// Kt[k][i] = K[i][k] for the gain K [n][n2], rows n2 .. rows-1 of Kt zero: 32 x 32 tiles through LDS (both sides coalesced);
+// grid (ceil(rows / 32), ceil(n / 32)), 256 threads
+template <typename T>
+__global__ void __launch_bounds__(256) crb_gain_transpose_kernel(const T* __restrict__ K, T* __restrict__ Kt, int n, int n2, int rows) {
+    __shared__ T tile[32][33];
+    const int k0 = int(blockIdx.x) * 32, i0 = int(blockIdx.y) * 32, tx = int(threadIdx.x) & 31, ty = int(threadIdx.x) >> 5;
+    for (int yy = ty; yy < 32; yy += 8) {
+        const int i = i0 + yy, k = k0 + tx;
+        tile[yy][tx] = (i < n && k < n2) ? K[size_t(i) * n2 + k] : T(0);
+    }
+    __syncthreads();
+    for (int yy = ty; yy < 32; yy += 8) {
+        const int k = k0 + yy, i = i0 + tx;
+        if (k < rows && i < n) Kt[size_t(k) * n + i] = tile[tx][yy];
+    }
+}
+
+// The three entries of K e that belong to one node (rows i0 / i1 / i2 of the gain) with the gain in global memory, transposed
+// (gt: [n2s][n], n2s a multiple of CTRL_SG_BATCH): neighbouring lanes read neighbouring addresses of every row, e[k] is an LDS
+// broadcast.  Same order of multiply-adds as fb_product_lds.  Whole workgroup (barrier first:
+// the caller has just written e).
+template <typename T>
+__device__ __forceinline__ void fb_feedback_streamed(const T* e, const T* __restrict__ gt, int n, int n2s, bool valid, const int (&red)[3],
+                                                     T (&u)[3]) {
+    __syncthreads();
+    u[0] = u[1] = u[2] = T(0);
+    if (!valid) return;
+    // (row addresses are wave-uniform, the lane's offsets 32-bit: one scalar base per row and three shared lane offsets,
+    //  instead of a 64-bit address per load and lane)
+    const unsigned i0 = red[0] >= 0 ? unsigned(red[0]) : 0u, i1 = red[1] >= 0 ? unsigned(red[1]) : 0u, i2 = red[2] >= 0 ? unsigned(red[2]) : 0u;
+    T u0 = T(0), u1 = T(0), u2 = T(0);
+#pragma unroll 1
+    for (int k = 0; k < n2s; k += CTRL_SG_BATCH) {
+        T ek[CTRL_SG_BATCH], r0[CTRL_SG_BATCH], r1[CTRL_SG_BATCH], r2[CTRL_SG_BATCH];
+        const T* const rows = gt + size_t(__builtin_amdgcn_readfirstlane(k)) * unsigned(n);
+#pragma unroll
+        for (int qq = 0; qq < CTRL_SG_BATCH; ++qq) {
+            const T* row = rows + size_t(qq) * unsigned(n);
+            r0[qq] = row[i0]; r1[qq] = row[i1]; r2[qq] = row[i2];
+        }
+#pragma unroll
+        for (int qq = 0; qq < CTRL_SG_BATCH; ++qq) ek[qq] = e[k + qq];
+#pragma unroll
+        for (int qq = 0; qq < CTRL_SG_BATCH; ++qq) { u0 += r0[qq] * ek[qq]; u1 += r1[qq] * ek[qq]; u2 += r2[qq] * ek[qq]; }
+    }
+    u[0] = red[0] >= 0 ? u0 : T(0);
+    u[1] = red[1] >= 0 ? u1 : T(0);
+    u[2] = red[2] >= 0 ? u2 : T(0);
 }
 
 // The explicit right-hand side a = Minv (u - k(q) + drag + gravity) of ONE beam that lives in one wave, in the lean form (the
@@ -102,10 +163,12 @@ __device__ __forceinline__ void lean_wave_rhs(const ElemCoef<T>& ec, bool correc
 // PACK (lean form, one wave): beams of fewer than 33 slots, G = 64 / S of them per wave (lane = g S + j) as in the packed
 // fixed-step kernels; the beams of a wave share ONE step sequence -- the worst of them decides -- so an ensemble of thousands
 // of short beams fills the chip with a fifth of the waves (control per group of G neighbours instead of per beam).
-template <typename T, int LV, bool FB, int LNW = -1, bool GRAV = false, bool PACK = false>
+// SG (FB only): the gain streamed from q.gain_t instead of held in LDS.
+template <typename T, int LV, bool FB, int LNW = -1, bool GRAV = false, bool PACK = false, bool SG = false>
 __global__ void __launch_bounds__(LNW >= 0 ? (64 << LNW) : 256, 1)
 crb_controlled_kernel(const KParams<T> p, const CtrlParams<T> q) {
     static_assert(sizeof(T) == 8, "the controlled steppers are fp64");
+    static_assert(!SG || FB, "only the closed loop has a gain to stream");
     static_assert(!(FB && LNW > 0) && !(FB && PACK), "the closed loop runs one beam per wave: the lean RHS of one wave, or the general one");
     static_assert(LNW < 0 || LV >= 1, "the lean form needs at least one reduction level");
     static_assert(!PACK || LNW == 0, "packed beams live inside one wave");
@@ -209,11 +272,12 @@ crb_controlled_kernel(const KParams<T> p, const CtrlParams<T> q) {
     }
 
     // FB: reduced indices and reference of this node, the gain into LDS (crb_beam_kernel's layout with one beam per group)
-    const int fb_n = p.n_red, fb_n2 = 2 * p.n_red, fb_n2p = fb_padded(fb_n2);
+    // SG: e padded to whole batches of the streamed product, no gain in LDS
+    const int fb_n = p.n_red, fb_n2 = 2 * p.n_red, fb_n2p = SG ? ctrl_sg_rows(fb_n2) : fb_padded(fb_n2);
     T* const fbx = lds.r1 + 3 * NT;            // [2n padded]     r - x of the stage
-    T* const fbK = fbx + fb_n2p;               // [2n padded][n]  gain, transposed
-    T* const fbu = fbK + size_t(fb_n2p) * fb_n;   // [FBM_UPAD]      K e of the stage (matrix-core form, crb_generic.h)
-    const bool fb_mfma = FB && fb_on_matrix_cores(1, fb_n);
+    T* const fbK = fbx + fb_n2p;               // [2n padded][n]  gain, transposed (not SG)
+    T* const fbu = fbK + (SG ? size_t(0) : size_t(fb_n2p) * fb_n);   // [FBM_UPAD]      K e of the stage (matrix-core form, crb_generic.h)
+    const bool fb_mfma = FB && !SG && fb_on_matrix_cores(1, fb_n);
     T fb_af[FBM_MT][FBM_KS];
     double* const red = (SLIM && !FB) ? reinterpret_cast<double*>(smem0 + size_t(NTL + 1) * size_t(12 + 3 * (LOGNW > 1 ? LOGNW - 1 : 0)))
                              : reinterpret_cast<double*>(FB ? fbu + FBM_UPAD : fbx);   // [NT / 64]; PACK: [64]
@@ -230,11 +294,13 @@ crb_controlled_kernel(const KParams<T> p, const CtrlParams<T> q) {
                 }
             }
         }
-        for (int idx = tp.t; idx < fb_n * fb_n2; idx += NT) {
-            const int i = idx / fb_n2, k = idx - i * fb_n2;
-            fbK[size_t(k) * fb_n + i] = p.fb_gain[idx];
+        if (!SG) {
+            for (int idx = tp.t; idx < fb_n * fb_n2; idx += NT) {
+                const int i = idx / fb_n2, k = idx - i * fb_n2;
+                fbK[size_t(k) * fb_n + i] = p.fb_gain[idx];
+            }
+            for (int idx = tp.t; idx < (fb_n2p - fb_n2) * fb_n; idx += NT) fbK[size_t(fb_n2) * fb_n + idx] = T(0);
         }
-        for (int idx = tp.t; idx < (fb_n2p - fb_n2) * fb_n; idx += NT) fbK[size_t(fb_n2) * fb_n + idx] = T(0);
         for (int idx = tp.t; idx < fb_n2p - fb_n2; idx += NT) fbx[fb_n2 + idx] = T(0);
         __syncthreads();
         if (fb_mfma) fbm_gain_fragments<T>(fb_af, fbK, fb_n, fb_n2p, tp.lane);
@@ -297,7 +363,8 @@ crb_controlled_kernel(const KParams<T> p, const CtrlParams<T> q) {
                                 if (ridx[c] >= 0) { fbx[ridx[c]] = rq[c] - xs[c]; fbx[fb_n + ridx[c]] = rv[c] - xs[3 + c]; }
                         }
                         T ufb[3];
-                        fb_feedback<T>(fb_mfma, fb_af, fbx, fbK, fbu, 1, 0, fb_n, fb_n2p, tp.lane, valid, ridx, ufb);
+                        if (SG) fb_feedback_streamed<T>(fbx, q.gain_t, fb_n, fb_n2p, valid, ridx, ufb);
+                        else fb_feedback<T>(fb_mfma, fb_af, fbx, fbK, fbu, 1, 0, fb_n, fb_n2p, tp.lane, valid, ridx, ufb);
 #pragma unroll
                         for (int c = 0; c < 3; ++c) ua[c] += ufb[c];
                         __syncthreads();   // (several waves per beam: every wave has read the error vector before the next stage overwrites it)

@@ -93,6 +93,10 @@ struct crb_plan {
     mutable Ladder ladders[N_LADDERS];
     mutable void* d_pieces = nullptr;
     mutable size_t pieces_cap = 0;
+    // ... and its closed loop with a gain too large for the LDS: the gain transposed, rebuilt by every call (callers overwrite
+    // gains in place, so nothing is cached by pointer)
+    mutable void* d_gain_t = nullptr;
+    mutable size_t gain_t_cap = 0;
     mutable void* d_rhs0 = nullptr;      // [B][2][n_node][4]: the RHS at the start of a crb_step_implicit_damped call (its a_0)
     // host-vector entry points (crb_rhs_host): full -> reduced map on the device, pinned staging, a stream of the plan's own
     mutable int32_t* d_red_map = nullptr;
@@ -699,6 +703,7 @@ extern "C" void crb_plan_destroy(crb_plan* p) {
         for (auto& set : p->stiff_sets) { (void)hipFree(set.lev); (void)hipFree(set.fin); }
         for (auto& lad : p->ladders) { (void)hipFree(lad.lev); (void)hipFree(lad.fin); }
         (void)hipFree(p->d_pieces);
+        (void)hipFree(p->d_gain_t);
         (void)hipFree(p->d_rhs0);
         (void)hipFree(p->d_red_map);
         if (p->h_stage) (void)hipHostFree(p->h_stage);
@@ -978,6 +983,13 @@ bool lean_controlled_ok(const crb_plan* p, bool fb) {
     const bool shape = p->lognw <= 2 && p->NT == (64 << p->lognw) && lean_grav_ok(p) && !env_set("CRB_DISABLE_LEAN");
     return fb ? (shape && p->lognw == 0 && p->levels >= 1 && p->levels <= 6 && !env_set("CRB_DISABLE_LEAN_FEEDBACK"))
               : (shape && p->levels_full >= 1 && !env_set("CRB_DISABLE_LEAN_IMPLICIT"));
+}
+// crb_solve_controlled, closed loop: the gain in LDS while it fits there (beams of up to ~30 elements), else streamed from a
+// transposed copy in global memory (crb_ctrl.h, SG).  CRB_CTRL_STREAM_GAIN=1: streamed whatever the size.
+bool ctrl_stream_gain(const crb_plan* p) {
+    if (const char* v = env("CRB_CTRL_STREAM_GAIN"))
+        if (std::atoi(v) != 0) return true;
+    return ctrl_lds_bytes<double>(p->NT, true, p->n_free) > size_t(160) * 1024;
 }
 // crb_solve_controlled per_wave: beams of 2 .. 32 slots packed G to a wave, implicit scheme through the lean kernel only
 bool controlled_pack_ok(const crb_plan* p, bool fb, bool lean) {
@@ -1595,9 +1607,8 @@ extern "C" int crb_solve_controlled(const crb_plan* p, void* x, double t0, doubl
     if (fb) {
         if (p->mixed_topology) return fail(CRB_EUNSUPPORTED, "crb_solve_controlled: one gain matrix for the ensemble needs one free-DOF set");
         if (f.held) return fail(CRB_EUNSUPPORTED, "crb_solve_controlled: the closed loop runs without a held force");
+        // (the closed loop's instances cover 0 .. 6 levels of M: uniform Nitinol rods of up to 255 elements keep 5, crb_ctrl_launch.h)
         if (p->levels > 6) return fail(CRB_EUNSUPPORTED, "crb_solve_controlled: unsupported number of cyclic-reduction levels");
-        if (ctrl_lds_bytes<double>(p->NT, true, p->n_free) > size_t(160) * 1024)
-            return fail(CRB_EUNSUPPORTED, "crb_solve_controlled: the gain matrix does not fit the LDS (beams of up to ~30 elements); use crb_step_rk4_feedback");
     } else if (ref) {
         return fail(CRB_EINVAL, "crb_solve_controlled: a reference without a gain");
     }
@@ -1656,6 +1667,21 @@ extern "C" int crb_solve_controlled(const crb_plan* p, void* x, double t0, doubl
     }
     HIP_TRY(hipMemcpy(p->d_pieces, pieces.data(), piece_bytes, hipMemcpyHostToDevice));
     q.pieces = static_cast<const crb::CtrlPiece*>(p->d_pieces);
+    // the streamed gain: its transposed copy, rebuilt from `gain` on every call (after the wait above: no launch reads the old one)
+    const bool stream_gain = fb && ctrl_stream_gain(p);
+    q.gain_t = nullptr;
+    if (stream_gain) {
+        const int n = p->n_free, rows = crb::ctrl_sg_rows(2 * n);
+        const size_t bytes = size_t(rows) * size_t(n) * sizeof(double);
+        if (p->gain_t_cap < bytes) {
+            if (p->d_gain_t) (void)hipFree(p->d_gain_t);
+            p->d_gain_t = nullptr; p->gain_t_cap = 0;
+            HIP_TRY(hipMalloc(&p->d_gain_t, bytes));
+            p->gain_t_cap = bytes;
+        }
+        HIP_TRY(crb::launch_gain_transpose(static_cast<const double*>(gain), static_cast<double*>(p->d_gain_t), n, rows, st));
+        q.gain_t = static_cast<const double*>(p->d_gain_t);
+    }
     q.n_pieces = int(pieces.size());
     q.n_rungs = rungs; q.n_iter = n_iter; q.n_intervals = n_intervals;
     q.rtol = ctl->rtol; q.atol = ctl->atol;
@@ -1700,8 +1726,8 @@ extern "C" int crb_solve_controlled(const crb_plan* p, void* x, double t0, doubl
     if (ctl->per_wave != 0 && !pack)
         return fail(CRB_EUNSUPPORTED, "crb_solve_controlled: per_wave packs beams of 2 .. 32 thread-carried nodes of the implicit scheme (gravity absent or canonical)");
     if (pack) k.G = p->G;
-    HIP_TRY(crb::launch_controlled(k, q, fb ? p->levels : p->levels_full, fb, lean_lognw, grav_on(p), pack, threads,
-                                   ctrl_lds_bytes<double>(threads, fb, p->n_free, fb ? -1 : lean_lognw), st));
+    HIP_TRY(crb::launch_controlled(k, q, fb ? p->levels : p->levels_full, fb, stream_gain, lean_lognw, grav_on(p), pack, threads,
+                                   ctrl_lds_bytes<double>(threads, fb, p->n_free, fb ? -1 : lean_lognw, stream_gain), st));
     return CRB_OK;
 }
 

@@ -251,7 +251,11 @@ int crb_step_implicit_damped(const crb_plan* plan, void* x, double t0, double h,
  * The step size is controlled INSIDE the kernel, per beam (one workgroup per beam; csrc/crb_ctrl.h):
  *   gain == NULL  the implicit midpoint rule of crb_step_implicit (order 2);
  *   gain != NULL  RK4 with u = K (ref - x) in every stage (order 4; device [n][2n] / [B][2n] like crb_step_rk4_feedback;
- *                 beams whose gain fits the LDS, up to ~30 elements; one free-DOF set, no held force).
+ *                 one free-DOF set, no held force).  The gain is held in LDS while it fits there (beams of up to ~30
+ *                 elements); larger gains are streamed: every call first writes a transposed copy [2n][n] that the plan owns
+ *                 (never cached: callers overwrite gains in place), and the node threads read their rows of it from global
+ *                 memory in every stage, with the multiply-adds in the LDS form's order.  Environment CRB_CTRL_STREAM_GAIN=1 forces the
+ *                 streamed form for every gain (tests).
  * by step doubling per piece -- a t_eval interval [t0 + k dt_eval, t0 + (k+1) dt_eval], cut at input->duration when the
  * impulse ends inside it (the impulse is then simply on or off within a piece): m = 2^r and 2m steps from the same state,
  * (fine - coarse) / (2^order - 1) measured in scipy's norm (RMS over the beam's reduced state -- its position half with

@@ -14,7 +14,7 @@ Reference interfaces mirrored (file:line under /root/reference/src/continuum_rob
 """
 import ctypes as C
 import pathlib
-from typing import Optional, Sequence, Union
+from typing import NamedTuple, Optional, Sequence, Union
 
 import numpy as np
 import pandas as pd
@@ -25,6 +25,20 @@ from .models.force_params import ForceParams
 
 _CSV_REQUIRED = ["length", "elastic_modulus", "moment_inertia", "density", "cross_area", "type", "boundary_condition"]
 _PARAM = {"u": 0, "w": 1, "phi": 2}
+
+# Default relative tolerance of solve_static (profiles/exp_static.py), measured on 4096 255-element nonlinear
+# rods under gravity and tip loads of 0 .. 5 N: at 1e-7, 20 of them (the lightest loads) stay above their fp64 residual
+# floor; at 1e-6 every beam converges.  Shorter rods reach far less: ~1e-9 at 64 elements, ~1e-12 at 10.
+STATIC_RTOL = 1e-6
+
+
+class StaticSolution(NamedTuple):
+    """Result of BeamEnsemble.solve_static: reduced positions [B, n], and per beam whether it converged, the Newton
+    iterations it used (-1 not converged, -2 non-finite) and its final scaled residual."""
+    q: torch.Tensor
+    converged: torch.Tensor
+    iterations: torch.Tensor
+    residual: torch.Tensor
 
 
 def _columns(parameters, need_fluid):
@@ -394,6 +408,69 @@ class BeamEnsemble:
         with self._on_device():
             nat.check(self._lib.crb_internal_force(self.plan.h, self._ptr(x), self._ptr(k), self._stream()))
         return self.unpack_vec(k)
+
+    def _positions(self, q_red) -> torch.Tensor:
+        """a fresh device-layout state with positions ``q_red`` [B, n] (zeros: None) and zero velocities"""
+        if q_red is None:
+            return torch.zeros_like(self.state)
+        q = self._dev(q_red, (self.n_beams, self.n))
+        return self.pack_state(torch.cat([q, torch.zeros_like(q)], dim=1))
+
+    def _tangent_index(self):
+        """(source entries of the [B, n_node, 3, 3, 3] block tensor, their rows / columns in the full DOF ordering, the
+        reduced -> full index [B, n] with padding entries pointing at a zero row, the padding mask) -- built once"""
+        if getattr(self, "_tangent_idx", None) is None:
+            nn = self.n_node
+            node, blk, r, c = np.meshgrid(np.arange(nn), np.arange(3), np.arange(3), np.arange(3), indexing="ij")
+            other = node + blk - 1
+            ok = (other >= 0) & (other < nn)
+            src = np.nonzero(ok.ravel())[0]
+            rows = (3 * node + r).ravel()[src]
+            cols = (3 * other + c).ravel()[src]
+            red = np.full((self.n_beams, self.n), 3 * nn, dtype=np.int64)   # (3 nn: the zero row / column appended below)
+            for b in range(self.n_beams):
+                fi = self.free_index_per_beam[b]
+                red[b, :fi.size] = fi
+            dev = lambda a: torch.as_tensor(a, dtype=torch.long, device=self.device)   # noqa: E731
+            self._tangent_idx = (dev(src), dev(rows), dev(cols), dev(red))
+        return self._tangent_idx
+
+    def tangent_stiffness(self, q_red=None) -> torch.Tensor:
+        """dk/dq of every beam, dense and reduced [B, n, n] (crb_tangent_stiffness): the Jacobian of the reference's
+        stiffness function (EulerBernoulliBeam.create_stiffness_function, euler_bernoulli_beam.py:163-219) at the reduced
+        positions ``q_red`` [B, n] (None: the resident state's).  For all-linear beams it is get_stiffness_matrix()
+        (``plan.stiffness()``) at any q; for nonlinear ones it is what that function refuses to give.  Padding rows and
+        columns of ``mixed_topology`` ensembles are zero."""
+        x = self.state if q_red is None else self._positions(q_red)
+        blocks = torch.empty((self.n_beams, self.n_node, 3, 3, 3), dtype=self.dtype, device=self.device)
+        with self._on_device():
+            nat.check(self._lib.crb_tangent_stiffness(self.plan.h, self._ptr(x), self._ptr(blocks), self._stream()))
+        src, rows, cols, red = self._tangent_index()
+        nf = 3 * self.n_node
+        dense = torch.zeros((self.n_beams, nf + 1, nf + 1), dtype=self.dtype, device=self.device)
+        dense[:, rows, cols] = blocks.reshape(self.n_beams, -1)[:, src]
+        bidx = torch.arange(self.n_beams, device=self.device)[:, None, None]
+        return dense[bidx, red[:, :, None], red[:, None, :]]
+
+    def solve_static(self, held_force=None, q0=None, load_steps: int = 8, max_iter: int = 20, rtol: float = STATIC_RTOL,
+                     atol: float = 0.0) -> StaticSolution:
+        """Static equilibrium k(q) = g(q) + u of every beam (crb_solve_static): the rest shape under the held generalised
+        force ``held_force`` (reduced [B, n], None = 0) and the plan's gravity -- where the reference's dynamic system
+        (dynamic_beam_model.py:294-328) has zero acceleration at zero velocity.  Newton from ``q0`` (reduced [B, n], None =
+        0) along the load path H(q, lam) = r(q) - (1 - lam) r(q0), lam = 0 -> 1 in ``load_steps`` increments (halved when
+        one does not converge within ``max_iter`` iterations): the equilibrium returned is the one that path reaches.  A
+        beam has converged when |r|inf <= rtol max(|k|inf, |g + u|inf) + atol.  One launch; fp64 ensembles only.
+        ``state`` and ``time`` are left alone: ``set_state`` starts dynamics from the result."""
+        x = self._positions(q0)
+        desc, keep = self._input_desc(held_force=held_force)
+        iters = torch.empty((self.n_beams,), dtype=torch.int32, device=self.device)
+        resid = torch.empty((self.n_beams,), dtype=self.dtype, device=self.device)
+        with self._on_device():
+            nat.check(self._lib.crb_solve_static(self.plan.h, self._ptr(x), C.byref(desc), int(load_steps), int(max_iter),
+                                                 float(rtol), float(atol), self._ptr(iters), self._ptr(resid), self._stream()))
+        self._keep = keep
+        q = self.unpack_state(x)[:, :self.n]
+        return StaticSolution(q, iters >= 0, iters, resid)
 
     def rhs_device(self, x: torch.Tensor, u: Optional[torch.Tensor] = None) -> torch.Tensor:
         """xdot in device layout for a state (and optional force) in device layout."""

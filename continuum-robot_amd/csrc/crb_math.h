@@ -446,4 +446,129 @@ CRB_HD void pcr_apply_final(const T* cf, const T r[3], T x[3]) {
     x[2] = cf[3] * r[1] + cf[4] * r[2];
 }
 
+// ------------------------------------------------------------------ tangent stiffness / static equilibrium (crb_static.h)
+// Forward-mode dual number: v + d eps, eps^2 = 0.  elem_force<Dual<T>> with one input seeded (d = 1) returns in the d parts
+// the column of the element tangent for that input, exactly (no hand-derived polynomials: every form of elem_force --
+// linear, nonlinear symmetric / literal, the corrected flag -- is differentiated as written).
+template <typename T>
+struct Dual {
+    T v, d;
+    CRB_HD Dual() : v(T(0)), d(T(0)) {}
+    CRB_HD Dual(double x) : v(T(x)), d(T(0)) {}
+    CRB_HD Dual(T x, T dx) : v(x), d(dx) {}
+};
+template <typename T> CRB_HD Dual<T> operator+(Dual<T> a, Dual<T> b) { return Dual<T>(a.v + b.v, a.d + b.d); }
+template <typename T> CRB_HD Dual<T> operator-(Dual<T> a, Dual<T> b) { return Dual<T>(a.v - b.v, a.d - b.d); }
+template <typename T> CRB_HD Dual<T> operator-(Dual<T> a) { return Dual<T>(-a.v, -a.d); }
+template <typename T> CRB_HD Dual<T> operator*(Dual<T> a, Dual<T> b) { return Dual<T>(a.v * b.v, a.d * b.v + a.v * b.d); }
+template <typename T> CRB_HD Dual<T> operator/(Dual<T> a, Dual<T> b) {
+    const T q = a.v / b.v;
+    return Dual<T>(q, (a.d - q * b.d) / b.v);
+}
+
+// Element tangent d[fl; fr] / d[ql; qr] (6 x 6, row = force component, column = input) of elem_force at (ql, qr): six
+// dual passes, one seed each.  The element forces fl / fr of the point come out of the first pass.
+template <typename T>
+CRB_HD void elem_tangent(const ElemCoef<T>& e, const T ql[3], const T qr[3], bool corrected, T K[6][6], T fl[3], T fr[3]) {
+    typedef Dual<T> D;
+    ElemCoef<D> ed;
+    ed.kind = e.kind;
+    ed.pad = 0;
+    for (int k = 0; k < 6; ++k) ed.c[k] = D(e.c[k], T(0));
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int s = 0; s < 6; ++s) {
+        D dl[3], dr[3], gl[3], gr[3];
+        for (int c = 0; c < 3; ++c) {
+            dl[c] = D(ql[c], s == c ? T(1) : T(0));
+            dr[c] = D(qr[c], s == 3 + c ? T(1) : T(0));
+        }
+        elem_force<D>(ed, dl, dr, corrected, gl, gr);
+        for (int c = 0; c < 3; ++c) {
+            K[c][s] = gl[c].d;
+            K[3 + c][s] = gr[c].d;
+            if (s == 0) { fl[c] = gl[c].v; fr[c] = gr[c].v; }
+        }
+    }
+}
+
+// d/dphi of gravity_segment: the segment force rotated by a further 90 degrees, [g1, -g0]
+template <typename T>
+CRB_HD void gravity_segment_dphi(const T g[2], T dg[2]) {
+    dg[0] = g[1];
+    dg[1] = -g[0];
+}
+
+// 3 x 3 blocks, row-major.  inv3: Gauss-Jordan elimination with partial pivoting (the raw adjugate loses the small
+// pivots of blocks that mix EA/L and 4EI/L).  A singular block gives non-finite entries.  The pivot search is a chain of
+// conditional row swaps with compile-time indices (a data-dependent row index would put the array in scratch memory).
+template <typename T>
+CRB_HD void inv3(const T M[9], T R[9]) {
+    T a[3][6];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) { a[r][c] = M[3 * r + c]; a[r][3 + c] = (r == c) ? T(1) : T(0); }
+    for (int k = 0; k < 3; ++k) {
+        for (int r = k + 1; r < 3; ++r) {
+            const bool sw = __builtin_fabs(double(a[r][k])) > __builtin_fabs(double(a[k][k]));
+            for (int c = 0; c < 6; ++c) {
+                const T x = a[k][c], y = a[r][c];
+                a[k][c] = sw ? y : x;
+                a[r][c] = sw ? x : y;
+            }
+        }
+        const T ip = T(1) / a[k][k];
+        for (int c = 0; c < 6; ++c) a[k][c] *= ip;
+        for (int r = 0; r < 3; ++r) {
+            if (r == k) continue;
+            const T f = a[r][k];
+            for (int c = 0; c < 6; ++c) a[r][c] -= f * a[k][c];
+        }
+    }
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) R[3 * r + c] = a[r][3 + c];
+}
+template <typename T>
+CRB_HD void mul3(const T X[9], const T Y[9], T R[9]) {
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) R[3 * r + c] = X[3 * r] * Y[c] + X[3 * r + 1] * Y[3 + c] + X[3 * r + 2] * Y[6 + c];
+}
+template <typename T>
+CRB_HD void mulv3(const T X[9], const T y[3], T r[3]) {
+    for (int i = 0; i < 3; ++i) r[i] = X[3 * i] * y[0] + X[3 * i + 1] * y[1] + X[3 * i + 2] * y[2];
+}
+
+// One node row of the block-tridiagonal system  A_i x_{i-s} + B_i x_i + C_i x_{i+s} = r_i  in 3 x 3 blocks on [u, w, phi].
+struct Row3 {
+    double A[9], B[9], C[9], r[3];
+};
+// Block-Jacobi normalisation of a row: B_i -> I (A, C, r multiplied by inv(B_i)).  What a level of the reduction reads
+// from the rows i - s and i + s is their normalised A, C and r.
+CRB_HD void row3_normalise(Row3& w) {
+    double Bi[9], t[9], v[3];
+    inv3<double>(w.B, Bi);
+    mul3<double>(Bi, w.A, t);
+    for (int k = 0; k < 9; ++k) w.A[k] = t[k];
+    mul3<double>(Bi, w.C, t);
+    for (int k = 0; k < 9; ++k) w.C[k] = t[k];
+    mulv3<double>(Bi, w.r, v);
+    for (int k = 0; k < 3; ++k) { w.r[k] = v[k]; w.B[k * 3 + 0] = k == 0; w.B[k * 3 + 1] = k == 1; w.B[k * 3 + 2] = k == 2; }
+}
+// One level of block cyclic reduction, factorisation and right-hand side together: with the normalised rows `me`, `lo` = row
+// i - s, `hi` = row i + s (zero blocks outside the beam) the couplings to i -+ s are eliminated:
+//   B' = I - A lo.C - C hi.A,   A' = -A lo.A,   C' = -C hi.C,   r' = r - A lo.r - C hi.r
+CRB_HD void row3_level(const Row3& me, const double loA[9], const double loC[9], const double lor[3], const double hiA[9],
+                       const double hiC[9], const double hir[3], Row3& out) {
+    double t[9], u[9], v[3], w[3];
+    mul3<double>(me.A, loC, t);
+    mul3<double>(me.C, hiA, u);
+    for (int k = 0; k < 9; ++k) out.B[k] = ((k % 4) == 0 ? 1.0 : 0.0) - t[k] - u[k];
+    mul3<double>(me.A, loA, t);
+    mul3<double>(me.C, hiC, u);
+    for (int k = 0; k < 9; ++k) { out.A[k] = -t[k]; out.C[k] = -u[k]; }
+    mulv3<double>(me.A, lor, v);
+    mulv3<double>(me.C, hir, w);
+    for (int k = 0; k < 3; ++k) out.r[k] = me.r[k] - v[k] - w[k];
+}
+
 }  // namespace crb

@@ -16,6 +16,7 @@
 #include "crb_lean_launch.h"
 #include "crb_loop_launch.h"
 #include "crb_ctrl_launch.h"
+#include "crb_static_launch.h"
 #include "crb_host.h"
 
 using namespace crb;
@@ -2172,5 +2173,84 @@ extern "C" int crb_gather_dof(const crb_plan* p, const void* x, int plane, int n
         hipLaunchKernelGGL((crb_gather_kernel<float>), dim3(grid), dim3(bs), 0, st, static_cast<const float*>(x), stride, off,
                            p->B, static_cast<float*>(out));
     HIP_TRY(hipGetLastError());
+    return CRB_OK;
+}
+
+// ------------------------------------------------------------------ static equilibrium, tangent stiffness (crb_static.h)
+namespace {
+// the tangent of a beam without a FIXED or PINNED node is singular (rigid translation): every node's u is free
+bool beam_supported(const std::vector<int32_t>& free_index, int n_elem) {
+    std::vector<uint8_t> u_free(size_t(n_elem) + 1, 0);
+    for (const int32_t f : free_index)
+        if (f % 3 == 0 && f / 3 <= n_elem) u_free[size_t(f / 3)] = 1;
+    for (const uint8_t u : u_free)
+        if (!u) return true;
+    return false;
+}
+int static_checks(const crb_plan* p, const char* who) {
+    if (int rc = need_device(p, who)) return rc;
+    if (p->NT > STATIC_MAX_NT)
+        return fail(CRB_EUNSUPPORTED, std::string(who) + ": beams of more than 256 thread-carried nodes are not supported");
+    return CRB_OK;
+}
+template <typename T>
+KParams<T> static_params(const crb_plan* p, const void* x) {
+    KParams<T> k = base_params<T>(p);
+    k.x = static_cast<T*>(const_cast<void*>(x));
+    k.levels = p->levels_full;   // (the static solve runs every level of the reduction: J is not diagonally dominant)
+    return k;
+}
+}  // namespace
+
+extern "C" int crb_tangent_stiffness(const crb_plan* p, const void* x, void* out, void* stream) {
+    if (int rc = static_checks(p, "crb_tangent_stiffness")) return rc;
+    if (!x || !out) return fail(CRB_EINVAL, "crb_tangent_stiffness: null pointer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int groups = (p->B + p->G - 1) / p->G;
+    if (p->dtype == CRB_F64) {
+        StaticParams<double> q{};
+        q.blocks = static_cast<double*>(out);
+        HIP_TRY(crb::launch_tangent(static_params<double>(p, x), q, groups, p->NT, st));
+    } else {
+        StaticParams<float> q{};
+        q.blocks = static_cast<float*>(out);
+        HIP_TRY(crb::launch_tangent(static_params<float>(p, x), q, groups, p->NT, st));
+    }
+    return CRB_OK;
+}
+
+extern "C" int crb_solve_static(const crb_plan* p, void* x, const crb_input_desc* in, int load_steps, int max_iter, double rtol,
+                                double atol, int32_t* iters, void* residual, void* stream) {
+    if (int rc = static_checks(p, "crb_solve_static")) return rc;
+    if (p->dtype != CRB_F64)   // (the tangent's condition number reaches 1e7 at 10 elements and grows with the element count)
+        return fail(CRB_EUNSUPPORTED, "crb_solve_static: the static solve needs an fp64 plan");
+    if (!x || !iters) return fail(CRB_EINVAL, "crb_solve_static: null pointer");
+    // (bounds of the per-beam work: at most 2^6 load_steps + 1 accepted increments, 7 attempts of max_iter + 1 evaluations
+    //  between two of them -- crb_static.h)
+    if (load_steps < 1 || load_steps > 4096) return fail(CRB_EINVAL, "crb_solve_static: load_steps must be in [1, 4096]");
+    if (max_iter < 1 || max_iter > 1000) return fail(CRB_EINVAL, "crb_solve_static: max_iter must be in [1, 1000]");
+    if (!(rtol >= 0.0) || !(atol >= 0.0)) return fail(CRB_EINVAL, "crb_solve_static: rtol and atol must be >= 0");
+    Forcing f;
+    if (int rc = decode_input(p, in, "crb_solve_static", &f)) return rc;
+    if (f.impulse) return fail(CRB_EINVAL, "crb_solve_static: an impulse input has no static equilibrium (held forces only)");
+    if (p->beam_free_index.empty()) {
+        if (!beam_supported(p->free_index, p->n_elem))
+            return fail(CRB_EINVAL, "crb_solve_static: the beams have no FIXED or PINNED node (singular tangent stiffness)");
+    } else {
+        for (size_t b = 0; b < p->beam_free_index.size(); ++b)
+            if (!beam_supported(p->beam_free_index[b], p->beam_n_elem[b]))
+                return fail(CRB_EINVAL, "crb_solve_static: beam " + std::to_string(b) +
+                                            " has no FIXED or PINNED node (singular tangent stiffness)");
+    }
+    KParams<double> k = static_params<double>(p, x);
+    set_io(k, f);
+    StaticParams<double> q{};
+    q.load_steps = load_steps;
+    q.max_iter = max_iter;
+    q.rtol = rtol;
+    q.atol = atol;
+    q.iters = iters;
+    q.residual = static_cast<double*>(residual);
+    HIP_TRY(crb::launch_static(k, q, (p->B + p->G - 1) / p->G, p->NT, static_cast<hipStream_t>(stream)));
     return CRB_OK;
 }

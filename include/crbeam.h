@@ -192,6 +192,24 @@ int crb_rhs(const crb_plan* plan, const void* x, const void* u, void* xdot, void
 int crb_rhs_host(const crb_plan* plan, const double* x_red, const double* u_red, double* xdot_red);
 int crb_internal_force_host(const crb_plan* plan, const double* q_red, double* k_red);
 
+/* Tangent stiffness dk/dq of every beam at its positions: the derivative of
+ * EulerBernoulliBeam.create_stiffness_function() (euler_bernoulli_beam.py:163-219) -- what get_stiffness_matrix()
+ * (euler_bernoulli_beam.py:422-511) returns for all-linear beams, for nonlinear beams at any q.
+ * dk/dq at positions x (plane 0 of x[B][2][n_node][4]); out: device [B][n_node][3][3][3] plan dtype,
+ * block 0/1/2 = coupling to the left node / own / right node, rows and cols [u, w, phi].  Constrained DOFs have
+ * identity rows and zero columns.  Beams of up to 256 thread-carried nodes, fp64 and fp32 plans. */
+int crb_tangent_stiffness(const crb_plan* plan, const void* x, void* out, void* stream);
+/* Static equilibrium: the q at which DynamicEulerBernoulliBeam.get_dynamic_system() (dynamic_beam_model.py:294-328)
+ * returns zero acceleration at v = 0, i.e. k(q) = g(q) + u (drag vanishes at rest).  Newton on the block-tridiagonal
+ * tangent with load continuation from the initial guess (load_steps <= 4096 increments, each halved up to 6 times when it
+ * does not converge within max_iter <= 1000 steps, never below 1/64 of its nominal size), converged when |k - g - u|inf <= rtol max(|k|inf, |g + u|inf) + atol per beam.
+ * Equilibrium k(q) = g(q) + u of every beam; x: in = initial guess (plane 0), out = solution, plane 1 zeroed.
+ * input: kind CRB_INPUT_NONE, f_held = u or NULL.  iters: device int32 [B], >= 0 Newton iterations used,
+ * -1 not converged, -2 non-finite.  residual: device [B] plan dtype, final scaled residual (may be NULL).
+ * fp64 plans only (CRB_EUNSUPPORTED otherwise); every beam needs a FIXED or PINNED node; up to 256 thread-carried nodes. */
+int crb_solve_static(const crb_plan* plan, void* x, const crb_input_desc* input, int load_steps, int max_iter,
+                     double rtol, double atol, int32_t* iters, void* residual, void* stream);
+
 /* n_steps classical RK4 steps of size dt, in place, in ONE launch (replaces the
  * scipy.solve_ivp call sites example_utilities.py:153-159, lqr_control.py:117-125).  The clock
  * starts at t0 and accumulates by addition (t <- t + dt); stage times t, t+dt/2, t+dt.

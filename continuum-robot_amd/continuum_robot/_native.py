@@ -60,6 +60,12 @@ class InputDesc(C.Structure):
     ]
 
 
+class InputTangent(C.Structure):
+    """crb_input_tangent: per-direction derivatives of the impulse amplitude ([n_dir][B]) and of the held force
+    ([n_dir][B][n_node][4]), device pointers or None"""
+    _fields_ = [("d_amp", C.c_void_p), ("df_held", C.c_void_p)]
+
+
 class RecordDesc(C.Structure):
     _fields_ = [("plane", C.c_int32), ("node", C.c_int32), ("dof", C.c_int32), ("every", C.c_int32), ("out", C.c_void_p)]
 
@@ -144,6 +150,9 @@ def load():
     L.crb_tangent_stiffness.argtypes = [vp, vp, vp, vp]
     L.crb_solve_static.argtypes = [vp, vp, C.POINTER(InputDesc), i32, i32, C.c_double, C.c_double, vp, vp, vp]
     L.crb_feedback_work_bytes.restype = C.c_size_t
+    L.crb_rhs_jvp.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    L.crb_step_rk4_tangent.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, i32, C.POINTER(InputDesc),
+                                       C.POINTER(InputTangent), _dp, vp]
     L.crb_step_rk4_feedback.argtypes = [vp, vp, C.c_double, C.c_double, i32, vp, vp, C.POINTER(InputDesc), vp,
                                         C.POINTER(C.c_double), vp]
     _lib = L

@@ -513,6 +513,139 @@ class BeamEnsemble:
         self.time = t_end.value
         return (self.time, samples) if record is not None else self.time
 
+    # ------------------------------------------------------------------ tangent-linear model (crb_tangent.h)
+    def _dir_index(self):
+        """(state, force) gather indices of reduced [B, 2n] / [B, n] entries into the flattened device layouts [B, 2, n_node,
+        4] / [B, n_node, 4] with one extra zero entry at the end, to which padding entries of mixed_topology point -- built
+        once"""
+        if getattr(self, "_dir_idx", None) is None:
+            nn, n, B = self.n_node, self.n, self.n_beams
+            sidx = np.full((B, 2 * n), B * 2 * nn * 4, dtype=np.int64)
+            fidx = np.full((B, n), B * nn * 4, dtype=np.int64)
+            for b in range(B):
+                fi = self.free_index_per_beam[b].astype(np.int64)
+                rec = (fi // 3) * 4 + fi % 3
+                sidx[b, :fi.size] = b * 2 * nn * 4 + rec
+                sidx[b, n:n + fi.size] = b * 2 * nn * 4 + nn * 4 + rec
+                fidx[b, :fi.size] = b * nn * 4 + rec
+            dev = lambda a: torch.as_tensor(a.ravel(), dtype=torch.long, device=self.device)   # noqa: E731
+            self._dir_idx = (dev(sidx), dev(fidx))
+        return self._dir_idx
+
+    def _dirs(self, v, width, what):
+        """reduced [B, width] or [D, B, width] -> ([D, B, width] on the device, whether the input had no direction axis)"""
+        t = torch.as_tensor(v, dtype=self.dtype, device=self.device)
+        single = t.dim() == 2
+        if single:
+            t = t.unsqueeze(0)
+        if t.dim() != 3 or tuple(t.shape[1:]) != (self.n_beams, width) or t.shape[0] < 1:
+            raise ValueError(f"{what}: expected shape [{self.n_beams}, {width}] or [D >= 1, {self.n_beams}, {width}], "
+                             f"got {tuple(t.shape)}")
+        return t.contiguous(), single
+
+    def _pack_dirs(self, v, state: bool) -> torch.Tensor:
+        """[D, B, 2n] (state) / [D, B, n] (force) reduced -> device layout [D, B, 2, n_node, 4] / [D, B, n_node, 4], on the
+        device in one scatter"""
+        sidx, fidx = self._dir_index()
+        idx = sidx if state else fidx
+        D = v.shape[0]
+        rec = (2 if state else 1) * self.n_node * 4
+        flat = torch.zeros((D, self.n_beams * rec + 1), dtype=self.dtype, device=self.device)
+        flat[:, idx] = v.reshape(D, -1)        # (padding entries all land on the last, discarded column)
+        return flat[:, :-1].reshape((D, self.n_beams) + ((2,) if state else ()) + (self.n_node, 4)).contiguous()
+
+    def _unpack_dirs(self, x: torch.Tensor) -> torch.Tensor:
+        """device layout [D, B, 2, n_node, 4] -> reduced [D, B, 2n] (padding entries 0)"""
+        sidx, _ = self._dir_index()
+        D = x.shape[0]
+        flat = torch.cat([x.reshape(D, -1), torch.zeros((D, 1), dtype=self.dtype, device=self.device)], dim=1)
+        return flat[:, sidx].reshape(D, self.n_beams, 2 * self.n)
+
+    def rhs_jvp(self, dx_red, x_red=None, u_red=None, du_red=None):
+        """Forward-mode derivative of the RHS (crb_rhs_jvp): returns (xdot, dxdot) with xdot = f(x, u) reduced [B, 2n] -- the
+        reference's dynamic_system(t, x, u), dynamic_beam_model.py:294-362 -- and dxdot = df/dx dx + df/du du, exact (dual
+        numbers, no finite differences), in the shape of ``dx_red``: [B, 2n] or D directions [D, B, 2n] in one launch.
+        ``x_red`` reduced [B, 2n] (None: the resident state), ``u_red`` [B, n] held force (None = 0), ``du_red`` its tangent
+        [B, n] / [D, B, n] (None = 0).  fp64 ensembles only."""
+        dx, single = self._dirs(dx_red, 2 * self.n, "rhs_jvp: dx_red")
+        D = dx.shape[0]
+        du = None
+        if du_red is not None:
+            du, _ = self._dirs(du_red, self.n, "rhs_jvp: du_red")
+            if du.shape[0] != D:
+                du = du.expand(D, -1, -1) if du.shape[0] == 1 else None
+            if du is None:
+                raise ValueError("rhs_jvp: du_red must have the directions of dx_red")
+        x = self.state if x_red is None else self.pack_state(x_red)
+        u = None if u_red is None else self.pack_vec(u_red)
+        dxd = self._pack_dirs(dx, True)
+        dud = None if du is None else self._pack_dirs(du, False)
+        xdot = torch.empty_like(x)
+        dxdot = torch.empty_like(dxd)
+        with self._on_device():
+            nat.check(self._lib.crb_rhs_jvp(self.plan.h, self._ptr(x), self._ptr(u), self._ptr(dxd), self._ptr(dud), int(D),
+                                            self._ptr(xdot), self._ptr(dxdot), self._stream()))
+        out = self._unpack_dirs(dxdot)
+        return self.unpack_state(xdot), (out[0] if single else out)
+
+    def linearize(self, x_red=None, u_red=None):
+        """The linearised dynamics at (x, u): (A [B, 2n, 2n], Bu [B, 2n, n]), the dense Jacobians d f / d x and d f / d u of
+        the reference's dynamic_system (dynamic_beam_model.py:294-362) -- for a linear beam at rest without drag or gravity,
+        LinearQuadraticRegulator's A = [[0, I], [-M^-1 K, 0]] and B = [0; M^-1] (linear_quadratic_regulator.py:84-147); for a
+        nonlinear, dragged, gravity-loaded rod the exact Jacobian about any operating point, e.g. its equilibrium from
+        solve_static.  Two launches of crb_rhs_jvp with identity seeds (2n state, n input directions).  ``x_red`` reduced
+        [B, 2n] (None: the resident state), ``u_red`` [B, n] (None = 0).  Padding rows and columns of ``mixed_topology``
+        ensembles are zero."""
+        B, n = self.n_beams, self.n
+        eye2 = torch.eye(2 * n, dtype=self.dtype, device=self.device)
+        _, dA = self.rhs_jvp(eye2[:, None, :].expand(2 * n, B, 2 * n), x_red, u_red)
+        eye1 = torch.eye(n, dtype=self.dtype, device=self.device)
+        _, dB = self.rhs_jvp(torch.zeros((n, B, 2 * n), dtype=self.dtype, device=self.device), x_red, u_red,
+                             eye1[:, None, :].expand(n, B, n))
+        return dA.permute(1, 2, 0).contiguous(), dB.permute(1, 2, 0).contiguous()
+
+    def step_tangent(self, n_steps: int, dt: float, dx0_red, impulse_amp=None, impulse_duration: float = 0.01,
+                     impulse_index: int = -2, held_force=None, d_impulse_amp=None, d_held_force=None,
+                     t0: Optional[float] = None):
+        """``step()`` with the tangent of the rollout alongside (crb_step_rk4_tangent): advances ``state`` and ``time`` exactly as
+        step() does, and returns dx(T) = dx(T)/dx(0) dx0 + dx(T)/d amp d_impulse_amp + dx(T)/d f_held d_held_force in the shape
+        of ``dx0_red`` ([B, 2n] or D directions [D, B, 2n], one launch).  An identity batch of seeds (D = 2n) gives the
+        state-transition matrix.  ``d_impulse_amp`` [B] / [D, B] and ``d_held_force`` [B, n] / [D, B, n] are the tangents of
+        ``impulse_amp`` and ``held_force`` (None = 0; a [B] / [B, n] tangent is used for every direction).  The derivative is
+        that of the discrete RK4 map itself, exact.  fp64 ensembles only."""
+        dx, single = self._dirs(dx0_red, 2 * self.n, "step_tangent: dx0_red")
+        D = dx.shape[0]
+        if t0 is not None:
+            self.time = float(t0)
+        if d_impulse_amp is not None and impulse_amp is None:
+            impulse_amp = torch.zeros((self.n_beams,), dtype=self.dtype, device=self.device)
+        desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index, held_force)
+        dxd = self._pack_dirs(dx, True)
+        tan = nat.InputTangent()
+        if d_impulse_amp is not None:
+            da = torch.as_tensor(d_impulse_amp, dtype=self.dtype, device=self.device)
+            if tuple(da.shape) not in ((self.n_beams,), (D, self.n_beams)):
+                raise ValueError(f"step_tangent: d_impulse_amp must be [{self.n_beams}] or [{D}, {self.n_beams}]")
+            da = da.expand(D, self.n_beams).contiguous()
+            tan.d_amp = da.data_ptr()
+            keep.append(da)
+        if d_held_force is not None:
+            dh, _ = self._dirs(d_held_force, self.n, "step_tangent: d_held_force")
+            if dh.shape[0] not in (1, D):
+                raise ValueError("step_tangent: d_held_force must have the directions of dx0_red")
+            dhd = self._pack_dirs(dh.expand(D, -1, -1), False)
+            tan.df_held = dhd.data_ptr()
+            keep.append(dhd)
+        t_end = C.c_double(0.0)
+        with self._on_device():
+            nat.check(self._lib.crb_step_rk4_tangent(self.plan.h, self._ptr(self.state), self._ptr(dxd), int(D), self.time,
+                                                     float(dt), int(n_steps), C.byref(desc), C.byref(tan), C.byref(t_end),
+                                                     self._stream()))
+        self._keep = keep + [dxd]
+        self.time = t_end.value
+        out = self._unpack_dirs(dxd)
+        return out[0] if single else out
+
     def step_implicit(self, n_steps: int, h: float, n_iter: int = 2, impulse_amp=None, impulse_duration: float = 0.01,
                       impulse_index: int = -2, held_force=None, t0: Optional[float] = None, record=None,
                       record_every: int = 1, rho_inf: float = 1.0):

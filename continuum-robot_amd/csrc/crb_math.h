@@ -465,6 +465,16 @@ template <typename T> CRB_HD Dual<T> operator/(Dual<T> a, Dual<T> b) {
     const T q = a.v / b.v;
     return Dual<T>(q, (a.d - q * b.d) / b.v);
 }
+// |x| and sin / cos on dual numbers (drag_force and gravity_segment on dual velocities and rotations, crb_tangent.h).  At
+// x = 0 the derivative of |x| is taken as +1: drag_force multiplies it by v = 0, so -c v|v| has the exact derivative 0 there.
+template <typename T> CRB_HD Dual<T> crb_abs(Dual<T> x) { return x.v < T(0) ? -x : x; }
+template <typename T>
+CRB_HD void crb_sincos(Dual<T> x, Dual<T>* s, Dual<T>* c) {
+    T sv, cv;
+    crb_sincos(x.v, &sv, &cv);
+    *s = Dual<T>(sv, cv * x.d);
+    *c = Dual<T>(cv, -sv * x.d);
+}
 
 // Element tangent d[fl; fr] / d[ql; qr] (6 x 6, row = force component, column = input) of elem_force at (ql, qr): six
 // dual passes, one seed each.  The element forces fl / fr of the point come out of the first pass.

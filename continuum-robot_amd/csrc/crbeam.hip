@@ -17,6 +17,7 @@
 #include "crb_loop_launch.h"
 #include "crb_ctrl_launch.h"
 #include "crb_static_launch.h"
+#include "crb_tangent_launch.h"
 #include "crb_host.h"
 #include "crb_blocked.h"
 
@@ -100,6 +101,7 @@ struct crb_plan {
     mutable void* d_gain_t = nullptr;
     mutable size_t gain_t_cap = 0;
     mutable void* d_rhs0 = nullptr;      // [B][2][n_node][4]: the RHS at the start of a crb_step_implicit_damped call (its a_0)
+    mutable void* d_tan_x0 = nullptr;    // [B][2][n_node][4]: the base state at the start of a crb_step_rk4_tangent call (n_dir > 1)
     // host-vector entry points (crb_rhs_host): full -> reduced map on the device, pinned staging, a stream of the plan's own
     mutable int32_t* d_red_map = nullptr;
     mutable double* h_stage = nullptr;   // pinned + mapped: [2n | n | 2n] doubles (x, u, out)
@@ -731,6 +733,7 @@ extern "C" void crb_plan_destroy(crb_plan* p) {
         (void)hipFree(p->d_pieces);
         (void)hipFree(p->d_gain_t);
         (void)hipFree(p->d_rhs0);
+        (void)hipFree(p->d_tan_x0);
         (void)hipFree(p->d_red_map);
         if (p->h_stage) (void)hipHostFree(p->h_stage);
         if (p->host_stream) (void)hipStreamDestroy(p->host_stream);
@@ -2314,5 +2317,69 @@ extern "C" int crb_solve_static(const crb_plan* p, void* x, const crb_input_desc
     q.iters = iters;
     q.residual = static_cast<double*>(residual);
     HIP_TRY(crb::launch_static(k, q, (p->B + p->G - 1) / p->G, p->NT, static_cast<hipStream_t>(stream)));
+    return CRB_OK;
+}
+
+// ------------------------------------------------------------------ tangent-linear RHS and rollout (crb_tangent.h)
+namespace {
+int tangent_checks(const crb_plan* p, int n_dir, const char* who) {
+    if (int rc = need_device(p, who)) return rc;
+    if (p->dtype != CRB_F64) return fail(CRB_EUNSUPPORTED, std::string(who) + ": the tangent kernels need an fp64 plan");
+    if (p->NT > TANGENT_MAX_NT)
+        return fail(CRB_EUNSUPPORTED, std::string(who) + ": beams of more than 256 thread-carried nodes are not supported");
+    if (n_dir < 1 || n_dir > 65535) return fail(CRB_EINVAL, std::string(who) + ": n_dir must be in [1, 65535]");
+    return CRB_OK;
+}
+}  // namespace
+
+extern "C" int crb_rhs_jvp(const crb_plan* p, const void* x, const void* u, const void* dx, const void* du, int n_dir, void* xdot,
+                           void* dxdot, void* stream) {
+    if (int rc = tangent_checks(p, n_dir, "crb_rhs_jvp")) return rc;
+    if (!x || !dx || !dxdot) return fail(CRB_EINVAL, "crb_rhs_jvp: null pointer");
+    if (x == xdot || dx == dxdot) return fail(CRB_EINVAL, "crb_rhs_jvp: outputs must not alias inputs");
+    KParams<double> k = base_params<double>(p);
+    k.x = static_cast<double*>(const_cast<void*>(x));
+    k.u_held = static_cast<const double*>(u);
+    k.out = static_cast<double*>(xdot);
+    TangentParams<double> q{};
+    q.dx = static_cast<double*>(const_cast<void*>(dx));
+    q.dxdot = static_cast<double*>(dxdot);
+    q.du_held = static_cast<const double*>(du);
+    HIP_TRY(crb::launch_jvp_rhs(k, q, (p->B + p->G - 1) / p->G, n_dir, p->NT, static_cast<hipStream_t>(stream)));
+    return CRB_OK;
+}
+
+extern "C" int crb_step_rk4_tangent(const crb_plan* p, void* x, void* dx, int n_dir, double t0, double dt, int n_steps,
+                                    const crb_input_desc* in, const crb_input_tangent* din, double* t_end, void* stream) {
+    if (int rc = tangent_checks(p, n_dir, "crb_step_rk4_tangent")) return rc;
+    if (!x || !dx) return fail(CRB_EINVAL, "crb_step_rk4_tangent: null state or tangent");
+    if (n_steps < 0) return fail(CRB_EINVAL, "crb_step_rk4_tangent: n_steps must be >= 0");
+    if (!(dt > 0)) return fail(CRB_EINVAL, "crb_step_rk4_tangent: dt must be positive");
+    Forcing f;
+    if (int rc = decode_input(p, in, "crb_step_rk4_tangent", &f)) return rc;
+    if (din && din->d_amp && !f.impulse)
+        return fail(CRB_EINVAL, "crb_step_rk4_tangent: d_amp needs an impulse input (its amplitude is what it differentiates)");
+    if (t_end) *t_end = clock_after(t0, dt, n_steps);
+    if (n_steps == 0) return CRB_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    KParams<double> k = base_params<double>(p);
+    k.x = static_cast<double*>(x);
+    set_io(k, f);
+    k.t0 = t0; k.dt = dt; k.n_steps = n_steps;
+    arm_status(p, k, n_steps);
+    TangentParams<double> q{};
+    q.x0 = k.x;
+    if (n_dir > 1) {   // (instance d = 0 writes the base back while the others may still be loading it: they read a copy)
+        const size_t bytes = size_t(p->B) * 2 * p->n_node * 4 * sizeof(double);
+        if (!p->d_tan_x0) HIP_TRY(hipMalloc(&p->d_tan_x0, bytes));
+        HIP_TRY(hipMemcpyAsync(p->d_tan_x0, x, bytes, hipMemcpyDeviceToDevice, st));
+        q.x0 = static_cast<const double*>(p->d_tan_x0);
+    }
+    q.dx = static_cast<double*>(dx);
+    if (din) {
+        q.du_held = static_cast<const double*>(din->df_held);
+        q.d_amp = static_cast<const double*>(din->d_amp);
+    }
+    HIP_TRY(crb::launch_jvp_step(k, q, (p->B + p->G - 1) / p->G, n_dir, p->NT, st));
     return CRB_OK;
 }

@@ -216,6 +216,32 @@ int crb_tangent_stiffness(const crb_plan* plan, const void* x, void* out, void* 
 int crb_solve_static(const crb_plan* plan, void* x, const crb_input_desc* input, int load_steps, int max_iter,
                      double rtol, double atol, int32_t* iters, void* residual, void* stream);
 
+/* Tangents of the inputs of crb_step_rk4_tangent, per direction (device, fp64; layouts of crb_input_desc with a leading
+ * direction index). */
+typedef struct crb_input_tangent {
+    const void* d_amp;    /* device [n_dir][B]: derivative of the impulse amplitude per direction, or NULL (= 0) */
+    const void* df_held;  /* device [n_dir][B][n_node][4]: derivative of the held force, or NULL (= 0) */
+} crb_input_tangent;
+
+/* Forward-mode derivative (Jacobian-vector products) of the RHS: the derivative of get_dynamic_system()(t, x, u)
+ * (dynamic_beam_model.py:294-362) along n_dir directions per beam, exact (dual numbers through the element forces, drag
+ * and gravity, the same cyclic-reduction mass solve as crb_rhs; no finite differences).
+ * xdot = f(x, u) and dxdot[d] = df/dx·dx[d] + df/du·du[d], for d < n_dir.
+ * x: [B][2][n_node][4]; u: [B][n_node][4] or NULL; dx, dxdot: [n_dir][B][2][n_node][4];
+ * du: [n_dir][B][n_node][4] or NULL; xdot: may be NULL.  Outputs must not alias inputs.
+ * fp64 plans only (CRB_EUNSUPPORTED), beams of up to 256 thread-carried nodes, 1 <= n_dir <= 65535. */
+int crb_rhs_jvp(const crb_plan* plan, const void* x, const void* u, const void* dx, const void* du, int n_dir,
+                void* xdot, void* dxdot, void* stream);
+
+/* crb_step_rk4 (same clock, same input), with the tangent dx [n_dir][B][2][n_node][4] of the rollout propagated
+ * in place: dx(T) = ∂x(T)/∂x(0)·dx(0) + ∂x(T)/∂amp·d_amp + ∂x(T)/∂f_held·df_held.
+ * The derivative of the discrete RK4 map crb_step_rk4 applies (the scipy.solve_ivp call sites it replaces,
+ * example_utilities.py:153-159, lqr_control.py:117-125), in ONE launch: an identity batch of seeds (n_dir = 2 n_free)
+ * gives the state-transition matrix.  x advances exactly as under crb_step_rk4; *t_end as there.  dinput may be NULL;
+ * d_amp needs an impulse input.  fp64 plans only, beams of up to 256 thread-carried nodes, 1 <= n_dir <= 65535. */
+int crb_step_rk4_tangent(const crb_plan* plan, void* x, void* dx, int n_dir, double t0, double dt, int n_steps,
+                         const crb_input_desc* input, const crb_input_tangent* dinput, double* t_end, void* stream);
+
 /* n_steps classical RK4 steps of size dt, in place, in ONE launch (replaces the
  * scipy.solve_ivp call sites example_utilities.py:153-159, lqr_control.py:117-125).  The clock
  * starts at t0 and accumulates by addition (t <- t + dt); stage times t, t+dt/2, t+dt.

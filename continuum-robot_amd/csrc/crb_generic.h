@@ -138,6 +138,49 @@ struct Topo {
     __device__ __forceinline__ int thread_of(int jj) const { return base + ((jj & nwm1) << 6) + (jj >> lognw); }
 };
 
+// The slot a thread carries: G beams of S slots in the workgroup (thread = g S + j) when G > 1 or lognw == 0, else one beam
+// per workgroup with slot j in wave j % NW, lane j / NW.  g = the beam's index inside the workgroup.  A padding thread
+// becomes an isolated dummy node of beam 0 (j = 0, S = 1, its own base, no other wave; g = G); tp.lognw stays the launch
+// value (the barrier / shuffle choice must be workgroup-uniform).
+template <typename T>
+__device__ __forceinline__ Topo make_topo(const KParams<T>& p, int& g) {
+    Topo tp;
+    tp.t = threadIdx.x;
+    tp.lane = tp.t & 63;
+    tp.S = p.S;
+    tp.lognw = p.lognw;
+    tp.nwm1 = (1 << p.lognw) - 1;
+    if (p.G > 1 || p.lognw == 0) {
+        g = tp.t / p.S;
+        tp.j = tp.t - g * p.S;
+        tp.base = g * p.S;
+    } else {
+        g = 0;
+        tp.j = (tp.lane << p.lognw) + (tp.t >> 6);
+        tp.base = 0;
+    }
+    const int beam = blockIdx.x * p.G + g;
+    tp.valid = (g < p.G) && (tp.j < p.S) && (beam < p.B);
+    tp.beam = tp.valid ? beam : 0;
+    if (!tp.valid) { tp.j = 0; tp.S = 1; tp.base = tp.t; tp.nwm1 = 0; g = p.G; }
+    return tp;
+}
+
+// The constants of a thread without a slot: all coefficients 0 (every formula returns zero forces), no gravity entry
+template <typename T>
+__device__ __forceinline__ SlotConst<T> padding_slot() {
+    SlotConst<T> sc;
+    sc.elem.kind = KIND_NONE;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) sc.elem.c[k] = T(0);
+    sc.drag = sc.half_mass = T(0);
+    sc.mask[0] = sc.mask[1] = sc.mask[2] = T(0);
+    sc.grav.phiA = sc.grav.phiB = -1;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { sc.grav.segA[c] = sc.grav.segB[c] = -1; sc.grav.comp[c] = 0; }
+    return sc;
+}
+
 template <typename T>
 __device__ __forceinline__ T shfl_from(T v, int src_lane) {
     return __shfl(v, src_lane, 64);

@@ -578,9 +578,7 @@ crb_step_lean_kernel(const KParams<T> p_formal) {
 #pragma unroll
             for (int k = 0; k < 5; ++k) cf.fin[k] = p.pcr_final[size_t(beam) * p.fin_stride + size_t(j) * PCR_FINAL_VALS + k];
         } else {
-            ec.kind = KIND_NONE;
-#pragma unroll
-            for (int k = 0; k < 6; ++k) ec.c[k] = T(0);
+            ec = padding_slot<T>().elem;
 #pragma unroll
             for (int l = 0; l < LV; ++l)
 #pragma unroll
@@ -968,9 +966,7 @@ __global__ void __launch_bounds__(64 << LOGNW, (sizeof(T) == 4 && LOGNW <= 2) ? 
 #pragma unroll
             for (int k = 0; k < 5; ++k) cf.fin[k] = p.pcr_final[size_t(beam) * p.fin_stride + size_t(j) * PCR_FINAL_VALS + k];
         } else {
-            ec.kind = KIND_NONE;
-#pragma unroll
-            for (int k = 0; k < 6; ++k) ec.c[k] = T(0);
+            ec = padding_slot<T>().elem;
 #pragma unroll
             for (int l = 0; l < LV; ++l)
 #pragma unroll

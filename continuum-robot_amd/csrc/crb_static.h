@@ -34,7 +34,7 @@
 // node row by its pivoted block inverse (crb_math.h: row3_normalise / row3_level), so the neighbours' diagonal blocks need
 // not be exchanged: 21 values per node and level.
 //
-// Mapping.  As the implicit stepper (crb_stiff.h): Topo, beams of fewer than 64 slots packed G to a wave, longer ones one
+// Mapping.  make_topo (crb_generic.h): beams of fewer than 64 slots packed G to a wave, longer ones one
 // beam per workgroup of up to 4 waves (256 thread-carried nodes).  The whole solve is one launch; every beam keeps its own
 // increment / iteration state (uniform over its threads: all of them reduce the same norms), a beam that has converged or
 // failed is switched off by predication, and a workgroup leaves when all of its beams are done.
@@ -84,31 +84,6 @@ __device__ __forceinline__ StaticLds<T> carve_static_lds(int NT) {
     return l;
 }
 
-// The slot a thread carries (crb_implicit_kernel's mapping); g = beam of the thread inside its workgroup
-template <typename T>
-__device__ __forceinline__ Topo static_topo(const KParams<T>& p, int& g) {
-    Topo tp;
-    tp.t = threadIdx.x;
-    tp.lane = tp.t & 63;
-    tp.S = p.S;
-    tp.lognw = p.lognw;
-    tp.nwm1 = (1 << p.lognw) - 1;
-    if (p.G > 1 || p.lognw == 0) {
-        g = tp.t / p.S;
-        tp.j = tp.t - g * p.S;
-        tp.base = g * p.S;
-    } else {
-        g = 0;
-        tp.j = (tp.lane << p.lognw) + (tp.t >> 6);
-        tp.base = 0;
-    }
-    const int beam = blockIdx.x * p.G + g;
-    tp.valid = (g < p.G) && (tp.j < p.S) && (beam < p.B);
-    tp.beam = tp.valid ? beam : 0;
-    if (!tp.valid) { tp.j = 0; tp.S = 1; tp.base = tp.t; tp.nwm1 = 0; g = p.G; }   // padding thread: an isolated dummy node
-    return tp;
-}
-
 // Per-thread constants: the slot table, the left neighbour's mask and, per DOF and gravity segment, the rotation sources
 // (phiA / phiB of that segment's table entry) of the gravity derivative.
 template <typename T>
@@ -135,12 +110,7 @@ __device__ __forceinline__ void static_load_const(const KParams<T>& p, const Top
             if (sb >= 0) { k.src[c][1][0] = st[sb].grav.phiA; k.src[c][1][1] = st[sb].grav.phiB; }
         }
     } else {
-        sc.elem.kind = KIND_NONE;
-        for (int q = 0; q < 6; ++q) sc.elem.c[q] = T(0);
-        sc.drag = sc.half_mass = T(0);
-        sc.mask[0] = sc.mask[1] = sc.mask[2] = T(0);
-        sc.grav.phiA = sc.grav.phiB = -1;
-        for (int c = 0; c < 3; ++c) { sc.grav.segA[c] = sc.grav.segB[c] = -1; sc.grav.comp[c] = 0; }
+        sc = padding_slot<T>();
     }
 }
 
@@ -255,7 +225,7 @@ template <typename T>
 __global__ void __launch_bounds__(STATIC_MAX_NT) crb_tangent_kernel(const KParams<T> p, const StaticParams<T> sp) {
     const StaticLds<T> L = carve_static_lds<T>(blockDim.x);
     int g;
-    const Topo tp = static_topo<T>(p, g);
+    const Topo tp = make_topo<T>(p, g);
     StaticConst<T> k;
     static_load_const<T>(p, tp, k);
     const size_t plane = size_t(p.n_node) * 4, node = size_t(tp.j + p.off);
@@ -355,7 +325,7 @@ __global__ void __launch_bounds__(STATIC_MAX_NT, 1) crb_static_kernel(const KPar
     const int NT = blockDim.x;
     const StaticLds<T> L = carve_static_lds<T>(NT);
     int g;
-    const Topo tp = static_topo<T>(p, g);
+    const Topo tp = make_topo<T>(p, g);
     const bool valid = tp.valid;
     StaticConst<T> k;
     static_load_const<T>(p, tp, k);

@@ -338,9 +338,7 @@ __global__ void __launch_bounds__(64 << LOGNW, implicit_lean_minw(LV, GRAV, LOGN
 #pragma unroll
             for (int k = 0; k < 5; ++k) cf.fin[k] = q.a_final[size_t(beam) * q.afin_stride + size_t(j) * PCR_FINAL_VALS + k];
         } else {
-            ec.kind = KIND_NONE;
-#pragma unroll
-            for (int k = 0; k < 6; ++k) ec.c[k] = T(0);
+            ec = padding_slot<T>().elem;
 #pragma unroll
             for (int l = 0; l < LV; ++l)
 #pragma unroll

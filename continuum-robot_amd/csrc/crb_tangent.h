@@ -17,7 +17,7 @@
 //   - the held-force tangent d f_held and the impulse tangent d amp (on the impulse's DOF, inside its time window);
 //   - constrained DOFs: zero in both parts (masked on load; their rows are zero in every multiplier of the solve).
 //
-// Mapping.  One thread per node slot (static_topo: beams of fewer than 64 slots packed G to a wave, longer ones one beam per
+// Mapping.  One thread per node slot (make_topo: beams of fewer than 64 slots packed G to a wave, longer ones one beam per
 // workgroup of up to 4 waves, 256 thread-carried nodes).  The direction index is the grid's second dimension: instance
 // (d, b) carries beam b's base state AND its tangent d -- every instance recomputes the base trajectory with identical
 // arithmetic, and only d == 0 writes it back (MODE_STEP reads the base from a copy made before the launch when n_dir > 1,
@@ -105,14 +105,7 @@ __device__ __forceinline__ void jvp_load_const(const KParams<T>& p, const Topo& 
 #pragma unroll
         for (int i = 0; i < 5; ++i) k.fin[i] = f[i];
     } else {   // padding thread: an isolated dummy node, all coefficients 0
-        sc.elem.kind = KIND_NONE;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) sc.elem.c[i] = T(0);
-        sc.drag = sc.half_mass = T(0);
-        sc.mask[0] = sc.mask[1] = sc.mask[2] = T(0);
-        sc.grav.phiA = sc.grav.phiB = -1;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { sc.grav.segA[c] = sc.grav.segB[c] = -1; sc.grav.comp[c] = 0; }
+        sc = padding_slot<T>();
 #pragma unroll
         for (int i = 0; i < 5; ++i) k.fin[i] = T(0);
     }
@@ -235,7 +228,7 @@ __global__ void __launch_bounds__(TANGENT_MAX_NT) crb_jvp_kernel(const KParams<T
     static_assert(MODE == MODE_RHS || MODE == MODE_STEP, "MODE_RHS or MODE_STEP");
     const TangentLds<T> L = carve_tangent_lds<T>(blockDim.x);
     int g;
-    const Topo tp = static_topo<T>(p, g);
+    const Topo tp = make_topo<T>(p, g);
     const bool valid = tp.valid;
     const size_t d = blockIdx.y;
 

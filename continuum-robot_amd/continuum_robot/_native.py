@@ -66,6 +66,12 @@ class InputTangent(C.Structure):
     _fields_ = [("d_amp", C.c_void_p), ("df_held", C.c_void_p)]
 
 
+class InputCotangent(C.Structure):
+    """crb_input_cotangent: accumulated cotangents of the impulse amplitude ([n_cot][B]) and of the held force
+    ([n_cot][B][n_node][4]), device pointers or None"""
+    _fields_ = [("amp_bar", C.c_void_p), ("f_held_bar", C.c_void_p)]
+
+
 class RecordDesc(C.Structure):
     _fields_ = [("plane", C.c_int32), ("node", C.c_int32), ("dof", C.c_int32), ("every", C.c_int32), ("out", C.c_void_p)]
 
@@ -153,6 +159,14 @@ def load():
     L.crb_rhs_jvp.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp]
     L.crb_step_rk4_tangent.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, i32, C.POINTER(InputDesc),
                                        C.POINTER(InputTangent), _dp, vp]
+    L.crb_rhs_vjp.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.crb_rk4_adjoint_work_bytes.restype = C.c_size_t
+    L.crb_rk4_adjoint_work_bytes.argtypes = [vp, i32]
+    L.crb_step_rk4_checkpoint.argtypes = [vp, vp, C.c_double, C.c_double, i32, i32, C.POINTER(InputDesc),
+                                          C.POINTER(RecordDesc), vp, _dp, vp]
+    L.crb_step_rk4_adjoint.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, i32, i32, C.POINTER(InputDesc),
+                                       C.POINTER(RecordDesc), C.POINTER(InputCotangent), vp, vp]
+    L.crb_plan_get_grav_transpose.argtypes = [vp, i32, vp, vp, vp]
     L.crb_step_rk4_feedback.argtypes = [vp, vp, C.c_double, C.c_double, i32, vp, vp, C.POINTER(InputDesc), vp,
                                         C.POINTER(C.c_double), vp]
     _lib = L

@@ -19,6 +19,7 @@ from typing import NamedTuple, Optional, Sequence, Union
 import numpy as np
 import pandas as pd
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _native as nat
 from .models.force_params import ForceParams
@@ -646,6 +647,138 @@ class BeamEnsemble:
         out = self._unpack_dirs(dxd)
         return out[0] if single else out
 
+    # ------------------------------------------------------------------ adjoint (reverse mode, crb_adjoint.h)
+    ADJOINT_WORK_BUDGET = 1 << 30   # bytes the default checkpoint interval keeps crb_step_rk4_adjoint's work buffer under
+
+    def _unpack_force_dirs(self, v: torch.Tensor) -> torch.Tensor:
+        """device layout [D, B, n_node, 4] -> reduced [D, B, n] (padding entries 0): the transposed gather of force-shaped
+        outputs"""
+        _, fidx = self._dir_index()
+        D = v.shape[0]
+        flat = torch.cat([v.reshape(D, -1), torch.zeros((D, 1), dtype=self.dtype, device=self.device)], dim=1)
+        return flat[:, fidx].reshape(D, self.n_beams, self.n)
+
+    def rhs_vjp(self, lam_red, x_red=None, u_red=None):
+        """Reverse-mode derivative of the RHS (crb_rhs_vjp): returns (xbar, ubar) = ((df/dx)^T lam, (df/du)^T lam) for the
+        reference's dynamic_system(t, x, u) (dynamic_beam_model.py:294-362), exact, in the shape of ``lam_red``: [B, 2n] ->
+        ([B, 2n], [B, n]), or D cotangents [D, B, 2n] -> ([D, B, 2n], [D, B, n]) in one launch.  ``x_red`` reduced [B, 2n]
+        (None: the resident state), ``u_red`` [B, n] held force (None = 0).  fp64 ensembles only."""
+        lam, single = self._dirs(lam_red, 2 * self.n, "rhs_vjp: lam_red")
+        D = lam.shape[0]
+        x = self.state if x_red is None else self.pack_state(x_red)
+        u = None if u_red is None else self.pack_vec(u_red)
+        lamd = self._pack_dirs(lam, True)
+        xbar = torch.empty_like(lamd)
+        ubar = torch.empty((D, self.n_beams, self.n_node, 4), dtype=self.dtype, device=self.device)
+        with self._on_device():
+            nat.check(self._lib.crb_rhs_vjp(self.plan.h, self._ptr(x), self._ptr(u), self._ptr(lamd), int(D), None,
+                                            self._ptr(xbar), self._ptr(ubar), self._stream()))
+        xb, ub = self._unpack_dirs(xbar), self._unpack_force_dirs(ubar)
+        return (xb[0], ub[0]) if single else (xb, ub)
+
+    def checkpoint_interval(self, n_steps: int, checkpoint_every: Optional[int] = None) -> int:
+        """Steps per checkpoint segment of an adjoint rollout: ``checkpoint_every``, or ceil(sqrt(n_steps)) lowered until the
+        work buffer of crb_step_rk4_adjoint (crb_rk4_adjoint_work_bytes) fits ADJOINT_WORK_BUDGET."""
+        if checkpoint_every is not None:
+            if int(checkpoint_every) < 1:
+                raise ValueError("checkpoint_every must be >= 1")
+            return int(checkpoint_every)
+        every = max(1, int(np.ceil(np.sqrt(max(int(n_steps), 1)))))
+        while every > 1 and self._lib.crb_rk4_adjoint_work_bytes(self.plan.h, every) > self.ADJOINT_WORK_BUDGET:
+            every -= 1
+        return every
+
+    def _checkpoint(self, x, n_steps, dt, t0, desc, every, rec):
+        """crb_step_rk4_checkpoint on the device state ``x`` (advanced in place): returns the checkpoint buffer"""
+        nseg = max(1, -(-int(n_steps) // every))
+        ckpt = torch.empty((nseg,) + tuple(self.state.shape), dtype=self.dtype, device=self.device)
+        t_end = C.c_double(0.0)
+        with self._on_device():
+            nat.check(self._lib.crb_step_rk4_checkpoint(self.plan.h, self._ptr(x), float(t0), float(dt), int(n_steps),
+                                                        int(every), C.byref(desc), C.byref(rec) if rec is not None else None,
+                                                        self._ptr(ckpt), C.byref(t_end), self._stream()))
+        return ckpt
+
+    def _adjoint(self, ckpt, lamd, n_steps, dt, t0, desc, every, rec_bar, want_amp):
+        """crb_step_rk4_adjoint: lamd [D, B, 2, n_node, 4] in place; returns (amp_bar [D, B] or None, f_bar [D, B, n_node, 4])"""
+        D = lamd.shape[0]
+        grad = nat.InputCotangent()
+        amp_bar = torch.zeros((D, self.n_beams), dtype=self.dtype, device=self.device) if want_amp else None
+        f_bar = torch.zeros((D, self.n_beams, self.n_node, 4), dtype=self.dtype, device=self.device)
+        grad.amp_bar = amp_bar.data_ptr() if amp_bar is not None else None
+        grad.f_held_bar = f_bar.data_ptr()
+        work = torch.empty((max(1, int(self._lib.crb_rk4_adjoint_work_bytes(self.plan.h, every))) + 7) // 8,
+                           dtype=torch.float64, device=self.device)
+        with self._on_device():
+            nat.check(self._lib.crb_step_rk4_adjoint(self.plan.h, self._ptr(ckpt), self._ptr(lamd), int(D), float(t0),
+                                                     float(dt), int(n_steps), int(every), C.byref(desc),
+                                                     C.byref(rec_bar) if rec_bar is not None else None, C.byref(grad),
+                                                     self._ptr(work), self._stream()))
+        self._keep = [work, ckpt, lamd, amp_bar, f_bar]
+        return amp_bar, f_bar
+
+    def _record_cotangent(self, record, n_steps, every, lam_record, D):
+        """crb_record_desc pointing at the cotangent of step()'s record samples, [D, ...] on the device (zeros if None)"""
+        rec, samples = self._record_desc(record, n_steps, every)
+        if rec is None:
+            return None, None
+        shape = (D,) + tuple(samples.shape)
+        if lam_record is None:
+            cot = torch.zeros(shape, dtype=self.dtype, device=self.device)
+        else:
+            cot = torch.as_tensor(lam_record, dtype=self.dtype, device=self.device)
+            if tuple(cot.shape) == tuple(samples.shape):
+                cot = cot.unsqueeze(0)
+            if tuple(cot.shape[1:]) != tuple(samples.shape) or cot.shape[0] not in (1, D):
+                raise ValueError(f"lam_record: expected shape {tuple(samples.shape)} or [D, ...] of it, got {tuple(cot.shape)}")
+            cot = cot.expand(shape).contiguous()
+        rec.out = cot.data_ptr()
+        return rec, cot
+
+    def step_adjoint(self, n_steps: int, dt: float, lam_red, x0_red=None, impulse_amp=None, impulse_duration: float = 0.01,
+                     impulse_index: int = -2, held_force=None, t0: Optional[float] = None, record=None,
+                     record_every: int = 1, lam_record=None, checkpoint_every: Optional[int] = None):
+        """Gradient of a scalar loss through an RK4 rollout of ``step()`` (crb_step_rk4_checkpoint + crb_step_rk4_adjoint), in
+        ONE backward sweep: for the cotangent ``lam_red`` = dL/dx(T) (reduced [B, 2n], or D cotangents [D, B, 2n]) and,
+        with ``record`` as in step(), ``lam_record`` = dL/d samples (the samples' shape, or [D, ...] of it), returns
+        (xbar0, amp_bar, f_held_bar) = (dL/dx(0) [B, 2n], dL/d impulse_amp [B] or None without an impulse,
+        dL/d held_force [B, n]), with a leading D axis when ``lam_red`` has one.  The rollout starts at ``x0_red`` (None: the
+        resident state) and clock ``t0`` (None: ``time``); ``state``, ``time`` and ``status`` are left alone.
+        ``checkpoint_every``: steps per checkpoint segment (checkpoint_interval); the result does not depend on it, bitwise.
+        The derivative is the exact transpose of the discrete RK4 map.  fp64 ensembles only."""
+        lam, single = self._dirs(lam_red, 2 * self.n, "step_adjoint: lam_red")
+        D = lam.shape[0]
+        t0 = self.time if t0 is None else float(t0)
+        every = self.checkpoint_interval(n_steps, checkpoint_every)
+        desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index, held_force)
+        x = self.state.clone() if x0_red is None else self.pack_state(x0_red)
+        ckpt = self._checkpoint(x, n_steps, dt, t0, desc, every, None)
+        rec_bar, cot = self._record_cotangent(record, n_steps, record_every, lam_record, D)
+        lamd = self._pack_dirs(lam, True)
+        amp_bar, f_bar = self._adjoint(ckpt, lamd, n_steps, dt, t0, desc, every, rec_bar, impulse_amp is not None)
+        self._keep += keep + [x, cot]
+        xb, fb = self._unpack_dirs(lamd), self._unpack_force_dirs(f_bar)
+        if single:
+            return xb[0], (amp_bar[0] if amp_bar is not None else None), fb[0]
+        return xb, amp_bar, fb
+
+    def rollout(self, x0_red, n_steps: int, dt: float, impulse_amp=None, held_force=None, impulse_duration: float = 0.01,
+                impulse_index: int = -2, t0: float = 0.0, record=None, record_every: int = 1,
+                checkpoint_every: Optional[int] = None):
+        """A differentiable RK4 rollout: x(T) reduced [B, 2n] from ``x0_red`` after ``n_steps`` steps of ``step()``'s map
+        (and the ``record`` samples as step() returns them), as a torch.autograd.Function whose backward is the adjoint
+        (crb_step_rk4_adjoint) -- ``loss.backward()`` reaches whichever of ``x0_red``, ``impulse_amp`` [B] and
+        ``held_force`` [B, n] require grad.  The forward is the checkpoint pass, whose checkpoints backward reuses.  Leaves
+        ``state`` and ``time`` alone.  fp64 ensembles only; once differentiable."""
+        x0 = torch.as_tensor(x0_red, dtype=self.dtype, device=self.device)
+        amp = None if impulse_amp is None else torch.as_tensor(impulse_amp, dtype=self.dtype, device=self.device)
+        held = None if held_force is None else torch.as_tensor(held_force, dtype=self.dtype, device=self.device)
+        opts = dict(n_steps=int(n_steps), dt=float(dt), t0=float(t0), duration=float(impulse_duration),
+                    index=int(impulse_index), record=record, record_every=int(record_every),
+                    every=self.checkpoint_interval(n_steps, checkpoint_every))
+        xT, samples = _Rollout.apply(self, opts, x0, amp, held)
+        return (xT, samples) if record is not None else xT
+
     def step_implicit(self, n_steps: int, h: float, n_iter: int = 2, impulse_amp=None, impulse_duration: float = 0.01,
                       impulse_index: int = -2, held_force=None, t0: Optional[float] = None, record=None,
                       record_every: int = 1, rho_inf: float = 1.0):
@@ -1189,3 +1322,41 @@ class BeamEnsemble:
         rows = torch.arange(self.n_beams, device=self.device)      # beams of different length: each beam's own last node
         nodes = torch.as_tensor(self.n_elem_per_beam, device=self.device)
         return self.state[rows, 0, nodes, 1].clone()
+
+
+class _Rollout(torch.autograd.Function):
+    """BeamEnsemble.rollout: forward = crb_step_rk4_checkpoint, backward = crb_step_rk4_adjoint on the saved checkpoints"""
+
+    @staticmethod
+    def forward(ctx, ens, opts, x0, amp, held):
+        desc, keep = ens._input_desc(None if amp is None else amp.detach(), opts["duration"], opts["index"],
+                                     None if held is None else held.detach())
+        x = ens.pack_state(x0.detach())
+        rec, samples = ens._record_desc(opts["record"], opts["n_steps"], opts["record_every"])
+        ckpt = ens._checkpoint(x, opts["n_steps"], opts["dt"], opts["t0"], desc, opts["every"], rec)
+        ens._keep = keep + [x, samples]
+        ctx.ens, ctx.opts = ens, opts
+        ctx.has_amp, ctx.has_held = amp is not None, held is not None
+        ctx.save_for_backward(ckpt, None if amp is None else amp.detach(), None if held is None else held.detach())
+        if samples is None:
+            samples = torch.zeros(0, dtype=ens.dtype, device=ens.device)
+        if opts["record"] is None:
+            ctx.mark_non_differentiable(samples)
+        return ens.unpack_state(x), samples
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_x, g_samples):
+        ens, o = ctx.ens, ctx.opts
+        ckpt, amp, held = ctx.saved_tensors
+        desc, keep = ens._input_desc(amp, o["duration"], o["index"], held)
+        g_x = torch.zeros((ens.n_beams, 2 * ens.n), dtype=ens.dtype, device=ens.device) if g_x is None else g_x
+        lamd = ens._pack_dirs(g_x.to(ens.dtype).reshape(1, ens.n_beams, 2 * ens.n).contiguous(), True)
+        rec_bar, cot = ens._record_cotangent(o["record"], o["n_steps"], o["record_every"],
+                                             g_samples if o["record"] is not None else None, 1)
+        amp_bar, f_bar = ens._adjoint(ckpt, lamd, o["n_steps"], o["dt"], o["t0"], desc, o["every"], rec_bar, ctx.has_amp)
+        ens._keep += keep + [cot]
+        gx0 = ens._unpack_dirs(lamd)[0] if ctx.needs_input_grad[2] else None
+        gamp = amp_bar[0] if (ctx.has_amp and ctx.needs_input_grad[3]) else None
+        gheld = ens._unpack_force_dirs(f_bar)[0] if (ctx.has_held and ctx.needs_input_grad[4]) else None
+        return None, None, gx0, gamp, gheld

@@ -18,6 +18,7 @@
 #include "crb_ctrl_launch.h"
 #include "crb_static_launch.h"
 #include "crb_tangent_launch.h"
+#include "crb_adjoint_launch.h"
 #include "crb_host.h"
 #include "crb_blocked.h"
 
@@ -102,6 +103,12 @@ struct crb_plan {
     mutable size_t gain_t_cap = 0;
     mutable void* d_rhs0 = nullptr;      // [B][2][n_node][4]: the RHS at the start of a crb_step_implicit_damped call (its a_0)
     mutable void* d_tan_x0 = nullptr;    // [B][2][n_node][4]: the base state at the start of a crb_step_rk4_tangent call (n_dir > 1)
+    // the adjoint kernels (crb_adjoint.h): the gravity index table of every distinct beam topology and which one each beam
+    // uses (empty: one table, topology 0), and their inverse lists on the device, built on first use
+    std::vector<std::vector<crb::GravTab>> h_grav_topo;
+    std::vector<int32_t> grav_topo_of;
+    mutable crb::GravAdj* d_gadj = nullptr;
+    mutable int32_t* d_gadj_beam = nullptr;
     // host-vector entry points (crb_rhs_host): full -> reduced map on the device, pinned staging, a stream of the plan's own
     mutable int32_t* d_red_map = nullptr;
     mutable double* h_stage = nullptr;   // pinned + mapped: [2n | n | 2n] doubles (x, u, out)
@@ -531,6 +538,8 @@ static int plan_create_impl(crb_plan** out, int device, int dtype, int n_beams, 
     std::vector<const BeamTopo*> topo(nd);
     for (int b = 0; b < nd; ++b) topo[b] = &topos[topo_of[b]];
     const BeamTopo& t0 = *topo[0];
+    for (const BeamTopo& t : topos) p->h_grav_topo.push_back(t.grav);
+    if (topos.size() > 1) p->grav_topo_of = topo_of;
     p->free_index = t0.free_index;
     p->full2red = t0.full2red;
     p->n_free = t0.n_free;
@@ -734,6 +743,8 @@ extern "C" void crb_plan_destroy(crb_plan* p) {
         (void)hipFree(p->d_gain_t);
         (void)hipFree(p->d_rhs0);
         (void)hipFree(p->d_tan_x0);
+        (void)hipFree(p->d_gadj);
+        (void)hipFree(p->d_gadj_beam);
         (void)hipFree(p->d_red_map);
         if (p->h_stage) (void)hipHostFree(p->h_stage);
         if (p->host_stream) (void)hipStreamDestroy(p->host_stream);
@@ -2381,5 +2392,227 @@ extern "C" int crb_step_rk4_tangent(const crb_plan* p, void* x, void* dx, int n_
         q.d_amp = static_cast<const double*>(din->d_amp);
     }
     HIP_TRY(crb::launch_jvp_step(k, q, (p->B + p->G - 1) / p->G, n_dir, p->NT, st));
+    return CRB_OK;
+}
+
+// ------------------------------------------------------------------ adjoint RHS and rollout (crb_adjoint.h)
+namespace {
+// The inverse lists of one gravity index table (crb_adjoint.h GravAdj): every forward edge once, in ascending order of the
+// slot that reads it.  *seg_fanin / *phi_fanin: the largest fan-in found; false when one exceeds the kernels' lists.
+bool grav_transpose(const std::vector<GravTab>& g, std::vector<GravAdj>& out, int* seg_fanin, int* phi_fanin) {
+    const int S = int(g.size());
+    GravAdj none;
+    for (int m = 0; m < 2; ++m)
+        for (int i = 0; i < GRAV_SEG_FANIN; ++i) none.seg[m][i] = -1;
+    for (int c = 0; c < 3; ++c)
+        for (int i = 0; i < GRAV_PHI_FANIN; ++i) none.phi[c][i] = -1;
+    out.assign(size_t(S), none);
+    std::vector<int> ns(size_t(S) * 2, 0), np(size_t(S) * 3, 0);
+    int ms = 0, mp = 0;
+    for (int j = 0; j < S; ++j)   // node DOF (j, c) sums component comp[c] of segments segA[c], segB[c]
+        for (int c = 0; c < 3; ++c) {
+            const int segs[2] = {g[j].segA[c], g[j].segB[c]};
+            for (int e = 0; e < 2; ++e) {
+                const int sg = segs[e];
+                if (sg < 0 || sg >= S) continue;
+                const int m = g[j].comp[c] & 1;
+                const int k = ns[size_t(sg) * 2 + m]++;
+                ms = k + 1 > ms ? k + 1 : ms;
+                if (k < GRAV_SEG_FANIN) out[sg].seg[m][k] = j * 4 + c;
+            }
+        }
+    for (int sg = 0; sg < S; ++sg) {   // segment sg reads rotation phiA (weight 1, or 0.5 next to phiB) and phiB (0.5)
+        const int ia = g[sg].phiA, ib = g[sg].phiB;
+        const int idx[2] = {ia, ib};
+        for (int e = 0; e < 2; ++e) {
+            const int f = idx[e];
+            if (f < 0 || (f >> 2) >= S || (f & 3) > 2) continue;
+            const int j = f >> 2, c = f & 3;
+            const int k = np[size_t(j) * 3 + c]++;
+            mp = k + 1 > mp ? k + 1 : mp;
+            if (k < GRAV_PHI_FANIN) out[j].phi[c][k] = (sg << 1) | (ib >= 0 ? 1 : 0);
+        }
+    }
+    // (ascending order of the reading slot per list: the segment loop above visits segments in order)
+    if (seg_fanin) *seg_fanin = ms;
+    if (phi_fanin) *phi_fanin = mp;
+    return ms <= GRAV_SEG_FANIN && mp <= GRAV_PHI_FANIN;
+}
+
+// the plan and size checks of every adjoint entry point, before the device is touched (so that they hold for host-only plans
+// too; a valid call on a host-only plan then fails with CRB_ENODEV)
+int adjoint_checks(const crb_plan* p, int n_cot, const char* who) {
+    if (!p) return fail(CRB_EINVAL, std::string(who) + ": null plan");
+    if (p->dtype != CRB_F64) return fail(CRB_EUNSUPPORTED, std::string(who) + ": the adjoint kernels need an fp64 plan");
+    if (p->NT > ADJ_MAX_NT)
+        return fail(CRB_EUNSUPPORTED, std::string(who) + ": beams of more than 256 thread-carried nodes are not supported");
+    if (n_cot < 1 || n_cot > 65535) return fail(CRB_EINVAL, std::string(who) + ": n_cot must be in [1, 65535]");
+    return CRB_OK;
+}
+
+// the inverse gravity lists on the device (built and uploaded on first use; gravity-free plans need none)
+int ensure_gadj(const crb_plan* p, const char* who) {
+    if (!(p->flags & CRB_FORCE_GRAVITY) || p->d_gadj) return CRB_OK;
+    const size_t S = size_t(p->S), nt = p->h_grav_topo.size();
+    std::vector<GravAdj> all(nt * S), one;
+    for (size_t t = 0; t < nt; ++t) {
+        int ms = 0, mp = 0;
+        if (!grav_transpose(p->h_grav_topo[t], one, &ms, &mp))
+            return fail(CRB_EUNSUPPORTED, std::string(who) + ": the gravity index table has a fan-in of " + std::to_string(ms) +
+                                              " / " + std::to_string(mp) + ", beyond the adjoint's lists");
+        std::memcpy(&all[t * S], one.data(), S * sizeof(GravAdj));
+    }
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p->d_gadj), all.size() * sizeof(GravAdj)));
+    HIP_TRY(hipMemcpy(p->d_gadj, all.data(), all.size() * sizeof(GravAdj), hipMemcpyHostToDevice));
+    if (!p->grav_topo_of.empty()) {
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p->d_gadj_beam), p->grav_topo_of.size() * sizeof(int32_t)));
+        HIP_TRY(hipMemcpy(p->d_gadj_beam, p->grav_topo_of.data(), p->grav_topo_of.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    return CRB_OK;
+}
+
+AdjParams<double> adj_params(const crb_plan* p) {
+    AdjParams<double> q;
+    std::memset(&q, 0, sizeof(q));
+    q.gadj = p->d_gadj;
+    q.gadj_beam = p->d_gadj_beam;
+    q.store_every = 1;
+    return q;
+}
+size_t state_doubles(const crb_plan* p) { return size_t(p->B) * 2 * size_t(p->n_node) * 4; }
+}  // namespace
+
+extern "C" int crb_plan_get_grav_transpose(const crb_plan* p, int beam, int32_t* seg, int32_t* phi, int32_t* fanin) {
+    if (!p) return fail(CRB_EINVAL, "crb_plan_get_grav_transpose: null plan");
+    if (beam < 0 || beam >= p->B) return fail(CRB_EINVAL, "crb_plan_get_grav_transpose: beam out of range");
+    const size_t t = p->grav_topo_of.empty() ? 0 : size_t(p->grav_topo_of[size_t(beam)]);
+    std::vector<GravAdj> lists;
+    int ms = 0, mp = 0;
+    const bool ok = grav_transpose(p->h_grav_topo[t], lists, &ms, &mp);
+    if (fanin) { fanin[0] = ms; fanin[1] = mp; }
+    for (int j = 0; j < p->S; ++j) {
+        if (seg)
+            for (int m = 0; m < 2; ++m)
+                for (int i = 0; i < GRAV_SEG_FANIN; ++i) seg[(size_t(j) * 2 + m) * GRAV_SEG_FANIN + i] = lists[j].seg[m][i];
+        if (phi)
+            for (int c = 0; c < 3; ++c)
+                for (int i = 0; i < GRAV_PHI_FANIN; ++i) phi[(size_t(j) * 3 + c) * GRAV_PHI_FANIN + i] = lists[j].phi[c][i];
+    }
+    return ok ? CRB_OK : fail(CRB_EUNSUPPORTED, "crb_plan_get_grav_transpose: fan-in beyond the adjoint's lists");
+}
+
+extern "C" int crb_rhs_vjp(const crb_plan* p, const void* x, const void* u, const void* lam, int n_cot, void* xdot, void* xbar,
+                           void* ubar, void* stream) {
+    if (int rc = adjoint_checks(p, n_cot, "crb_rhs_vjp")) return rc;
+    if (!x || !lam || !xbar) return fail(CRB_EINVAL, "crb_rhs_vjp: null pointer");
+    if (xbar == x || xbar == lam || xbar == u || (xdot && (xdot == x || xdot == lam || xdot == xbar)) ||
+        (ubar && (ubar == x || ubar == lam || ubar == u || ubar == xbar)))
+        return fail(CRB_EINVAL, "crb_rhs_vjp: outputs must not alias inputs or each other");
+    if (int rc = need_device(p, "crb_rhs_vjp")) return rc;
+    if (int rc = ensure_gadj(p, "crb_rhs_vjp")) return rc;
+    KParams<double> k = base_params<double>(p);
+    k.x = static_cast<double*>(const_cast<void*>(x));
+    k.u_held = static_cast<const double*>(u);
+    k.out = static_cast<double*>(xdot);
+    AdjParams<double> q = adj_params(p);
+    q.lam_in = static_cast<const double*>(lam);
+    q.xbar = static_cast<double*>(xbar);
+    q.ubar = static_cast<double*>(ubar);
+    HIP_TRY(crb::launch_adj_rhs(k, q, (p->B + p->G - 1) / p->G, n_cot, p->NT, static_cast<hipStream_t>(stream)));
+    return CRB_OK;
+}
+
+extern "C" size_t crb_rk4_adjoint_work_bytes(const crb_plan* p, int every) {
+    if (!p || every < 1) return 0;
+    return size_t(every) * (4 * state_doubles(p) + 1) * sizeof(double);
+}
+
+extern "C" int crb_step_rk4_checkpoint(const crb_plan* p, void* x, double t0, double dt, int n_steps, int every,
+                                       const crb_input_desc* in, const crb_record_desc* rec, void* ckpt, double* t_end,
+                                       void* stream) {
+    if (int rc = adjoint_checks(p, 1, "crb_step_rk4_checkpoint")) return rc;
+    if (!x || !ckpt) return fail(CRB_EINVAL, "crb_step_rk4_checkpoint: null state or checkpoint buffer");
+    if (x == ckpt) return fail(CRB_EINVAL, "crb_step_rk4_checkpoint: the checkpoint buffer must not alias the state");
+    if (n_steps < 0) return fail(CRB_EINVAL, "crb_step_rk4_checkpoint: n_steps must be >= 0");
+    if (every < 1) return fail(CRB_EINVAL, "crb_step_rk4_checkpoint: every must be >= 1");
+    if (!(dt > 0)) return fail(CRB_EINVAL, "crb_step_rk4_checkpoint: dt must be positive");
+    if (int rc = need_device(p, "crb_step_rk4_checkpoint")) return rc;
+    Recording r;
+    if (int rc = decode_record(p, rec, n_steps, true, "crb_step_rk4_checkpoint", &r)) return rc;
+    Forcing f;
+    if (int rc = decode_input(p, in, "crb_step_rk4_checkpoint", &f)) return rc;
+    if (t_end) *t_end = clock_after(t0, dt, n_steps);
+    if (n_steps == 0) return CRB_OK;
+    if (int rc = ensure_gadj(p, "crb_step_rk4_checkpoint")) return rc;
+    KParams<double> k = base_params<double>(p);
+    k.x = static_cast<double*>(x);
+    set_io(k, f, &r);
+    k.t0 = t0; k.dt = dt; k.n_steps = n_steps;
+    AdjParams<double> q = adj_params(p);
+    q.states = static_cast<double*>(ckpt);
+    q.store_every = every;
+    q.write_back = 1;
+    HIP_TRY(crb::launch_adj_forward(k, q, (p->B + p->G - 1) / p->G, p->NT, static_cast<hipStream_t>(stream)));
+    return CRB_OK;
+}
+
+extern "C" int crb_step_rk4_adjoint(const crb_plan* p, const void* ckpt, void* lam, int n_cot, double t0, double dt, int n_steps,
+                                    int every, const crb_input_desc* in, const crb_record_desc* rec_bar,
+                                    const crb_input_cotangent* grad, void* work, void* stream) {
+    if (int rc = adjoint_checks(p, n_cot, "crb_step_rk4_adjoint")) return rc;
+    if (!ckpt || !lam) return fail(CRB_EINVAL, "crb_step_rk4_adjoint: null checkpoint buffer or cotangent");
+    if (!work) return fail(CRB_EINVAL, "crb_step_rk4_adjoint: null work buffer (crb_rk4_adjoint_work_bytes)");
+    if (n_steps < 0) return fail(CRB_EINVAL, "crb_step_rk4_adjoint: n_steps must be >= 0");
+    if (every < 1) return fail(CRB_EINVAL, "crb_step_rk4_adjoint: every must be >= 1");
+    if (!(dt > 0)) return fail(CRB_EINVAL, "crb_step_rk4_adjoint: dt must be positive");
+    if (lam == ckpt || lam == work) return fail(CRB_EINVAL, "crb_step_rk4_adjoint: lam must not alias another buffer of the call");
+    if (int rc = need_device(p, "crb_step_rk4_adjoint")) return rc;
+    Recording r;
+    if (int rc = decode_record(p, rec_bar, n_steps, true, "crb_step_rk4_adjoint", &r)) return rc;
+    Forcing f;
+    if (int rc = decode_input(p, in, "crb_step_rk4_adjoint", &f)) return rc;
+    void* amp_bar = grad ? grad->amp_bar : nullptr;
+    void* f_bar = grad ? grad->f_held_bar : nullptr;
+    if (amp_bar && !f.impulse)
+        return fail(CRB_EINVAL, "crb_step_rk4_adjoint: amp_bar needs an impulse input (its amplitude is what it differentiates)");
+    const void* bufs[6] = {ckpt, work, amp_bar, f_bar, r.out, f.held};
+    for (const void* b : bufs)
+        if (b && b == lam) return fail(CRB_EINVAL, "crb_step_rk4_adjoint: lam must not alias another buffer of the call");
+    if ((amp_bar && (amp_bar == work || amp_bar == ckpt || amp_bar == f_bar)) || (f_bar && (f_bar == work || f_bar == ckpt)) ||
+        work == ckpt)
+        return fail(CRB_EINVAL, "crb_step_rk4_adjoint: the output and work buffers must not alias each other or the checkpoints");
+    if (n_steps == 0) return CRB_OK;
+    if (int rc = ensure_gadj(p, "crb_step_rk4_adjoint")) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int groups = (p->B + p->G - 1) / p->G;
+    const size_t sd = state_doubles(p);
+    double* const wstates = static_cast<double*>(work);
+    double* const wclock = wstates + size_t(every) * 4 * sd;
+    const int nseg = (n_steps + every - 1) / every;
+    for (int g = nseg - 1; g >= 0; --g) {
+        const int k0 = g * every, n = (n_steps - k0) < every ? (n_steps - k0) : every;
+        const double tg = clock_after(t0, dt, k0);   // (the checkpoint pass's clock at the segment start: the same additions)
+        KParams<double> k = base_params<double>(p);
+        set_io(k, f);
+        k.dt = dt; k.t0 = tg; k.n_steps = n;
+        // 1. the segment's stage points from its checkpoint
+        k.x = const_cast<double*>(static_cast<const double*>(ckpt)) + size_t(g) * sd;
+        AdjParams<double> q = adj_params(p);
+        q.states = wstates;
+        q.clocks = wclock;
+        q.stage_pts = 1;
+        HIP_TRY(crb::launch_adj_forward(k, q, groups, p->NT, st));
+        // 2. the sweep back over it, every cotangent
+        k.x = nullptr;
+        k.rec_out = static_cast<double*>(r.out); k.rec_slot = r.slot; k.rec_comp = r.comp; k.rec_every = r.every; k.rec_n = r.count;
+        AdjParams<double> b = adj_params(p);
+        b.work = wstates;
+        b.work_clock = wclock;
+        b.lam = static_cast<double*>(lam);
+        b.amp_bar = static_cast<double*>(amp_bar);
+        b.f_bar = static_cast<double*>(f_bar);
+        b.step0 = k0;
+        HIP_TRY(crb::launch_adj_backward(k, b, groups, n_cot, p->NT, st));
+    }
     return CRB_OK;
 }

@@ -242,6 +242,61 @@ int crb_rhs_jvp(const crb_plan* plan, const void* x, const void* u, const void* 
 int crb_step_rk4_tangent(const crb_plan* plan, void* x, void* dx, int n_dir, double t0, double dt, int n_steps,
                          const crb_input_desc* input, const crb_input_tangent* dinput, double* t_end, void* stream);
 
+/* Reverse-mode derivative (vector-Jacobian products) of the RHS: the transpose of crb_rhs_jvp's derivative of
+ * get_dynamic_system()(t, x, u) (dynamic_beam_model.py:294-362), exact (the element Jacobian on dual numbers, drag, gravity
+ * through inverse lists of the plan's index table, and the exact transpose of the plan's truncated cyclic-reduction solve).
+ * For n_cot cotangents lam[c] of xdot:  xbar[c] = (df/dx)^T lam[c],  ubar[c] = (df/du)^T lam[c];  xdot = f(x, u) when not NULL.
+ * x: [B][2][n_node][4]; u: [B][n_node][4] or NULL; lam, xbar: [n_cot][B][2][n_node][4]; ubar: [n_cot][B][n_node][4] or NULL.
+ * Constrained DOFs (and node 0 of plans without its slot) are zero in xbar and ubar.  Outputs must not alias inputs or each
+ * other.  fp64 plans only (CRB_EUNSUPPORTED), beams of up to 256 thread-carried nodes, 1 <= n_cot <= 65535. */
+int crb_rhs_vjp(const crb_plan* plan, const void* x, const void* u, const void* lam, int n_cot, void* xdot, void* xbar,
+                void* ubar, void* stream);
+
+/* Cotangents of the inputs of a rollout, ACCUMULATED by crb_step_rk4_adjoint (device, fp64; NULL = not wanted). */
+typedef struct crb_input_cotangent {
+    void* amp_bar;     /* device [n_cot][B]: dL/d amp of the impulse (needs an impulse input) */
+    void* f_held_bar;  /* device [n_cot][B][n_node][4]: dL/d f_held */
+} crb_input_cotangent;
+
+/* Device bytes of the work buffer of crb_step_rk4_adjoint for checkpoints every `every` steps:
+ * every * (4 * B * 2 * n_node * 4 + 1) * sizeof(double) -- the four RK4 stage points of each step of one segment, then the
+ * steps' clocks.  0 for every < 1. */
+size_t crb_rk4_adjoint_work_bytes(const crb_plan* plan, int every);
+
+/* The forward pass of a differentiable rollout: crb_step_rk4 (same clock, same input; x advances in place, *t_end as there) in
+ * the adjoint's own arithmetic, writing the state at the start of steps 0, every, 2 every, ... to
+ * ckpt [ceil(n_steps / every)][B][2][n_node][4] (device).  rec: as crb_step_rk4_rec (may be NULL), so that a loss over the
+ * recorded trajectory (the t_eval samples of example_utilities.py:153-159, 173-205) can be differentiated.  x agrees with
+ * crb_step_rk4 to rounding, not bitwise.  fp64 plans only, beams of up to 256 thread-carried nodes. */
+int crb_step_rk4_checkpoint(const crb_plan* plan, void* x, double t0, double dt, int n_steps, int every,
+                            const crb_input_desc* input, const crb_record_desc* rec, void* ckpt, double* t_end, void* stream);
+
+/* Adjoint (reverse-mode) of the RK4 rollout crb_step_rk4_checkpoint ran from t0 (the same dt, n_steps, every and input):
+ * the gradient of a scalar loss L(x(T), samples) with respect to x(0) and the inputs in ONE backward sweep, for n_cot
+ * cotangents per beam -- what central differences of the scipy.solve_ivp call sites (example_utilities.py:153-159,
+ * lqr_control.py:117-125) or one crb_step_rk4_tangent direction per input would otherwise give.
+ *   lam      device [n_cot][B][2][n_node][4], in place: dL/dx(T) on entry, dL/dx(0) on exit
+ *   rec_bar  the record of the forward pass with out = its cotangent dL/d samples: [n_cot][B][n_rec] for one DOF,
+ *            [n_cot][n_rec][B][2][n_node][4] for CRB_RECORD_ALL; NULL when the loss reads no samples
+ *   grad     amp_bar / f_held_bar += dL/d amp, dL/d f_held (may be NULL)
+ *   work     crb_rk4_adjoint_work_bytes(plan, every) device bytes
+ * Per segment of `every` steps, last to first: one launch recomputes its RK4 stage points from the checkpoint, one sweeps it
+ * back for all cotangents.  The result is the exact transpose of the discrete map (the derivative crb_step_rk4_tangent
+ * propagates forward), bitwise independent of `every`, and D cotangents in one call are bitwise D calls of one.  lam must
+ * not alias any other buffer; the outputs and work must not alias each other or ckpt.  fp64 plans only
+ * (CRB_EUNSUPPORTED), beams of up to 256 thread-carried nodes, 1 <= n_cot <= 65535; host-only plans CRB_ENODEV. */
+int crb_step_rk4_adjoint(const crb_plan* plan, const void* ckpt, void* lam, int n_cot, double t0, double dt, int n_steps,
+                         int every, const crb_input_desc* input, const crb_record_desc* rec_bar,
+                         const crb_input_cotangent* grad, void* work, void* stream);
+
+/* Inverse lists of the gravity index table of beam `beam` (crb_plan_get_slot_tables' grav, reversed), host-only plans too:
+ *   seg [n_slots][2][2]: per segment and force component (0 axial / 1 transverse), slot*4+dof of the node DOFs it adds to
+ *   phi [n_slots][3][2]: per DOF of a slot, (segment << 1) | half of the segments whose rotation reads it (half: the segment
+ *                        averages two rotations, weight 0.5)
+ *   -1 = no entry; fanin[2] = the largest fan-in of each list kind.  Any pointer may be NULL.  CRB_EUNSUPPORTED when a
+ *   fan-in exceeds the lists (the adjoint kernels refuse such plans). */
+int crb_plan_get_grav_transpose(const crb_plan* plan, int beam, int32_t* seg, int32_t* phi, int32_t* fanin);
+
 /* n_steps classical RK4 steps of size dt, in place, in ONE launch (replaces the
  * scipy.solve_ivp call sites example_utilities.py:153-159, lqr_control.py:117-125).  The clock
  * starts at t0 and accumulates by addition (t <- t + dt); stage times t, t+dt/2, t+dt.

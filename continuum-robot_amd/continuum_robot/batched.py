@@ -616,8 +616,7 @@ class BeamEnsemble:
         that of the discrete RK4 map itself, exact.  fp64 ensembles only."""
         dx, single = self._dirs(dx0_red, 2 * self.n, "step_tangent: dx0_red")
         D = dx.shape[0]
-        if t0 is not None:
-            self.time = float(t0)
+        t_start = self.time if t0 is None else float(t0)   # (``time`` moves only when the launch is accepted)
         if d_impulse_amp is not None and impulse_amp is None:
             impulse_amp = torch.zeros((self.n_beams,), dtype=self.dtype, device=self.device)
         desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index, held_force)
@@ -639,7 +638,7 @@ class BeamEnsemble:
             keep.append(dhd)
         t_end = C.c_double(0.0)
         with self._on_device():
-            nat.check(self._lib.crb_step_rk4_tangent(self.plan.h, self._ptr(self.state), self._ptr(dxd), int(D), self.time,
+            nat.check(self._lib.crb_step_rk4_tangent(self.plan.h, self._ptr(self.state), self._ptr(dxd), int(D), t_start,
                                                      float(dt), int(n_steps), C.byref(desc), C.byref(tan), C.byref(t_end),
                                                      self._stream()))
         self._keep = keep + [dxd]

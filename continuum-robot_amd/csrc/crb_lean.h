@@ -209,18 +209,29 @@ __device__ __forceinline__ void lean_rhs(const ElemCoef<T>& ec, T dragc, bool co
 // crb_step_lean_kernel<double, LS, 2, false, EM, false, false, false, 4>: fp64 beams of exactly 256 slots with one table set
 // and one element kind whose mass matrix is uniform (crbeam.hip: blocked_step_ok).  One WAVE per beam, lane l owning slots
 // 4l .. 4l+3: the mass solve and the exchanges scale with the lane boundaries, not with the nodes (crb_blocked.h):
-//   exchanges per stage, all DPP lane shifts: q of lane-1's last node (the next stage's rides on this one), the left half of
-//   the lane's first element back to lane-1, y_0 of lane+1, LS separator levels at lane strides 1, 2, 4, x_s of lane-1;
-//   no LDS round and no barrier in the step loop.  A workgroup is four independent beam walkers.
+//   exchanges per stage: q of lane-1's last node (the next stage's rides on this one), the left half of the lane's first element
+//   back to lane-1, y_0 of lane+1, the separator levels at lane strides 1 and 2 and x_s of lane-1 by DPP lane shifts; the third
+//   separator level (stride 4) through the wave's own LDS strip [3][4 + 64 + 4] (3 ds_write_b64 + 6 ds_read_b64 at immediate
+//   offsets instead of 24 DPP moves; the pads, zeroed once, are the 0 that a bound_ctrl shift brings in past the root and the
+//   tip, so the results are bitwise those of the shifts).  No barrier in the step loop: a wave's LDS accesses execute in order.
+//   A workgroup is four independent beam walkers.
 // Wave-uniform constants (the interior's factors, W_L / W_R, A_s / C_s, the element pack, the drag factor) are read by scalar
 // loads through a pointer laundered per stage, so that they are not held across the loop; the per-lane separator tables sit
 // in LDS (shared by the four waves, [value pair][lane] records) and are read level by level.  LS = separator levels.
 // Measured at 4096 x 256: 549 vector instructions per beam and stage against 868 (4 waves x 217), 16.3 against
-// 27.1 us per step; 235 VGPRs, no scratch, two waves per SIMD.  The next beam's state is not prefetched as in the one-node-per-lane
+// 27.1 us per step with every level by DPP; the strip takes that to 501 and 16.53 to 16.15 us per step (strides 2 and 4 through
+// the strip: 477 and 16.17); 236 VGPRs, no scratch, two waves per SIMD.  The next beam's state is not prefetched as in the one-node-per-lane
 // form: four nodes' records are 48 more registers than the budget of two waves per SIMD holds.
+constexpr int BLK_STRIP_PAD = 4;   // the stride of the separator level that goes through the wave's LDS strip (the third)
+constexpr int BLK_STRIP_W = BLK_STRIP_PAD + BLK_LANES + BLK_STRIP_PAD;
+// dynamic LDS of the blocked stepper: the separator tables (value pairs per lane), then per wave a strip [3][W] of fp64
+__host__ __device__ constexpr size_t blk_lds_bytes(int ls) {
+    return size_t(blk_sep_vals(ls) + 1) / 2 * 2 * BLK_LANES * sizeof(double) + size_t(4) * 3 * BLK_STRIP_W * sizeof(double);
+}
 template <typename T, int LS, int EM, typename KPT>
 __device__ __forceinline__ void lean_blocked_body(KPT kp) {
     static_assert(sizeof(T) == 8, "the blocked stepper is fp64");
+    static_assert(LS == 3 && (1 << (LS - 1)) == BLK_STRIP_PAD, "the strip carries the third separator level, stride 4");
     constexpr int NP = BLK_NPL, NV = blk_sep_vals(LS), NV2 = (NV + 1) / 2;
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef const __attribute__((address_space(4))) T* CP;
@@ -236,6 +247,7 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
     KParams<T> p = *(const KParams<T>*)(kp);
     extern __shared__ __attribute__((aligned(16))) unsigned char crb_smem[];
     pair2* const sepL = reinterpret_cast<pair2*>(crb_smem);   // [NV2][64]
+    T* const strips = reinterpret_cast<T*>(sepL + NV2 * 64);    // [4 waves][3][BLK_STRIP_W]
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);   // (wave-uniform to the compiler: the walk below is scalar)
     {   // the separator tables, [value][lane] in the plan, value pairs per lane here
@@ -244,7 +256,20 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
             const int v = 2 * (i >> 6), l = i & 63;
             sepL[i] = pair2{src[size_t(v) * 64 + l], v + 1 < NV ? src[size_t(v + 1) * 64 + l] : T(0)};
         }
+        // the strips' pads: a neighbour past either end of the beam reads 0, as a DPP shift with bound_ctrl does
+        for (int i = t; i < 4 * 3 * BLK_STRIP_W; i += 256) {
+            const int k = i % BLK_STRIP_W;
+            if (k < BLK_STRIP_PAD || k >= BLK_STRIP_PAD + BLK_LANES) strips[i] = T(0);
+        }
     }
+    // this wave's strip at its lane's column (volatile: the compiler sees a level's reads as other addresses than this lane's
+    // store and would hoist them; a wave's LDS accesses execute in order, so the order is all that is needed -- no wait)
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef volatile __attribute__((address_space(3))) T* SP;   // (spelled out: a volatile access keeps a generic pointer flat)
+#else
+    typedef volatile T* SP;
+#endif
+    const SP strip = (SP)(strips + wave * 3 * BLK_STRIP_W + BLK_STRIP_PAD + lane);
     __syncthreads();   // (the only barrier: the waves walk over their beams independently from here on)
     const int n_groups = (p.B + 3) / 4;
     for (int grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
@@ -371,16 +396,17 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                         cf[i] = e[0]; cf[i + 1] = e[1];
                     }
                     T glo[3], ghi[3];
+                    if (l == 2) {   // stride 4 through the strip: 3 stores, 6 loads at immediate offsets
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        switch (l) {
-                            case 0: glo[c] = lane_lower<T, 1>(g[c], lane); ghi[c] = lane_higher<T, 1>(g[c], lane); break;
-                            case 1: glo[c] = lane_lower<T, 2>(g[c], lane); ghi[c] = lane_higher<T, 2>(g[c], lane); break;
-                            case 2: glo[c] = lane_lower<T, 4>(g[c], lane); ghi[c] = lane_higher<T, 4>(g[c], lane); break;
-                            case 3: glo[c] = lane_lower<T, 8>(g[c], lane); ghi[c] = lane_higher<T, 8>(g[c], lane); break;
-                            case 4: glo[c] = lane_lower<T, 16>(g[c], lane); ghi[c] = lane_higher<T, 16>(g[c], lane); break;
-                            default: glo[c] = lane_lower<T, 32>(g[c], lane); ghi[c] = lane_higher<T, 32>(g[c], lane); break;
-                        }
+                        for (int c = 0; c < 3; ++c) strip[c * BLK_STRIP_W] = g[c];
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) { glo[c] = strip[c * BLK_STRIP_W - 4]; ghi[c] = strip[c * BLK_STRIP_W + 4]; }
+                    } else if (l == 1) {
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) { glo[c] = lane_lower<T, 2>(g[c], lane); ghi[c] = lane_higher<T, 2>(g[c], lane); }
+                    } else {
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) { glo[c] = lane_lower<T, 1>(g[c], lane); ghi[c] = lane_higher<T, 1>(g[c], lane); }
                     }
                     pcr_apply_level<T>(cf, glo, ghi, g);
                 }

@@ -183,7 +183,7 @@ template <int LS, int EM>
 hipError_t one_blocked(const KParams<T>& k, int n_beams, hipStream_t st) {
     // NPL = 4: a wave is a beam, a workgroup four of them; shared-table plans only, so the workgroups walk over groups of beams
     auto kernel = crb_step_lean_kernel<T, LS, 2, false, EM, false, false, false, BLK_NPL>;
-    const size_t smem = size_t(blk_sep_vals(LS) + 1) / 2 * 2 * BLK_LANES * sizeof(double);   // the separator tables
+    const size_t smem = blk_lds_bytes(LS);   // the separator tables and the waves' strips
     const int groups = (n_beams + 3) / 4;
     static int resident = -1;   // (per instantiation)
     int grid = groups;
@@ -203,8 +203,6 @@ hipError_t launch_lean_blocked(const KParams<T>& k, int n_beams, int levels, int
 #else
         if (levels == 3) return elem_mode == EM_NONLINEAR ? one_blocked<3, EM_NONLINEAR>(k, n_beams, st)
                               : elem_mode == EM_LINEAR ? one_blocked<3, EM_LINEAR>(k, n_beams, st) : hipErrorInvalidValue;
-        if (levels == 4) return elem_mode == EM_NONLINEAR ? one_blocked<4, EM_NONLINEAR>(k, n_beams, st)
-                              : elem_mode == EM_LINEAR ? one_blocked<4, EM_LINEAR>(k, n_beams, st) : hipErrorInvalidValue;
 #endif
     }
     (void)k; (void)n_beams; (void)levels; (void)elem_mode; (void)st;

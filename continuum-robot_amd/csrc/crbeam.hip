@@ -1025,7 +1025,7 @@ bool lean_step_ok(const crb_plan* p) {
 // CRB_DISABLE_BLOCKED=1: the one-node-per-lane stepper.
 bool blocked_step_ok(const crb_plan* p, const void* held) {
     return p->d_blocked && lean_step_ok(p) && !grav_on(p) && !held && p->G == 1 &&
-           (p->elem_mode == EM_NONLINEAR || p->elem_mode == EM_LINEAR) && (p->blocked_levels == 3 || p->blocked_levels == 4) &&
+           (p->elem_mode == EM_NONLINEAR || p->elem_mode == EM_LINEAR) && p->blocked_levels == 3 &&
            !env_set("CRB_DISABLE_BLOCKED");
 }
 // crb_rk4_stage: the lean stepper's shapes less the packed one (the stage kernel walks over whole beams)

@@ -220,7 +220,10 @@ __device__ __forceinline__ void lean_rhs(const ElemCoef<T>& ec, T dragc, bool co
 // in LDS (shared by the four waves, [value pair][lane] records) and are read level by level.  LS = separator levels.
 // Measured at 4096 x 256: 549 vector instructions per beam and stage against 868 (4 waves x 217), 16.3 against
 // 27.1 us per step with every level by DPP; the strip takes that to 501 and 16.53 to 16.15 us per step (strides 2 and 4 through
-// the strip: 477 and 16.17); 236 VGPRs, no scratch, two waves per SIMD.  The next beam's state is not prefetched as in the one-node-per-lane
+// the strip: 477 and 16.17).  The impulse behind scalar branches instead of a selector FMA per component, and RK4 sums started by
+// stage 0: 410 -> 393 executed fp64 instructions per stage, no SGPR spill left (52 before), 16.25 -> 15.41 us per step (the shipped
+// library against its parent's, one box, alternating); 210 VGPRs, no scratch, two waves per SIMD.  DESIGN.md §4 has the
+// stage's fp64 budget per phase.  The next beam's state is not prefetched as in the one-node-per-lane
 // form: four nodes' records are 48 more registers than the budget of two waves per SIMD holds.
 constexpr int BLK_STRIP_PAD = 4;   // the stride of the separator level that goes through the wave's LDS strip (the third)
 constexpr int BLK_STRIP_W = BLK_STRIP_PAD + BLK_LANES + BLK_STRIP_PAD;
@@ -313,7 +316,7 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
 #pragma unroll
             for (int k = 0; k < NP; ++k)
 #pragma unroll
-                for (int c = 0; c < 3; ++c) { accq[k][c] = T(0); accv[k][c] = T(0); sq[k][c] = xq[k][c]; sv[k][c] = xv[k][c]; }
+                for (int c = 0; c < 3; ++c) { sq[k][c] = xq[k][c]; sv[k][c] = xv[k][c]; }
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 // (what a stage needs of the launch parameters is re-read through the laundered kernarg pointer: held across
@@ -325,7 +328,6 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                 const bool imp_on = ts < q.duration;
                 const T w = (s == 0 || s == 3) ? T(1) : T(2);
                 const T cs = (s == 2) ? dt : hdt;
-                const int kidx = imp_on ? 3 * kimp + q.imp_dof : -1;   // the impulse's (node, dof) in this stage, or none
                 const CP U = (CP)q.blocked;
                 const CS SC = (CS)q.slot;
                 T ec[6];
@@ -338,7 +340,7 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
 #pragma unroll
                 for (int k = 0; k < NP; ++k)
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) accq[k][c] += w * sv[k][c];
+                    for (int c = 0; c < 3; ++c) accq[k][c] = (s == 0) ? sv[k][c] : accq[k][c] + w * sv[k][c];   // (stage 0 starts the sum: no 0 + x)
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     qn3[c] = (s == 3) ? (xq[NP - 1][c] + dt6 * accq[NP - 1][c]) : (xq[NP - 1][c] + cs * sv[NP - 1][c]);
@@ -347,22 +349,59 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                 // -- the four elements left of this lane's nodes (element k joins node k-1 -- lane-1's last for k = 0 -- and node k)
                 CRB_SETPRIO(P_FORCE);
                 T fl[NP][3], r[NP][3];
+                T fr[NP][3];
 #pragma unroll
                 for (int k = 0; k < NP; ++k) {
-                    T fr[3];
-                    if (EM == EM_NONLINEAR) elem_force_nonlinear<T>(ec, k ? sq[k - 1] : qL, sq[k], false, fl[k], fr);
-                    else elem_force_linear<T>(ec, k ? sq[k - 1] : qL, sq[k], fl[k], fr);
+                    if (EM == EM_NONLINEAR) elem_force_nonlinear<T>(ec, k ? sq[k - 1] : qL, sq[k], false, fl[k], fr[k]);
+                    else elem_force_linear<T>(ec, k ? sq[k - 1] : qL, sq[k], fl[k], fr[k]);
+                }
+                // -- the impulse: fr - amp on its one (node, dof), so that r = (amp - fr) - fl there and -fr - fl everywhere else,
+                //    instead of one r = sel * amp - fr per component (12 fp64 FMAs per stage for one lane's one component).  The
+                //    selector is wave-uniform, so the choice is scalar compares and branches around ONE v_add_f64; they are
+                //    written as an opaque block per node because a C++ branch here splits the stage's straight-line code, which
+                //    the scheduler then no longer interleaves with the solve (measured: 50 spilled VGPRs).  No lane shift inside.
+                //    After a compiler upgrade re-check with `make resource-usage`: this kernel at 0 SGPR spills, <= 256 VGPRs, no
+                //    scratch.  The block can go back to the C++ form of the host branch below once that no longer splits the
+                //    schedule (same resource figures, same step time).
+                {
+                    const int kon = imp_on ? kimp : -1, dof = q.imp_dof;
+#if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) r[k][c] = ((3 * k + c == kidx) ? T(1) : T(0)) * amp - fr[c];
-                    r[k][1] += drag_force<T>(dragc, sv[k][1]);
+                    for (int k = 0; k < NP; ++k)
+                        asm volatile(
+                            "s_cmp_lg_u32 %[kon], %[k]\n\t"
+                            "s_cbranch_scc1 2f\n\t"
+                            "s_cmp_lg_u32 %[dof], 0\n\t"
+                            "s_cbranch_scc1 0f\n\t"
+                            "v_add_f64 %[f0], %[f0], -%[amp]\n"
+                            "0:\n\t"
+                            "s_cmp_lg_u32 %[dof], 1\n\t"
+                            "s_cbranch_scc1 1f\n\t"
+                            "v_add_f64 %[f1], %[f1], -%[amp]\n"
+                            "1:\n\t"
+                            "s_cmp_lg_u32 %[dof], 2\n\t"
+                            "s_cbranch_scc1 2f\n\t"
+                            "v_add_f64 %[f2], %[f2], -%[amp]\n"
+                            "2:"
+                            : [f0] "+v"(fr[k][0]), [f1] "+v"(fr[k][1]), [f2] "+v"(fr[k][2])
+                            : [kon] "s"(kon), [dof] "s"(dof), [amp] "v"(amp), [k] "n"(k)
+                            : "scc");
+#else
+                    for (int k = 0; k < NP; ++k)
+                        for (int c = 0; c < 3; ++c) fr[k][c] -= (kon == k && c == dof) ? amp : T(0);
+#endif
                 }
                 CRB_SETPRIO(P_TAIL);
-                // -- the left half of the lane's first element belongs to lane-1's last node (0 past the tip)
+                // -- right-hand side: the left half of the lane's first element belongs to lane-1's last node (0 past the tip)
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     const T flR = dpp_from_higher(fl[0][c]);
 #pragma unroll
-                    for (int k = 0; k < NP; ++k) r[k][c] -= (k + 1 < NP) ? fl[k + 1][c] : flR;
+                    for (int k = 0; k < NP; ++k) {
+                        T h = -fr[k][c];
+                        if (c == 1) h += drag_force<T>(dragc, sv[k][1]);
+                        r[k][c] = h - ((k + 1 < NP) ? fl[k + 1][c] : flR);
+                    }
                 }
                 // -- mass solve: interior, separator right-hand side, separator levels, back substitution
                 // (at: the table behind a pointer laundered on the value that the pack is applied to, so that a pack's scalar
@@ -436,7 +475,7 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                 for (int k = 0; k < NP; ++k)
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
-                        accv[k][c] += w * a[k][c];
+                        accv[k][c] = (s == 0) ? a[k][c] : accv[k][c] + w * a[k][c];
                         if (k == NP - 1) sq[k][c] = qn3[c];
                         else sq[k][c] = (s == 3) ? (xq[k][c] + dt6 * accq[k][c]) : (xq[k][c] + cs * sv[k][c]);
                         sv[k][c] = (s == 3) ? (xv[k][c] + dt6 * accv[k][c]) : (xv[k][c] + cs * a[k][c]);

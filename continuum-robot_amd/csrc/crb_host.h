@@ -1,6 +1,12 @@
-// crb_host.h -- host-side helpers shared by the launch translation units (crbeam.hip, crb_lean.hip, crb_loop.hip).
+// crb_host.h -- host-side helpers shared by the launch translation units (crbeam.hip, crb_lean.hip, crb_loop.hip,
+// crb_ctrl.hip, crb_static.hip): the runtime switches and the mechanics of a launch.
 #pragma once
+#include <hip/hip_runtime.h>
+
 #include <cstdlib>
+#include <type_traits>
+
+#include "crb_generic.h"
 
 namespace crb {
 
@@ -51,6 +57,62 @@ inline int walk_grid(int groups, int cap) {
     if (cap <= 0 || groups <= cap) return groups;
     const int rounds = (groups + cap - 1) / cap;
     return (groups + rounds - 1) / rounds;
+}
+
+// Dynamic LDS above 64 KiB must be opted into per kernel (the CU has 160 KiB).
+template <typename K>
+hipError_t lds_opt_in(K kernel, size_t bytes) {
+    if (bytes <= size_t(64) * 1024) return hipSuccess;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes));
+}
+
+// Workgroups a launch of `Kernel` keeps resident on the device: CUs x workgroups per CU by the occupancy query, asked once
+// per kernel (every device of a node is the same part).  A failed query returns its error and leaves *groups = 0, which
+// walk_grid reads as "no cap".
+template <auto Kernel>
+hipError_t resident_groups(int threads, size_t smem, int* groups) {
+    static int resident = -1;
+    if (resident < 0) {
+        int dev = 0, cus = 0, per_cu = 0;
+        *groups = 0;
+        hipError_t e;
+        if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
+        if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
+        if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, Kernel, threads, smem)) != hipSuccess) return e;
+        resident = cus * per_cu;
+    }
+    *groups = resident;
+    return hipSuccess;
+}
+
+// One table set for the whole ensemble (k: a plan or a kernel parameter block): a workgroup may keep its rows of the
+// tables and walk over several beams.
+template <typename K>
+bool shared_tables(const K& k) { return k.slot_stride == 0 && k.lv_stride == 0 && k.fin_stride == 0; }
+
+// Run-time value -> template argument: calls f(std::integral_constant<int, V>()) for the V in LO .. HI that equals v (one
+// instantiation of f's body per V) and returns its result; none() -- hipErrorInvalidValue when not given -- for any other v.
+// A launcher builds an instance exactly where its family's ..._built(...) holds (crb_*_launch.h) with `if constexpr` inside f.
+template <int LO, int HI, typename F, typename N>
+auto with_int(int v, F&& f, N&& none) -> decltype(none()) {
+    if (v == LO) return f(std::integral_constant<int, LO>());
+    if constexpr (LO < HI) return with_int<LO + 1, HI>(v, f, none);
+    else return none();
+}
+template <int LO, int HI, typename F>
+hipError_t with_int(int v, F&& f) {
+    return with_int<LO, HI>(v, f, [] { return hipErrorInvalidValue; });
+}
+template <typename F>
+auto with_bool(bool b, F&& f) { return b ? f(std::true_type()) : f(std::false_type()); }
+// the element kinds of a plan: anything but all-linear / all-nonlinear runs the per-lane branch
+template <typename F>
+auto with_elem_mode(int em, F&& f) {
+    switch (em) {
+        case EM_LINEAR: return f(std::integral_constant<int, EM_LINEAR>());
+        case EM_NONLINEAR: return f(std::integral_constant<int, EM_NONLINEAR>());
+        default: return f(std::integral_constant<int, EM_MIXED>());
+    }
 }
 
 }  // namespace crb

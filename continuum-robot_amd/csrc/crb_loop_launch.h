@@ -5,8 +5,13 @@
 #include "crb_loop.h"
 
 namespace crb {
-// launches crb_loop_kernel<double, levels, ...> for beams of 65 .. 128 thread-carried nodes (two waves per beam, groups
-// of 8 workgroups) / 33 .. 64 (one wave per beam, groups of 4); levels in {5, 6}; P.n_groups is chosen here (what the
+// The instances of crb_loop_kernel<double, levels, lognw, NB, grav, elem_mode, has_ref> that are built (crb_loop.hip
+// instantiates exactly these; crbeam.hip: loop_shape_ok asks the same function): beams of 33 .. 64 thread-carried nodes
+// (one wave per beam, lognw = 0, groups of NB = 4 workgroups) and 65 .. 128 (two waves, lognw = 1, NB = 8) at the levels the
+// truncated reduction of an fp64 mass matrix lands on.
+constexpr int loop_nb(int lognw) { return lognw == 1 ? 8 : 4; }
+constexpr bool loop_built(int levels, int lognw) { return (lognw == 0 || lognw == 1) && (levels == 5 || levels == 6); }
+// launch_loop_long: lognw = 1; launch_loop_short: lognw = 0 (a translation unit each).  P.n_groups is chosen here (what the
 // device keeps resident).  hipErrorInvalidValue when no instance covers the plan.
 // `gain` [n][2n] is re-laid into P.kfrag by a small kernel of the same launch sequence (crb_loop_gain_kernel).
 hipError_t launch_loop_long(const LoopParams<double>& P, const double* gain, int levels, bool grav, int elem_mode, hipStream_t st);

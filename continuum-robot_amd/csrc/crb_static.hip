@@ -1,13 +1,9 @@
 // crb_static.hip -- the static-equilibrium kernels (crb_static.h), one translation unit of their own.
+#include "crb_host.h"
 #include "crb_static_launch.h"
 
 namespace crb {
 namespace {
-template <typename K>
-hipError_t lds_opt_in(K kern, size_t bytes) {
-    if (bytes <= size_t(64) * 1024) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes));
-}
 template <typename T>
 hipError_t tangent_impl(const KParams<T>& k, const StaticParams<T>& q, int groups, int threads, hipStream_t st) {
     if (threads > STATIC_MAX_NT) return hipErrorInvalidValue;

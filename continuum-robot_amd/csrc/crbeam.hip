@@ -304,9 +304,7 @@ int device_assemble(crb_plan* p, const crb_beam_desc* descs, int nd, const std::
     a.elem_stride = nd > 1 ? size_t(ne) : 0;
     const int nta = (S + 63) / 64 * 64;
     const size_t smem = size_t(S) * sizeof(NodeBlocks);
-    if (smem > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&crb_assemble_kernel<T>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, int(smem)));
+    HIP_TRY(lds_opt_in(crb_assemble_kernel<T>, smem));
     // pass 1: constants, multipliers of every level, their norms (max over beams)
     HIP_TRY(hipMemset(dNorms.p, 0, size_t(lf ? lf : 1) * sizeof(double)));
     hipLaunchKernelGGL((crb_assemble_kernel<T>), dim3(nd), dim3(nta), smem, nullptr, a);
@@ -915,21 +913,12 @@ void arm_status(const crb_plan* p, KParams<T>& k, int n_steps) {
     k.status_value = int32_t(p->status_steps < 2147483647LL ? p->status_steps : 2147483647LL);
 }
 
-// dynamic LDS above 64 KiB must be opted into per kernel (the CU has 160 KiB)
-template <typename K>
-int allow_lds(K kernel, size_t bytes) {
-    if (bytes > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes)));
-    return CRB_OK;
-}
-
-// Calls f(std::integral_constant<int, lv>) for a level count lv of 0 .. MAX (one instantiation of f's body per count);
-// fails with `msg` for any other count
-template <int MAX, int LV = 0, typename F>
-int with_levels(int lv, const char* msg, F&& f) {
-    if (lv == LV) return f(std::integral_constant<int, LV>());
-    if constexpr (LV < MAX) return with_levels<MAX, LV + 1>(lv, msg, f);
-    else return fail(CRB_EUNSUPPORTED, msg);
+// calls f(T()) with T the plan's dtype (one instantiation of f's body per dtype)
+template <typename F>
+int with_dtype(const crb_plan* p, F&& f) { return p->dtype == CRB_F64 ? f(double()) : f(float()); }
+// what with_int (crb_host.h) returns for a level count no instance covers
+auto unsupported(const char* msg) {
+    return [msg] { return fail(CRB_EUNSUPPORTED, msg); };
 }
 
 // ---- decoded inputs and records: the one check of a crb_input_desc / crb_record_desc against the plan
@@ -1002,57 +991,57 @@ void set_io(KParams<T>& k, const Forcing& f, const Recording* r = nullptr) {
     if (r) { k.rec_out = static_cast<T*>(r->out); k.rec_slot = r->slot; k.rec_comp = r->comp; k.rec_every = r->every; k.rec_n = r->count; }
 }
 
-// ---- which kernel a call runs: the condition of every path, side by side.  The lean kernels (crb_lean.hip, crb_loop.hip,
-// crb_ctrl.hip) are instantiated for these shapes only; every other plan runs the general kernels.
+// ---- which kernel a call runs: the condition of every path, side by side.  The shapes the lean kernels are built for are
+// stated once per family next to its launcher (lean_*_built, controlled_built, loop_built in crb_*_launch.h: the launchers
+// instantiate exactly those); a predicate here asks that function and adds what only a plan knows -- beams per wave,
+// threads, the form of gravity, the runtime switches, LDS.  Every other plan runs the general kernels.
 bool grav_on(const crb_plan* p) { return (p->flags & CRB_FORCE_GRAVITY) != 0; }
+bool f64(const crb_plan* p) { return p->dtype == CRB_F64; }
 // the lean kernels carry gravity only in the plain cantilever's nearest-neighbour form
 bool lean_grav_ok(const crb_plan* p) { return !grav_on(p) || p->canonical_gravity; }
-// beams of more than 64 slots: only the level counts the truncated reduction lands on are built (crb_lean.hip: by_nw)
-bool lean_levels_ok(const crb_plan* p) {
-    const int lv_long = p->dtype == CRB_F64 ? 5 : 4;
-    return p->lognw == 0 ? (p->levels >= 3 && p->levels <= 6) : (p->levels == lv_long || p->levels == lv_long + 1);
-}
-// crb_step_rk4: one beam per workgroup of up to 8 waves, or beams of fewer than 64 slots packed G > 1 to a wave (the PACK
-// instantiation); a held input has its own instantiation
+// crb_step_rk4: one beam per workgroup, or beams of fewer than 64 slots packed G > 1 to a wave (the PACK instantiation); a
+// held input has its own instantiation
 bool lean_step_ok(const crb_plan* p) {
     const bool packed = p->G > 1 && p->lognw == 0 && p->NT == 64;
-    return lean_grav_ok(p) && (p->G == 1 || packed) && p->NT == (64 << p->lognw) && p->lognw <= 3 && lean_levels_ok(p) &&
+    return lean_grav_ok(p) && (p->G == 1 || packed) && p->NT == (64 << p->lognw) && lean_step_built(f64(p), p->levels, p->lognw) &&
            !env_set("CRB_DISABLE_LEAN");
 }
 // ... and its register-blocked form (crb_lean.h, NPL = 4: one wave per 256-slot beam): fp64 plans with the blocked tables
 // (built at plan time for one table set, 256 slots of equal constants, every DOF free, bitwise-uniform lane interiors:
-// crb_blocked.h), one element kind as shipped, no gravity, no held input, 3 or 4 separator levels (the instantiated ones).
-// CRB_DISABLE_BLOCKED=1: the one-node-per-lane stepper.
+// crb_blocked.h), no gravity, no held input.  CRB_DISABLE_BLOCKED=1: the one-node-per-lane stepper.
 bool blocked_step_ok(const crb_plan* p, const void* held) {
     return p->d_blocked && lean_step_ok(p) && !grav_on(p) && !held && p->G == 1 &&
-           (p->elem_mode == EM_NONLINEAR || p->elem_mode == EM_LINEAR) && p->blocked_levels == 3 &&
-           !env_set("CRB_DISABLE_BLOCKED");
+           lean_blocked_built(f64(p), p->blocked_levels, p->elem_mode) && !env_set("CRB_DISABLE_BLOCKED");
 }
-// crb_rk4_stage: the lean stepper's shapes less the packed one (the stage kernel walks over whole beams)
-bool lean_stage_ok(const crb_plan* p) { return lean_step_ok(p) && p->G == 1 && !env_set("CRB_DISABLE_LEAN_STAGE"); }
-// crb_solve_rk45: the lean RHS has no gravity form at all; one beam per workgroup of up to 4 waves
+// crb_rk4_stage: the lean stepper's plans less the packed ones (the stage kernel walks over whole beams)
+bool lean_stage_ok(const crb_plan* p) {
+    return lean_step_ok(p) && lean_stage_built(f64(p), p->levels, p->lognw) && p->G == 1 && !env_set("CRB_DISABLE_LEAN_STAGE");
+}
+// crb_solve_rk45: the lean RHS has no gravity form at all; one beam per workgroup
 bool lean_rk45_ok(const crb_plan* p) {
-    return !grav_on(p) && p->NT == (64 << p->lognw) && p->lognw <= 2 && lean_levels_ok(p) && !env_set("CRB_DISABLE_LEAN");
+    return !grav_on(p) && p->NT == (64 << p->lognw) && lean_rk45_built(f64(p), p->levels, p->lognw) && !env_set("CRB_DISABLE_LEAN");
 }
-// crb_step_implicit, one beam per workgroup of 1 / 2 / 4 waves: the kernels run 5 .. the full level count, and exist for
-// the full count of that width only (33 .. 64 / 65 .. 128 / 129 .. 256 slots)
+// crb_step_implicit, one beam per workgroup: beams that take more than half of the workgroup's lanes (the full level count
+// of that width) ...
 bool implicit_group_shape(const crb_plan* p) {
-    return p->G == 1 && p->lognw <= 2 && p->NT == (64 << p->lognw) && p->levels_full == 6 + p->lognw;
+    return p->G == 1 && p->NT == (64 << p->lognw) && p->levels_full == 6 + p->lognw && lean_implicit_built(f64(p), p->levels_full, p->lognw);
 }
-// crb_step_implicit, several beams per wave: the packed kernels exist for 3 .. 5 levels
+// ... or several beams per wave
 bool implicit_pack_shape(const crb_plan* p) {
-    return p->G > 1 && p->lognw == 0 && p->NT == 64 && p->levels_full >= 3 && p->levels_full <= 5;
+    return p->G > 1 && p->lognw == 0 && p->NT == 64 && lean_implicit_pack_built(f64(p), p->levels_full);
 }
 bool lean_implicit_enabled() { return !env_set("CRB_DISABLE_LEAN") && !env_set("CRB_DISABLE_LEAN_IMPLICIT"); }
+// (stiff_levels: where the reduction of A stops for the step size at hand, stiff_tables)
 bool lean_implicit_ok(const crb_plan* p) {
-    return (implicit_group_shape(p) || (implicit_pack_shape(p) && p->stiff_levels >= 3)) && lean_grav_ok(p) && lean_implicit_enabled();
+    const bool built = implicit_group_shape(p) ? lean_implicit_built(f64(p), p->stiff_levels, p->lognw)
+                                               : implicit_pack_shape(p) && lean_implicit_pack_built(f64(p), p->stiff_levels);
+    return built && lean_grav_ok(p) && lean_implicit_enabled();
 }
-// crb_solve_controlled: one beam per workgroup of up to 4 waves; the closed loop (fb) in one wave at the levels of M, the
-// implicit scheme at all levels of A
+// crb_solve_controlled: one beam per workgroup; the closed loop (fb) at the levels of M, the implicit scheme at all levels of A
 bool lean_controlled_ok(const crb_plan* p, bool fb) {
-    const bool shape = p->lognw <= 2 && p->NT == (64 << p->lognw) && lean_grav_ok(p) && !env_set("CRB_DISABLE_LEAN");
-    return fb ? (shape && p->lognw == 0 && p->levels >= 1 && p->levels <= 6 && !env_set("CRB_DISABLE_LEAN_FEEDBACK"))
-              : (shape && p->levels_full >= 1 && !env_set("CRB_DISABLE_LEAN_IMPLICIT"));
+    const bool shape = p->NT == (64 << p->lognw) && lean_grav_ok(p) && !env_set("CRB_DISABLE_LEAN") &&
+                       controlled_built(fb ? p->levels : p->levels_full, fb, p->lognw, grav_on(p), false, false);
+    return shape && !env_set(fb ? "CRB_DISABLE_LEAN_FEEDBACK" : "CRB_DISABLE_LEAN_IMPLICIT");
 }
 // crb_solve_controlled, closed loop: the gain in LDS while it fits there (beams of up to ~30 elements), else streamed from a
 // transposed copy in global memory (crb_ctrl.h, SG).  CRB_CTRL_STREAM_GAIN=1: streamed whatever the size.
@@ -1063,7 +1052,7 @@ bool ctrl_stream_gain(const crb_plan* p) {
 }
 // crb_solve_controlled per_wave: beams of 2 .. 32 slots packed G to a wave, implicit scheme through the lean kernel only
 bool controlled_pack_ok(const crb_plan* p, bool fb, bool lean) {
-    return !fb && lean && p->G > 1 && p->lognw == 0 && p->levels_full <= 5;
+    return !fb && lean && p->G > 1 && controlled_built(p->levels_full, false, p->lognw, grav_on(p), true, false);
 }
 // crb_step_rk4_feedback, fused: beams that live in one wave and whose gain fits LDS -- the whole rollout as ONE launch of the
 // general stepper's feedback instantiation (crb_generic.h, FB) instead of eight launches per step
@@ -1081,10 +1070,10 @@ bool fused_feedback_ok(const crb_plan* p, const void* held) {
     const size_t groups = size_t((p->B + p->G - 1) / p->G);
     return need <= size_t(52) * 1024 || groups <= per_cu * 256;
 }
-// ... and its packed lean form: several beams per wave with 3 .. 5 levels (its right-hand side costs half of the general kernel's)
+// ... and its packed lean form: several beams per wave (its right-hand side costs half of the general kernel's)
 template <typename T>
 bool lean_fused_feedback_ok(const crb_plan* p) {
-    return p->G > 1 && lean_step_ok(p) && p->levels >= 3 && p->levels <= 5 && fb_lean_lds_bytes<T>(p->G, p->n_free) <= size_t(144) * 1024 &&
+    return p->G > 1 && lean_step_ok(p) && lean_feedback_built(p->levels) && fb_lean_lds_bytes<T>(p->G, p->n_free) <= size_t(144) * 1024 &&
            !env_set("CRB_DISABLE_LEAN_FEEDBACK");
 }
 // crb_step_rk4_feedback, persistent (crb_loop.h): fp64 plans with one table set and one free-DOF set, beams of 33 .. 128
@@ -1092,11 +1081,9 @@ bool lean_fused_feedback_ok(const crb_plan* p) {
 // ensembles of at least LOOP_MIN_BEAMS beams (a group of workgroups owns 64 beams: small ensembles leave most of the chip
 // idle and are faster through the stage-split launches).
 constexpr int LOOP_MIN_BEAMS = 512;
-int loop_nb(const crb_plan* p) { return p->lognw == 1 ? 8 : 4; }
 bool loop_shape_ok(const crb_plan* p) {
-    return p->dtype == CRB_F64 && !p->mixed_topology && p->slot_stride == 0 && p->lv_stride == 0 && p->fin_stride == 0 && p->G == 1 &&
-           (p->lognw == 0 || p->lognw == 1) && p->NT == (64 << p->lognw) && p->S > 32 && (p->levels == 5 || p->levels == 6) &&
-           lean_grav_ok(p);
+    return f64(p) && !p->mixed_topology && shared_tables(*p) && p->G == 1 && p->NT == (64 << p->lognw) && p->S > 32 &&
+           loop_built(p->levels, p->lognw) && lean_grav_ok(p);
 }
 bool loop_ok(const crb_plan* p, const void* held) {
     if (!loop_shape_ok(p) || held) return false;
@@ -1116,10 +1103,10 @@ int launch_beam_lean(const crb_plan* p, const KParams<T>& k, hipStream_t st) {
         // (beams of more than 256 slots always run a truncated reduction -- their full one has 9 or 10 levels -- and the
         //  truncation never lands below 4 levels: the multipliers of level 3 are ~1e-3; fewer levels are not built)
         if (p->NT <= 512) {
-            if (int rc = allow_lds(crb_beam_kernel<T, MODE, LV, 512, 2, LEAN>, smem)) return rc;
+            HIP_TRY(lds_opt_in(crb_beam_kernel<T, MODE, LV, 512, 2, LEAN>, smem));
             hipLaunchKernelGGL((crb_beam_kernel<T, MODE, LV, 512, 2, LEAN>), grid, block, smem, st, k);
         } else {
-            if (int rc = allow_lds(crb_beam_kernel<T, MODE, LV, 1024, 4, LEAN>, smem)) return rc;
+            HIP_TRY(lds_opt_in(crb_beam_kernel<T, MODE, LV, 1024, 4, LEAN>, smem));
             hipLaunchKernelGGL((crb_beam_kernel<T, MODE, LV, 1024, 4, LEAN>), grid, block, smem, st, k);
         }
     } else {
@@ -1142,8 +1129,8 @@ int launch_beam(const crb_plan* p, const KParams<T>& k, hipStream_t st) {
 #ifdef CRB_FAST_BUILD  // kernel-tuning build (make fast): only the config-3 lean stepper is instantiated
     return fail(CRB_EUNSUPPORTED, "CRB_FAST_BUILD: generic kernels not built");
 #else
-    return with_levels<8>(p->levels, "unsupported number of cyclic-reduction levels",
-                          [&](auto lv) { return launch_beam_lv<T, MODE, decltype(lv)::value>(p, k, st); });
+    return with_int<0, 8>(p->levels, [&](auto lv) { return launch_beam_lv<T, MODE, lv>(p, k, st); },
+                          unsupported("unsupported number of cyclic-reduction levels"));
 #endif
 }
 
@@ -1166,9 +1153,8 @@ int launch_lean(const crb_plan* p, const KParams<T>& k, hipStream_t st) {
 // workgroups, each walking over several beams with the solve tables in registers.
 template <typename T>
 int launch_stage_lean(const crb_plan* p, const KParams<T>& k, hipStream_t st) {
-    const bool shared = p->slot_stride == 0 && p->lv_stride == 0 && p->fin_stride == 0;
     int groups = p->B;
-    if (shared) {
+    if (shared_tables(*p)) {
         // one wave per SIMD (256 CUs x 4) / waves per group: measured best at 2048 x 128 (208 us per step
         // against 220 with two waves per SIMD and 236 with one group per beam) -- the table reload per
         // group costs more than the extra latency hiding gains
@@ -1231,36 +1217,27 @@ extern "C" int crb_unpack_vec(const crb_plan* p, const void* v, void* v_red, voi
 extern "C" int crb_internal_force(const crb_plan* p, const void* x, void* kout, void* stream) {
     if (int rc = need_device(p, "crb_internal_force")) return rc;
     if (!x || !kout) return fail(CRB_EINVAL, "crb_internal_force: null pointer");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (p->dtype == CRB_F64) {
-        KParams<double> k = base_params<double>(p);
-        k.x = static_cast<double*>(const_cast<void*>(x));
-        k.out = static_cast<double*>(kout);
-        return launch_beam<double, MODE_KQ>(p, k, st);
-    }
-    KParams<float> k = base_params<float>(p);
-    k.x = static_cast<float*>(const_cast<void*>(x));
-    k.out = static_cast<float*>(kout);
-    return launch_beam<float, MODE_KQ>(p, k, st);
+    return with_dtype(p, [&](auto t) {
+        using T = decltype(t);
+        KParams<T> k = base_params<T>(p);
+        k.x = static_cast<T*>(const_cast<void*>(x));
+        k.out = static_cast<T*>(kout);
+        return launch_beam<T, MODE_KQ>(p, k, static_cast<hipStream_t>(stream));
+    });
 }
 
 extern "C" int crb_rhs(const crb_plan* p, const void* x, const void* u, void* xdot, void* stream) {
     if (int rc = need_device(p, "crb_rhs")) return rc;
     if (!x || !xdot) return fail(CRB_EINVAL, "crb_rhs: null pointer");
     if (x == xdot) return fail(CRB_EINVAL, "crb_rhs: xdot must not alias x");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (p->dtype == CRB_F64) {
-        KParams<double> k = base_params<double>(p);
-        k.x = static_cast<double*>(const_cast<void*>(x));
-        k.u_held = static_cast<const double*>(u);
-        k.out = static_cast<double*>(xdot);
-        return launch_beam<double, MODE_RHS>(p, k, st);
-    }
-    KParams<float> k = base_params<float>(p);
-    k.x = static_cast<float*>(const_cast<void*>(x));
-    k.u_held = static_cast<const float*>(u);
-    k.out = static_cast<float*>(xdot);
-    return launch_beam<float, MODE_RHS>(p, k, st);
+    return with_dtype(p, [&](auto t) {
+        using T = decltype(t);
+        KParams<T> k = base_params<T>(p);
+        k.x = static_cast<T*>(const_cast<void*>(x));
+        k.u_held = static_cast<const T*>(u);
+        k.out = static_cast<T*>(xdot);
+        return launch_beam<T, MODE_RHS>(p, k, static_cast<hipStream_t>(stream));
+    });
 }
 
 extern "C" int crb_step_rk4(const crb_plan* p, void* x, double t0, double dt, int n_steps, const crb_input_desc* in,
@@ -1465,9 +1442,11 @@ int stiff_tables(const crb_plan* p, double alpha, hipStream_t st) {
         HIP_TRY(hipMemcpyAsync(norms.data(), in.dNormScratch.p, size_t(lf) * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         while (used > 0 && norms[size_t(used) - 1] < std::ldexp(1.0, -53)) --used;
-        // (the lean kernels exist for 5 ... full levels, the packed ones for 3 ... 5)
-        if (implicit_group_shape(p) && used < 5 && lean_implicit_enabled()) used = 5;
-        if (implicit_pack_shape(p) && used < 3) used = 3;
+        // (the lean kernels are built from some level count on: no fewer than that, lean_implicit_built / lean_implicit_pack_built)
+        if (implicit_group_shape(p) && lean_implicit_enabled())
+            while (used < lf && !lean_implicit_built(f64(p), used, p->lognw)) ++used;
+        if (implicit_pack_shape(p))
+            while (used < lf && !lean_implicit_pack_built(f64(p), used)) ++used;
         if (used < lf) {   // the final block inverses after `used` levels
             a.fin_level = used;
             hipLaunchKernelGGL((crb_assemble_kernel<T>), dim3(nd), dim3(in.threads), in.smem, st, a);
@@ -1504,7 +1483,7 @@ int launch_implicit(const crb_plan* p, const KParams<T>& k, const StiffParams<T>
     if (lean_implicit_ok(p)) {
         // one wave per SIMD (the tables of A fill the register file): 256 CUs x 4 / waves per beam workgroups are resident
         const bool grav = grav_on(p);
-        const bool shared = p->slot_stride == 0 && q.alv_stride == 0 && q.afin_stride == 0;
+        const bool shared = shared_tables(*p);   // (the tables of A are per beam exactly where the plan's own are)
         int resident = 256 * 4 / (1 << p->lognw) * implicit_lean_minw(p->stiff_levels, grav, p->lognw);   // (waves per SIMD: crb_stiff.h)
         if (const int cap = int(env_int("CRB_LEAN_MAX_GROUPS", 0)); cap > 0) resident = cap;   // (tests)
         const int groups = (p->B + p->G - 1) / p->G;
@@ -1513,8 +1492,8 @@ int launch_implicit(const crb_plan* p, const KParams<T>& k, const StiffParams<T>
         return CRB_OK;
     }
     // (the levels of A whose multipliers matter, stiff_tables)
-    return with_levels<8>(p->stiff_levels, "crb_step_implicit: beams of more than 256 thread-carried nodes are not supported",
-                          [&](auto lv) { return launch_implicit_lv<T, decltype(lv)::value>(p, k, q, st); });
+    return with_int<0, 8>(p->stiff_levels, [&](auto lv) { return launch_implicit_lv<T, lv>(p, k, q, st); },
+                          unsupported("crb_step_implicit: beams of more than 256 thread-carried nodes are not supported"));
 #endif
 }
 
@@ -1532,8 +1511,8 @@ int launch_implicit_damped(const crb_plan* p, const KParams<T>& k, const StiffPa
     return fail(CRB_EUNSUPPORTED, "CRB_FAST_BUILD: implicit stepper not built");
 #else
     if (p->NT > 256) return fail(CRB_EUNSUPPORTED, "crb_step_implicit: beams of more than 256 thread-carried nodes are not supported");
-    return with_levels<8>(p->stiff_levels, "crb_step_implicit: beams of more than 256 thread-carried nodes are not supported",
-                          [&](auto lv) { return launch_implicit_damped_lv<T, decltype(lv)::value>(p, k, q, st); });
+    return with_int<0, 8>(p->stiff_levels, [&](auto lv) { return launch_implicit_damped_lv<T, lv>(p, k, q, st); },
+                          unsupported("crb_step_implicit: beams of more than 256 thread-carried nodes are not supported"));
 #endif
 }
 
@@ -1863,7 +1842,7 @@ template <typename T, int LV>
 int launch_fused_feedback_lv(const crb_plan* p, const KParams<T>& k, hipStream_t st) {
     const dim3 grid((p->B + p->G - 1) / p->G), block(p->NT);
     const size_t smem = fb_lds_bytes<T>(p->NT, p->G, p->n_free);
-    if (int rc = allow_lds(crb_beam_kernel<T, MODE_STEP, LV, 64, 1, false, true>, smem)) return rc;
+    HIP_TRY(lds_opt_in(crb_beam_kernel<T, MODE_STEP, LV, 64, 1, false, true>, smem));
     hipLaunchKernelGGL((crb_beam_kernel<T, MODE_STEP, LV, 64, 1, false, true>), grid, block, smem, st, k);
     HIP_TRY(hipGetLastError());
     return CRB_OK;
@@ -1890,15 +1869,15 @@ int fused_feedback_impl(const crb_plan* p, void* x, double t0, double dt, int n_
         return CRB_OK;
     }
     // (a beam inside one wave: at most 6 levels)
-    return with_levels<6>(p->levels, "crb_step_rk4_feedback: unsupported number of cyclic-reduction levels",
-                          [&](auto lv) { return launch_fused_feedback_lv<T, decltype(lv)::value>(p, k, st); });
+    return with_int<0, 6>(p->levels, [&](auto lv) { return launch_fused_feedback_lv<T, lv>(p, k, st); },
+                          unsupported("crb_step_rk4_feedback: unsupported number of cyclic-reduction levels"));
 #endif
 }
 
 int loop_feedback(const crb_plan* p, void* x, double t0, double dt, int n_steps, const void* gain, const void* ref, const Forcing& f,
                   void* work, hipStream_t st) {
     if (int rc = ensure_red_map(p)) return rc;
-    const int nb = loop_nb(p), n_rb = (p->B + 63) / 64;
+    const int nb = loop_nb(p->lognw), n_rb = (p->B + 63) / 64;
     const crb::LoopWork lay = crb::loop_work_layout(nb, n_rb < crb::LOOP_MAX_GROUPS ? n_rb : crb::LOOP_MAX_GROUPS);
     char* w = static_cast<char*>(work);
     crb::LoopParams<double> P;
@@ -1935,7 +1914,7 @@ extern "C" size_t crb_feedback_work_bytes(const crb_plan* p) {
     size_t need = 3 * state + force;
     if (loop_shape_ok(p)) {
         const int n_rb = (p->B + 63) / 64;
-        const size_t loop = crb::loop_work_layout(loop_nb(p), n_rb < crb::LOOP_MAX_GROUPS ? n_rb : crb::LOOP_MAX_GROUPS).total;
+        const size_t loop = crb::loop_work_layout(loop_nb(p->lognw), n_rb < crb::LOOP_MAX_GROUPS ? n_rb : crb::LOOP_MAX_GROUPS).total;
         if (loop > need) need = loop;
     }
     return need;
@@ -1989,10 +1968,10 @@ int launch_rk45_lv(const crb_plan* p, const KParams<T>& k, const Rk45Params& q, 
     const dim3 grid(p->B), block(p->NT);
     const size_t smem = rk45_lds_bytes<T>(p->NT);
     if (p->NT <= 256) {
-        if (int rc = allow_lds(crb_rk45_kernel<T, LV, 256, 1>, smem)) return rc;
+        HIP_TRY(lds_opt_in(crb_rk45_kernel<T, LV, 256, 1>, smem));
         hipLaunchKernelGGL((crb_rk45_kernel<T, LV, 256, 1>), grid, block, smem, st, k, q);
     } else if constexpr (LV >= 4) {
-        if (int rc = allow_lds(crb_rk45_kernel<T, LV, 1024, 1>, smem)) return rc;
+        HIP_TRY(lds_opt_in(crb_rk45_kernel<T, LV, 1024, 1>, smem));
         hipLaunchKernelGGL((crb_rk45_kernel<T, LV, 1024, 1>), grid, block, smem, st, k, q);
     } else {
         return fail(CRB_EUNSUPPORTED, "a beam of more than 256 thread-carried nodes with fewer than 4 cyclic-reduction levels");
@@ -2009,8 +1988,8 @@ int launch_rk45(const crb_plan* p, const KParams<T>& k, const Rk45Params& q, hip
         HIP_TRY(crb::launch_rk45_lean(k, q, p->B, p->levels, p->lognw, p->elem_mode, st));
         return CRB_OK;
     }
-    return with_levels<6>(p->levels, "crb_solve_rk45: unsupported number of cyclic-reduction levels",
-                          [&](auto lv) { return launch_rk45_lv<T, decltype(lv)::value>(p, k, q, st); });
+    return with_int<0, 6>(p->levels, [&](auto lv) { return launch_rk45_lv<T, lv>(p, k, q, st); },
+                          unsupported("crb_solve_rk45: unsupported number of cyclic-reduction levels"));
 #endif
 }
 template <typename T>
@@ -2059,10 +2038,10 @@ int launch_feedback_tile(const FeedbackParams<T>& f, int ksplit, hipStream_t st)
     const size_t smem = feedback_lds_bytes<T, BM, BN, BK>(f.n2);
     if (ksplit > 1) HIP_TRY(hipMemsetAsync(f.u, 0, size_t(f.B) * f.u_stride * sizeof(T), st));
     if (f.ref) {
-        if (int rc = allow_lds(crb_feedback_kernel<T, BM, BN, BK, WR, true>, smem)) return rc;
+        HIP_TRY(lds_opt_in(crb_feedback_kernel<T, BM, BN, BK, WR, true>, smem));
         hipLaunchKernelGGL((crb_feedback_kernel<T, BM, BN, BK, WR, true>), grid, dim3(256), smem, st, f);
     } else {
-        if (int rc = allow_lds(crb_feedback_kernel<T, BM, BN, BK, WR, false>, smem)) return rc;
+        HIP_TRY(lds_opt_in(crb_feedback_kernel<T, BM, BN, BK, WR, false>, smem));
         hipLaunchKernelGGL((crb_feedback_kernel<T, BM, BN, BK, WR, false>), grid, dim3(256), smem, st, f);
     }
     return CRB_OK;
@@ -2072,10 +2051,10 @@ int launch_feedback_ws(const FeedbackParams<T>& f, hipStream_t st) {
     const dim3 grid((f.B + 63) / 64, (f.n + BN - 1) / BN);
     const size_t smem = feedback_lds_bytes<T, 64, BN, BK>(f.n2);
     if (f.ref) {
-        if (int rc = allow_lds(crb_feedback_ws_kernel<T, BN, BK, true>, smem)) return rc;
+        HIP_TRY(lds_opt_in(crb_feedback_ws_kernel<T, BN, BK, true>, smem));
         hipLaunchKernelGGL((crb_feedback_ws_kernel<T, BN, BK, true>), grid, dim3(256 + WS_NL), smem, st, f);
     } else {
-        if (int rc = allow_lds(crb_feedback_ws_kernel<T, BN, BK, false>, smem)) return rc;
+        HIP_TRY(lds_opt_in(crb_feedback_ws_kernel<T, BN, BK, false>, smem));
         hipLaunchKernelGGL((crb_feedback_ws_kernel<T, BN, BK, false>), grid, dim3(256 + WS_NL), smem, st, f);
     }
     return CRB_OK;
@@ -2242,14 +2221,12 @@ extern "C" int crb_gather_dof(const crb_plan* p, const void* x, int plane, int n
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t stride = size_t(2) * p->n_node * 4, off = (size_t(plane) * p->n_node + node) * 4 + dof;
     const int bs = 256, grid = (p->B + bs - 1) / bs;
-    if (p->dtype == CRB_F64)
-        hipLaunchKernelGGL((crb_gather_kernel<double>), dim3(grid), dim3(bs), 0, st, static_cast<const double*>(x), stride,
-                           off, p->B, static_cast<double*>(out));
-    else
-        hipLaunchKernelGGL((crb_gather_kernel<float>), dim3(grid), dim3(bs), 0, st, static_cast<const float*>(x), stride, off,
-                           p->B, static_cast<float*>(out));
-    HIP_TRY(hipGetLastError());
-    return CRB_OK;
+    return with_dtype(p, [&](auto t) -> int {
+        using T = decltype(t);
+        hipLaunchKernelGGL((crb_gather_kernel<T>), dim3(grid), dim3(bs), 0, st, static_cast<const T*>(x), stride, off, p->B, static_cast<T*>(out));
+        HIP_TRY(hipGetLastError());
+        return CRB_OK;
+    });
 }
 
 // ------------------------------------------------------------------ static equilibrium, tangent stiffness (crb_static.h)
@@ -2283,16 +2260,13 @@ extern "C" int crb_tangent_stiffness(const crb_plan* p, const void* x, void* out
     if (!x || !out) return fail(CRB_EINVAL, "crb_tangent_stiffness: null pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int groups = (p->B + p->G - 1) / p->G;
-    if (p->dtype == CRB_F64) {
-        StaticParams<double> q{};
-        q.blocks = static_cast<double*>(out);
-        HIP_TRY(crb::launch_tangent(static_params<double>(p, x), q, groups, p->NT, st));
-    } else {
-        StaticParams<float> q{};
-        q.blocks = static_cast<float*>(out);
-        HIP_TRY(crb::launch_tangent(static_params<float>(p, x), q, groups, p->NT, st));
-    }
-    return CRB_OK;
+    return with_dtype(p, [&](auto t) -> int {
+        using T = decltype(t);
+        StaticParams<T> q{};
+        q.blocks = static_cast<T*>(out);
+        HIP_TRY(crb::launch_tangent(static_params<T>(p, x), q, groups, p->NT, st));
+        return CRB_OK;
+    });
 }
 
 extern "C" int crb_solve_static(const crb_plan* p, void* x, const crb_input_desc* in, int load_steps, int max_iter, double rtol,

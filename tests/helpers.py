@@ -143,3 +143,44 @@ def nitinol_columns(n, kind="linear", bcs=None):
         "wetted_area": np.full(n, 2 * np.pi * r * L),
         "drag_coef": np.full(n, 0.82),
     }
+
+
+GRADED_FAMILIES = ("taper3", "taper10", "taper30", "mesh4", "step", "allcols", "nearly_uniform")
+
+
+def graded_columns(n, kind, family, bcs=None):
+    """The Nitinol rod of ``nitinol_columns`` with properties that vary along the span (deterministic, no random numbers),
+    s = j / (n - 1) for element j:
+
+    taper3 / taper10 / taper30   radius r_j = 0.005 ratio^-s (cross_area, moment_inertia, wetted_area follow), length 0.25
+    mesh4                        L_j = 0.25 4^(s - 1/2), the other columns constant (wetted_area as nitinol_columns has it)
+    step                         density and modulus x 0.1 on the tip half (j >= n / 2)
+    allcols                      taper3's radius, L_j = 0.25 (1 + 0.3 sin(2 pi j / 7)), density (1 + 0.2 cos(2 pi j / 5)),
+                                 drag_coef = 0.5 + 0.6 s: every column differs from both of its neighbours
+    nearly_uniform               nitinol_columns with length[100] x 1.01
+    """
+    assert family in GRADED_FAMILIES, family
+    cols = nitinol_columns(n, kind, bcs)
+    j = np.arange(n)
+    s = j / (n - 1) if n > 1 else np.zeros(n)
+    r = np.full(n, 0.005)
+    if family.startswith("taper") or family == "allcols":
+        r = 0.005 * (3.0 if family == "allcols" else float(family[5:])) ** (-s)
+    if family == "mesh4":
+        cols["length"] = 0.25 * 4.0 ** (s - 0.5)
+    if family == "step":
+        tip = j >= n / 2
+        cols["density"] = np.where(tip, 0.1, 1.0) * cols["density"]
+        cols["elastic_modulus"] = np.where(tip, 0.1, 1.0) * cols["elastic_modulus"]
+    if family == "allcols":
+        cols["length"] = 0.25 * (1.0 + 0.3 * np.sin(2.0 * np.pi * j / 7.0))
+        cols["density"] = 6450.0 * (1.0 + 0.2 * np.cos(2.0 * np.pi * j / 5.0))
+        cols["drag_coef"] = 0.5 + 0.6 * s
+    if family == "nearly_uniform":
+        assert n > 100, "nearly_uniform lengthens element 100: the rod needs more than 100 elements"
+        cols["length"][100] *= 1.01
+    if family.startswith("taper") or family == "allcols":
+        cols["cross_area"] = np.pi * r**2
+        cols["moment_inertia"] = np.pi * r**4 / 4
+        cols["wetted_area"] = 2 * np.pi * r * cols["length"]
+    return cols

@@ -72,6 +72,11 @@ class InputCotangent(C.Structure):
     _fields_ = [("amp_bar", C.c_void_p), ("f_held_bar", C.c_void_p)]
 
 
+class ParamCotangent(C.Structure):
+    """crb_param_cotangent: accumulated cotangents of the rod's parameters, device [n_cot][B][n_node][8]"""
+    _fields_ = [("param_bar", C.c_void_p)]
+
+
 class RecordDesc(C.Structure):
     _fields_ = [("plane", C.c_int32), ("node", C.c_int32), ("dof", C.c_int32), ("every", C.c_int32), ("out", C.c_void_p)]
 
@@ -166,6 +171,11 @@ def load():
                                           C.POINTER(RecordDesc), vp, _dp, vp]
     L.crb_step_rk4_adjoint.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, i32, i32, C.POINTER(InputDesc),
                                        C.POINTER(RecordDesc), C.POINTER(InputCotangent), vp, vp]
+    L.crb_rk4_adjoint_params_work_bytes.restype = C.c_size_t
+    L.crb_rk4_adjoint_params_work_bytes.argtypes = [vp, i32, i32]
+    L.crb_step_rk4_adjoint_params.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, i32, i32, C.POINTER(InputDesc),
+                                              C.POINTER(RecordDesc), C.POINTER(InputCotangent), C.POINTER(ParamCotangent), vp,
+                                              vp]
     L.crb_plan_get_grav_transpose.argtypes = [vp, i32, vp, vp, vp]
     L.crb_step_rk4_feedback.argtypes = [vp, vp, C.c_double, C.c_double, i32, vp, vp, C.POINTER(InputDesc), vp,
                                         C.POINTER(C.c_double), vp]

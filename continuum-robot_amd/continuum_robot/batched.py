@@ -675,15 +675,22 @@ class BeamEnsemble:
         xb, ub = self._unpack_dirs(xbar), self._unpack_force_dirs(ubar)
         return (xb[0], ub[0]) if single else (xb, ub)
 
-    def checkpoint_interval(self, n_steps: int, checkpoint_every: Optional[int] = None) -> int:
+    def checkpoint_interval(self, n_steps: int, checkpoint_every: Optional[int] = None,
+                            param_cotangents: Optional[int] = None) -> int:
         """Steps per checkpoint segment of an adjoint rollout: ``checkpoint_every``, or ceil(sqrt(n_steps)) lowered until the
-        work buffer of crb_step_rk4_adjoint (crb_rk4_adjoint_work_bytes) fits ADJOINT_WORK_BUDGET."""
+        work buffer of crb_step_rk4_adjoint (crb_rk4_adjoint_work_bytes) fits ADJOINT_WORK_BUDGET.  ``param_cotangents``: the
+        number of cotangents of a ``step_adjoint_params`` call, whose work buffer
+        (crb_rk4_adjoint_params_work_bytes) is sized instead."""
         if checkpoint_every is not None:
             if int(checkpoint_every) < 1:
                 raise ValueError("checkpoint_every must be >= 1")
             return int(checkpoint_every)
         every = max(1, int(np.ceil(np.sqrt(max(int(n_steps), 1)))))
-        while every > 1 and self._lib.crb_rk4_adjoint_work_bytes(self.plan.h, every) > self.ADJOINT_WORK_BUDGET:
+        if param_cotangents is None:
+            work_bytes = lambda e: self._lib.crb_rk4_adjoint_work_bytes(self.plan.h, e)  # noqa: E731
+        else:
+            work_bytes = lambda e: self._lib.crb_rk4_adjoint_params_work_bytes(self.plan.h, e, int(param_cotangents))  # noqa: E731
+        while every > 1 and work_bytes(every) > self.ADJOINT_WORK_BUDGET:
             every -= 1
         return every
 
@@ -698,14 +705,17 @@ class BeamEnsemble:
                                                         self._ptr(ckpt), C.byref(t_end), self._stream()))
         return ckpt
 
-    def _adjoint(self, ckpt, lamd, n_steps, dt, t0, desc, every, rec_bar, want_amp):
-        """crb_step_rk4_adjoint: lamd [D, B, 2, n_node, 4] in place; returns (amp_bar [D, B] or None, f_bar [D, B, n_node, 4])"""
+    def _adjoint(self, ckpt, lamd, n_steps, dt, t0, desc, every, rec_bar, want_amp, want_params=False):
+        """crb_step_rk4_adjoint: lamd [D, B, 2, n_node, 4] in place; returns (amp_bar [D, B] or None, f_bar [D, B, n_node, 4]).
+        ``want_params``: crb_step_rk4_adjoint_params instead, and a third return param_bar [D, B, n_node, 8]."""
         D = lamd.shape[0]
         grad = nat.InputCotangent()
         amp_bar = torch.zeros((D, self.n_beams), dtype=self.dtype, device=self.device) if want_amp else None
         f_bar = torch.zeros((D, self.n_beams, self.n_node, 4), dtype=self.dtype, device=self.device)
         grad.amp_bar = amp_bar.data_ptr() if amp_bar is not None else None
         grad.f_held_bar = f_bar.data_ptr()
+        if want_params:
+            return self._adjoint_params(ckpt, lamd, n_steps, dt, t0, desc, every, rec_bar, grad, amp_bar, f_bar)
         work = torch.empty((max(1, int(self._lib.crb_rk4_adjoint_work_bytes(self.plan.h, every))) + 7) // 8,
                            dtype=torch.float64, device=self.device)
         with self._on_device():
@@ -715,6 +725,64 @@ class BeamEnsemble:
                                                      self._ptr(work), self._stream()))
         self._keep = [work, ckpt, lamd, amp_bar, f_bar]
         return amp_bar, f_bar
+
+    def _adjoint_params(self, ckpt, lamd, n_steps, dt, t0, desc, every, rec_bar, grad, amp_bar, f_bar):
+        """crb_step_rk4_adjoint_params on _adjoint's buffers: returns (amp_bar, f_bar, param_bar [D, B, n_node, 8])"""
+        D = lamd.shape[0]
+        pgrad = nat.ParamCotangent()
+        param_bar = torch.zeros((D, self.n_beams, self.n_node, 8), dtype=self.dtype, device=self.device)
+        pgrad.param_bar = param_bar.data_ptr()
+        work = torch.empty((max(1, int(self._lib.crb_rk4_adjoint_params_work_bytes(self.plan.h, every, int(D)))) + 7) // 8,
+                           dtype=torch.float64, device=self.device)
+        with self._on_device():
+            nat.check(self._lib.crb_step_rk4_adjoint_params(self.plan.h, self._ptr(ckpt), self._ptr(lamd), int(D), float(t0),
+                                                            float(dt), int(n_steps), int(every), C.byref(desc),
+                                                            C.byref(rec_bar) if rec_bar is not None else None,
+                                                            C.byref(grad), C.byref(pgrad), self._ptr(work), self._stream()))
+        self._keep = [work, ckpt, lamd, amp_bar, f_bar, param_bar]
+        return amp_bar, f_bar, param_bar
+
+    def _param_columns(self):
+        """Per-beam parameter columns padded to [B, n_elem] (1 past a beam's own elements, so that divisions stay finite
+        where the gradients are zero anyway), the fluid densities [B] and the fluid switches [B], on the device"""
+        if getattr(self, "_param_cols", None) is None:
+            B, ne = self.n_beams, self.n_elem
+            cols = self.columns if isinstance(self.columns, list) else [self.columns] * B
+            fps = self._fps if len(self._fps) == B else [self._fps[0]] * B
+            out = {k: np.ones((B, ne)) for k in ("elastic_modulus", "moment_inertia", "drag_coef")}
+            for b, c in enumerate(cols):
+                nb = int(self.n_elem_per_beam[b])
+                out["elastic_modulus"][b, :nb] = np.asarray(c["elastic_modulus"], dtype=np.float64)[:nb]
+                out["moment_inertia"][b, :nb] = np.asarray(c["moment_inertia"], dtype=np.float64)[:nb]
+                if fps[b].enable_fluid_effects:
+                    out["drag_coef"][b, :nb] = np.asarray(c["drag_coef"], dtype=np.float64)[:nb]
+            out["fluid_density"] = np.array([f.fluid_density if f.enable_fluid_effects else 0.0 for f in fps])
+            self._param_cols = {k: torch.as_tensor(v, dtype=self.dtype, device=self.device) for k, v in out.items()}
+        return self._param_cols
+
+    def _param_dict(self, param_bar: torch.Tensor):
+        """crb_param_cotangent records [D, B, n_node, 8] -> step_adjoint_params' dict of parameter gradients, each [D, ...]"""
+        pc = self._param_columns()
+        D, B, ne = param_bar.shape[0], self.n_beams, self.n_elem
+        sA, sI = param_bar[:, :, 1:, 0].contiguous(), param_bar[:, :, 1:, 1].contiguous()   # element e lies left of node e + 1
+        sD = param_bar[:, :, :, 2].contiguous()
+        # the plan builder's node factor 0.5 rho_f Cd[row] A_wet[row], row = the node's own element row, the last row again
+        # for the tip (crbeam.hip; fluid_forces.py:59-61, 87-90): element e collects node e, the last one the tip too
+        last = torch.as_tensor(self.n_elem_per_beam - 1, dtype=torch.int64, device=self.device).view(1, B, 1).expand(D, B, 1)
+        tip = sD.gather(2, last + 1)
+        row_sum = sD.scatter(2, last + 1, 0.0)[:, :, :ne].contiguous()
+        row_sum.scatter_add_(2, last, tip)
+        cd, rho = pc["drag_coef"], pc["fluid_density"]
+        zero = torch.zeros((), dtype=self.dtype, device=self.device)
+        return {
+            "EA_scale": sA, "EI_scale": sI,
+            "elastic_modulus": (sA + sI) / pc["elastic_modulus"],
+            "moment_inertia": sI / pc["moment_inertia"],
+            "drag_scale": sD,
+            "fluid_density": torch.where(rho != 0, sD.sum(dim=2) / torch.where(rho != 0, rho, 1.0), zero),
+            "drag_coef": torch.where(cd != 0, row_sum / torch.where(cd != 0, cd, 1.0), zero),
+            "gravity": torch.stack([param_bar[:, :, :, 3].sum(dim=2), param_bar[:, :, :, 4].sum(dim=2)], dim=2),
+        }
 
     def _record_cotangent(self, record, n_steps, every, lam_record, D):
         """crb_record_desc pointing at the cotangent of step()'s record samples, [D, ...] on the device (zeros if None)"""
@@ -744,22 +812,53 @@ class BeamEnsemble:
         dL/d held_force [B, n]), with a leading D axis when ``lam_red`` has one.  The rollout starts at ``x0_red`` (None: the
         resident state) and clock ``t0`` (None: ``time``); ``state``, ``time`` and ``status`` are left alone.
         ``checkpoint_every``: steps per checkpoint segment (checkpoint_interval); the result does not depend on it, bitwise.
-        The derivative is the exact transpose of the discrete RK4 map.  fp64 ensembles only."""
+        The derivative is the exact transpose of the discrete RK4 map.  fp64 ensembles only.
+        ``step_adjoint_params`` also gives the gradient with respect to the rod's own parameters."""
+        return self._step_adjoint(False, n_steps, dt, lam_red, x0_red, impulse_amp, impulse_duration, impulse_index, held_force,
+                                  t0, record, record_every, lam_record, checkpoint_every)
+
+    def step_adjoint_params(self, n_steps: int, dt: float, lam_red, x0_red=None, impulse_amp=None,
+                            impulse_duration: float = 0.01, impulse_index: int = -2, held_force=None,
+                            t0: Optional[float] = None, record=None, record_every: int = 1, lam_record=None,
+                            checkpoint_every: Optional[int] = None):
+        """``step_adjoint`` (the same arguments; the first three returns are bitwise its returns) with a fourth return: the
+        gradient of the loss with respect to the rod itself -- stiffness per element, drag, gravity -- as fitting a rod to a
+        recorded trajectory needs it (crb_step_rk4_adjoint_params: the same sweep, storing its per-stage M^-T lambda_v, and one
+        reduction launch per segment).  A dict of tensors, each with a leading D axis when ``lam_red`` has one:
+          EA_scale, EI_scale [B, n_elem]  dL/d of relative scales of each element's EA and EI, at scale 1
+          elastic_modulus [B, n_elem]     (EA_scale + EI_scale) / E   (complete: E enters only the stiffness)
+          moment_inertia  [B, n_elem]     EI_scale / I                (complete)
+          drag_scale      [B, n_node]     dL/d of a relative scale of each node's drag factor 0.5 rho_f Cd A_wet
+          fluid_density   [B]             sum of drag_scale / rho_f; zeros when the fluid is off
+          drag_coef       [B, n_elem]     drag_scale through the node factor's map from the drag_coef column (a node reads its
+                                          own element row, the tip the last row again); zero where drag_coef is 0
+          gravity         [B, 2]          dL/d (g_x, g_y), summed over the segments
+        Entries past a beam's own element / node count (mixed-topology ensembles) are zero.  Not available: gradients with
+        respect to length, cross_area and density (they enter the mass matrix and its reduction tables), parameters as
+        autograd inputs of ``rollout`` (its forward would need parameter overrides), and the closed loop."""
+        return self._step_adjoint(True, n_steps, dt, lam_red, x0_red, impulse_amp, impulse_duration, impulse_index, held_force,
+                                  t0, record, record_every, lam_record, checkpoint_every)
+
+    def _step_adjoint(self, param_grads, n_steps, dt, lam_red, x0_red, impulse_amp, impulse_duration, impulse_index, held_force,
+                      t0, record, record_every, lam_record, checkpoint_every):
         lam, single = self._dirs(lam_red, 2 * self.n, "step_adjoint: lam_red")
         D = lam.shape[0]
         t0 = self.time if t0 is None else float(t0)
-        every = self.checkpoint_interval(n_steps, checkpoint_every)
+        every = self.checkpoint_interval(n_steps, checkpoint_every, D if param_grads else None)
         desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index, held_force)
         x = self.state.clone() if x0_red is None else self.pack_state(x0_red)
         ckpt = self._checkpoint(x, n_steps, dt, t0, desc, every, None)
         rec_bar, cot = self._record_cotangent(record, n_steps, record_every, lam_record, D)
         lamd = self._pack_dirs(lam, True)
-        amp_bar, f_bar = self._adjoint(ckpt, lamd, n_steps, dt, t0, desc, every, rec_bar, impulse_amp is not None)
+        res = self._adjoint(ckpt, lamd, n_steps, dt, t0, desc, every, rec_bar, impulse_amp is not None, param_grads)
+        amp_bar, f_bar = res[0], res[1]
         self._keep += keep + [x, cot]
         xb, fb = self._unpack_dirs(lamd), self._unpack_force_dirs(f_bar)
-        if single:
-            return xb[0], (amp_bar[0] if amp_bar is not None else None), fb[0]
-        return xb, amp_bar, fb
+        out = (xb[0], (amp_bar[0] if amp_bar is not None else None), fb[0]) if single else (xb, amp_bar, fb)
+        if param_grads:
+            pd = self._param_dict(res[2])
+            out += ({k: v[0] for k, v in pd.items()} if single else pd,)
+        return out
 
     def rollout(self, x0_red, n_steps: int, dt: float, impulse_amp=None, held_force=None, impulse_duration: float = 0.01,
                 impulse_index: int = -2, t0: float = 0.0, record=None, record_every: int = 1,

@@ -47,7 +47,8 @@ namespace crb {
 constexpr int ADJ_MAX_NT = 256;
 constexpr int GRAV_SEG_FANIN = 2;   // node DOFs one component of a segment's gravity lands on (fan-in of the reversed gathers)
 constexpr int GRAV_PHI_FANIN = 2;   // segments whose rotation average reads one DOF
-enum : int { ADJ_RHS = 0, ADJ_FWD = 1, ADJ_BWD = 2 };
+// ADJ_BWD_STORE: ADJ_BWD that also writes every stage's masked rbar for crb_param_grad_kernel (crb_paramgrad.h)
+enum : int { ADJ_RHS = 0, ADJ_FWD = 1, ADJ_BWD = 2, ADJ_BWD_STORE = 3 };
 
 // Inverse gravity lists of one slot (host-built: crb_plan_get_grav_transpose).  -1 = no entry; entries in ascending order.
 struct GravAdj {
@@ -81,6 +82,9 @@ struct AdjParams {
     T* amp_bar;                 // [n_cot][B] or nullptr
     T* f_bar;                   // [n_cot][B][n_node][4] or nullptr
     int step0;                  // index of the segment's first step in the rollout (record cotangents)
+    // ADJ_BWD_STORE writes, crb_param_grad_kernel reads (last, so that the fields above keep their kernel-argument offsets)
+    T* rbar;                    // [n_steps][4][n_cot][B][n_node][4] the masked rbar = M^-T lambda_v of every stage of the segment
+    T* param_bar;               // [n_cot][B][n_node][8] crb_param_grad_kernel's accumulators (crb_param_cotangent)
 };
 
 // LDS: q [3][NT], rbar [3][NT], element left halves / element forces [3][NT], segment gravity / phibar [2][NT], reduction
@@ -384,6 +388,7 @@ __device__ __forceinline__ void opaque_consts(JvpConst<T>& k, AdjIdx<T>& ix) {
 // ADJ_RHS: xdot = f(x, u) (instance 0, when p.out is set), xbar[d] = J_x^T lam[d], ubar[d] = J_u^T lam[d].
 // ADJ_FWD: p.n_steps RK4 steps from p.x with checkpoints / per-step start states (one instance per beam).
 // ADJ_BWD: the sweep of one segment of p.n_steps steps back over aq.work, lam[d] and the input cotangents in place.  fp64 only.
+// ADJ_BWD_STORE: the same sweep, the same arithmetic; each stage's masked ub also goes to aq.rbar (component 3 = 0).
 template <typename T, int MODE>
 __global__ void __launch_bounds__(ADJ_MAX_NT) crb_adj_kernel(const KParams<T> p, const AdjParams<T> aq) {
     static_assert(sizeof(T) == 8, "the adjoint kernels are fp64");
@@ -533,6 +538,12 @@ __global__ void __launch_bounds__(ADJ_MAX_NT) crb_adj_kernel(const KParams<T> p,
         rec_p = p.rec_slot == REC_ALL_SLOTS ? p.rec_out + d * size_t(p.rec_n) * state_sz + xoff
                                             : p.rec_out + (d * size_t(p.B) + tp.beam) * size_t(p.rec_n);
     asm volatile("" : "+v"(lam_p), "+v"(fb_p), "+v"(ab_p), "+v"(rec_p));
+    T* rb_p = nullptr;                                                    // (ADJ_BWD_STORE: this lane's rbar record of stage 0)
+    const size_t rb_stride = size_t(gridDim.y) * size_t(p.B) * plane;     //  and the stride from one stage to the next
+    if (MODE == ADJ_BWD_STORE) {
+        rb_p = aq.rbar + luoff;
+        asm volatile("" : "+v"(rb_p));
+    }
     const T dt = T(p.dt), hdt = T(0.5 * p.dt), dt3 = T(p.dt / 3.0), dt6 = T(p.dt / 6.0);
 #pragma unroll 1
     for (int i = p.n_steps - 1; i >= 0; --i) {
@@ -583,6 +594,12 @@ __global__ void __launch_bounds__(ADJ_MAX_NT) crb_adj_kernel(const KParams<T> p,
             for (int c = 0; c < 6; ++c) sum[c] = (s == 3) ? sb[c] : sum[c] + sb[c];
 #pragma unroll
             for (int c = 0; c < 3; ++c) fb[c] = fb[c] + ub[c] * sc.mask[c];
+            if (MODE == ADJ_BWD_STORE && valid) {
+                T* const ro = rb_p + (size_t(i) * 4 + size_t(s)) * rb_stride;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) ro[c] = ub[c] * sc.mask[c];
+                ro[3] = T(0);
+            }
             const double ts = (s == 0) ? tc : ((s == 3) ? t_full : t_half);
             if (imp && ts < p.duration) {
                 T ui = T(0);

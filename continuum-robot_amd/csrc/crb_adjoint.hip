@@ -1,5 +1,6 @@
 // crb_adjoint.hip -- the adjoint kernels (crb_adjoint.h), one translation unit of their own.
 #include "crb_adjoint_launch.h"
+#include "crb_paramgrad.h"
 
 namespace crb {
 namespace {
@@ -19,5 +20,14 @@ hipError_t launch_adj_forward(const KParams<double>& k, const AdjParams<double>&
 }
 hipError_t launch_adj_backward(const KParams<double>& k, const AdjParams<double>& q, int groups, int n_cot, int threads, hipStream_t st) {
     return adj_impl<ADJ_BWD>(k, q, groups, n_cot, threads, st);
+}
+hipError_t launch_adj_backward_store(const KParams<double>& k, const AdjParams<double>& q, int groups, int n_cot, int threads,
+                                     hipStream_t st) {
+    return adj_impl<ADJ_BWD_STORE>(k, q, groups, n_cot, threads, st);
+}
+hipError_t launch_param_grad(const KParams<double>& k, const AdjParams<double>& q, int groups, int n_cot, int threads, hipStream_t st) {
+    if (threads > ADJ_MAX_NT || n_cot < 1 || n_cot > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((crb_param_grad_kernel<double>), dim3(groups, n_cot), dim3(threads), adjoint_lds_bytes<double>(threads), st, k, q);
+    return hipGetLastError();
 }
 }  // namespace crb

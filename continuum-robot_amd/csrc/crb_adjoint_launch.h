@@ -11,4 +11,9 @@ hipError_t launch_adj_rhs(const KParams<double>& k, const AdjParams<double>& q, 
 hipError_t launch_adj_forward(const KParams<double>& k, const AdjParams<double>& q, int groups, int threads, hipStream_t st);
 // crb_adj_kernel<double, ADJ_BWD>: the backward sweep over one segment of k.n_steps steps, for n_cot cotangents
 hipError_t launch_adj_backward(const KParams<double>& k, const AdjParams<double>& q, int groups, int n_cot, int threads, hipStream_t st);
+// crb_adj_kernel<double, ADJ_BWD_STORE>: the same sweep, every stage's masked rbar also written to q.rbar
+hipError_t launch_adj_backward_store(const KParams<double>& k, const AdjParams<double>& q, int groups, int n_cot, int threads,
+                                     hipStream_t st);
+// crb_param_grad_kernel<double> (crb_paramgrad.h): the parameter sums of one segment of k.n_steps steps over q.work and q.rbar
+hipError_t launch_param_grad(const KParams<double>& k, const AdjParams<double>& q, int groups, int n_cot, int threads, hipStream_t st);
 }  // namespace crb

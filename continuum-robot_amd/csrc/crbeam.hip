@@ -2530,38 +2530,49 @@ extern "C" int crb_step_rk4_checkpoint(const crb_plan* p, void* x, double t0, do
     return CRB_OK;
 }
 
-extern "C" int crb_step_rk4_adjoint(const crb_plan* p, const void* ckpt, void* lam, int n_cot, double t0, double dt, int n_steps,
-                                    int every, const crb_input_desc* in, const crb_record_desc* rec_bar,
-                                    const crb_input_cotangent* grad, void* work, void* stream) {
-    if (int rc = adjoint_checks(p, n_cot, "crb_step_rk4_adjoint")) return rc;
-    if (!ckpt || !lam) return fail(CRB_EINVAL, "crb_step_rk4_adjoint: null checkpoint buffer or cotangent");
-    if (!work) return fail(CRB_EINVAL, "crb_step_rk4_adjoint: null work buffer (crb_rk4_adjoint_work_bytes)");
-    if (n_steps < 0) return fail(CRB_EINVAL, "crb_step_rk4_adjoint: n_steps must be >= 0");
-    if (every < 1) return fail(CRB_EINVAL, "crb_step_rk4_adjoint: every must be >= 1");
-    if (!(dt > 0)) return fail(CRB_EINVAL, "crb_step_rk4_adjoint: dt must be positive");
-    if (lam == ckpt || lam == work) return fail(CRB_EINVAL, "crb_step_rk4_adjoint: lam must not alias another buffer of the call");
-    if (int rc = need_device(p, "crb_step_rk4_adjoint")) return rc;
+namespace {
+// crb_step_rk4_adjoint and crb_step_rk4_adjoint_params (want_params): the same segments and launches, the
+// latter with the storing sweep and crb_param_grad_kernel after each
+int adjoint_rollout(const char* who_c, const crb_plan* p, const void* ckpt, void* lam, int n_cot, double t0, double dt, int n_steps,
+                    int every, const crb_input_desc* in, const crb_record_desc* rec_bar, const crb_input_cotangent* grad,
+                    bool want_params, const crb_param_cotangent* pgrad, void* work, void* stream) {
+    const std::string who(who_c);
+    if (int rc = adjoint_checks(p, n_cot, who_c)) return rc;
+    if (!ckpt || !lam) return fail(CRB_EINVAL, who + ": null checkpoint buffer or cotangent");
+    if (want_params && (!pgrad || !pgrad->param_bar))
+        return fail(CRB_EINVAL, who + ": null parameter cotangent (crb_param_cotangent.param_bar)");
+    if (!work) return fail(CRB_EINVAL, who + (want_params ? ": null work buffer (crb_rk4_adjoint_params_work_bytes)"
+                                                             : ": null work buffer (crb_rk4_adjoint_work_bytes)"));
+    if (n_steps < 0) return fail(CRB_EINVAL, who + ": n_steps must be >= 0");
+    if (every < 1) return fail(CRB_EINVAL, who + ": every must be >= 1");
+    if (!(dt > 0)) return fail(CRB_EINVAL, who + ": dt must be positive");
+    if (lam == ckpt || lam == work) return fail(CRB_EINVAL, who + ": lam must not alias another buffer of the call");
+    void* const param_bar = want_params ? pgrad->param_bar : nullptr;
+    if (param_bar && (param_bar == lam || param_bar == work || param_bar == ckpt))
+        return fail(CRB_EINVAL, who + ": param_bar must not alias lam, the work buffer or the checkpoints");
+    if (int rc = need_device(p, who_c)) return rc;
     Recording r;
-    if (int rc = decode_record(p, rec_bar, n_steps, true, "crb_step_rk4_adjoint", &r)) return rc;
+    if (int rc = decode_record(p, rec_bar, n_steps, true, who_c, &r)) return rc;
     Forcing f;
-    if (int rc = decode_input(p, in, "crb_step_rk4_adjoint", &f)) return rc;
+    if (int rc = decode_input(p, in, who_c, &f)) return rc;
     void* amp_bar = grad ? grad->amp_bar : nullptr;
     void* f_bar = grad ? grad->f_held_bar : nullptr;
     if (amp_bar && !f.impulse)
-        return fail(CRB_EINVAL, "crb_step_rk4_adjoint: amp_bar needs an impulse input (its amplitude is what it differentiates)");
+        return fail(CRB_EINVAL, who + ": amp_bar needs an impulse input (its amplitude is what it differentiates)");
     const void* bufs[6] = {ckpt, work, amp_bar, f_bar, r.out, f.held};
     for (const void* b : bufs)
-        if (b && b == lam) return fail(CRB_EINVAL, "crb_step_rk4_adjoint: lam must not alias another buffer of the call");
+        if (b && b == lam) return fail(CRB_EINVAL, who + ": lam must not alias another buffer of the call");
     if ((amp_bar && (amp_bar == work || amp_bar == ckpt || amp_bar == f_bar)) || (f_bar && (f_bar == work || f_bar == ckpt)) ||
-        work == ckpt)
-        return fail(CRB_EINVAL, "crb_step_rk4_adjoint: the output and work buffers must not alias each other or the checkpoints");
+        work == ckpt || (param_bar && (param_bar == amp_bar || param_bar == f_bar || param_bar == r.out || param_bar == f.held)))
+        return fail(CRB_EINVAL, who + ": the output and work buffers must not alias each other or the checkpoints");
     if (n_steps == 0) return CRB_OK;
-    if (int rc = ensure_gadj(p, "crb_step_rk4_adjoint")) return rc;
+    if (int rc = ensure_gadj(p, who_c)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int groups = (p->B + p->G - 1) / p->G;
     const size_t sd = state_doubles(p);
     double* const wstates = static_cast<double*>(work);
     double* const wclock = wstates + size_t(every) * 4 * sd;
+    double* const wrbar = wclock + size_t(every);   // (crb_rk4_adjoint_params_work_bytes: after the stage points and the clocks)
     const int nseg = (n_steps + every - 1) / every;
     for (int g = nseg - 1; g >= 0; --g) {
         const int k0 = g * every, n = (n_steps - k0) < every ? (n_steps - k0) : every;
@@ -2586,7 +2597,37 @@ extern "C" int crb_step_rk4_adjoint(const crb_plan* p, const void* ckpt, void* l
         b.amp_bar = static_cast<double*>(amp_bar);
         b.f_bar = static_cast<double*>(f_bar);
         b.step0 = k0;
-        HIP_TRY(crb::launch_adj_backward(k, b, groups, n_cot, p->NT, st));
+        if (!want_params) {
+            HIP_TRY(crb::launch_adj_backward(k, b, groups, n_cot, p->NT, st));
+            continue;
+        }
+        b.rbar = wrbar;
+        b.param_bar = static_cast<double*>(param_bar);
+        HIP_TRY(crb::launch_adj_backward_store(k, b, groups, n_cot, p->NT, st));
+        // 3. the parameter sums of the segment, from its stage points and the sweep's rbar
+        HIP_TRY(crb::launch_param_grad(k, b, groups, n_cot, p->NT, st));
     }
     return CRB_OK;
+}
+}  // namespace
+
+extern "C" int crb_step_rk4_adjoint(const crb_plan* p, const void* ckpt, void* lam, int n_cot, double t0, double dt, int n_steps,
+                                    int every, const crb_input_desc* in, const crb_record_desc* rec_bar,
+                                    const crb_input_cotangent* grad, void* work, void* stream) {
+    return adjoint_rollout("crb_step_rk4_adjoint", p, ckpt, lam, n_cot, t0, dt, n_steps, every, in, rec_bar, grad, false, nullptr,
+                           work, stream);
+}
+
+extern "C" size_t crb_rk4_adjoint_params_work_bytes(const crb_plan* p, int every, int n_cot) {
+    if (!p || every < 1 || n_cot < 1) return 0;
+    return crb_rk4_adjoint_work_bytes(p, every) +
+           size_t(every) * 4 * size_t(n_cot) * size_t(p->B) * size_t(p->n_node) * 4 * sizeof(double);
+}
+
+extern "C" int crb_step_rk4_adjoint_params(const crb_plan* p, const void* ckpt, void* lam, int n_cot, double t0, double dt,
+                                           int n_steps, int every, const crb_input_desc* in, const crb_record_desc* rec_bar,
+                                           const crb_input_cotangent* grad, const crb_param_cotangent* pgrad, void* work,
+                                           void* stream) {
+    return adjoint_rollout("crb_step_rk4_adjoint_params", p, ckpt, lam, n_cot, t0, dt, n_steps, every, in, rec_bar, grad, true,
+                           pgrad, work, stream);
 }

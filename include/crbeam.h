@@ -289,6 +289,37 @@ int crb_step_rk4_adjoint(const crb_plan* plan, const void* ckpt, void* lam, int 
                          int every, const crb_input_desc* input, const crb_record_desc* rec_bar,
                          const crb_input_cotangent* grad, void* work, void* stream);
 
+/* Cotangents of the rod's own parameters, ACCUMULATED by crb_step_rk4_adjoint_params (device, fp64). */
+typedef struct crb_param_cotangent {
+    void* param_bar;   /* device [n_cot][B][n_node][8]; the record of node i: sA, sI of the element left of node i, sD of
+                          node i, gx, gy of the segment of that node's slot, 0, 0, 0 (see crb_step_rk4_adjoint_params) */
+} crb_param_cotangent;
+
+/* Device bytes of the work buffer of crb_step_rk4_adjoint_params: crb_rk4_adjoint_work_bytes(plan, every) +
+ * every * 4 * n_cot * B * n_node * 4 * sizeof(double) -- after the stage points and the clocks, the rbar = M^-T lambda_v of
+ * every stage of one segment, per cotangent.  0 for every < 1 or n_cot < 1. */
+size_t crb_rk4_adjoint_params_work_bytes(const crb_plan* plan, int every, int n_cot);
+
+/* crb_step_rk4_adjoint (the same arguments, the same segments; lam, amp_bar and f_held_bar come out bitwise as there) that
+ * also gives the gradient of the loss with respect to the rod -- what fitting a rod to a recorded trajectory needs, and what
+ * central differences of the scipy.solve_ivp call sites (example_utilities.py:153-159) over rebuilt models
+ * (euler_bernoulli_beam.py:26-109, fluid_forces.py:59-90, gravity_forces.py:104-146) would otherwise give, two rollouts per
+ * parameter.  The right-hand side is linear in every parameter that stays out of the mass matrix, so per stage, with
+ * rbar = M^-T lambda_v:
+ *   sA, sI   -<(rbar_{i-1}, rbar_i), element force with only its EA / only its EI part>: dL/d of RELATIVE scales of EA and EI
+ *            of the element left of node i, at scale 1 (dL/dE = (sA + sI) / E, dL/dI = sI / I)
+ *   sD       rbar_w times the node's drag force: dL/d of a relative scale of the node's factor 0.5 rho_f Cd A_wet
+ *   gx, gy   dL/d of the gravity vector through the segment of the node's slot; the caller sums them over the nodes of a beam
+ * pgrad->param_bar is ACCUMULATED; constrained DOFs contribute nothing; padding nodes, and node 0 of plans without its slot,
+ * hold zeros.  Per segment: the sweep that also stores rbar, then one reduction launch; every sum has a fixed order (no
+ * atomics), so the result is bitwise independent of `every`, and D cotangents in one call are bitwise D calls of one.
+ *   work     crb_rk4_adjoint_params_work_bytes(plan, every, n_cot) device bytes
+ * Not differentiated: length, cross-section area and density (they enter the mass matrix).  CRB_EINVAL for a NULL pgrad,
+ * param_bar or work, or a bad n_cot or every; otherwise the checks, limits and codes of crb_step_rk4_adjoint. */
+int crb_step_rk4_adjoint_params(const crb_plan* plan, const void* ckpt, void* lam, int n_cot, double t0, double dt, int n_steps,
+                                int every, const crb_input_desc* input, const crb_record_desc* rec_bar,
+                                const crb_input_cotangent* grad, const crb_param_cotangent* pgrad, void* work, void* stream);
+
 /* Inverse lists of the gravity index table of beam `beam` (crb_plan_get_slot_tables' grav, reversed), host-only plans too:
  *   seg [n_slots][2][2]: per segment and force component (0 axial / 1 transverse), slot*4+dof of the node DOFs it adds to
  *   phi [n_slots][3][2]: per DOF of a slot, (segment << 1) | half of the segments whose rotation reads it (half: the segment

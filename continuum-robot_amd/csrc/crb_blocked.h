@@ -35,8 +35,68 @@ enum : int {
 // [value][lane] so that a wave reads one value of every lane with one conflict-free access
 __host__ __device__ constexpr int blk_sep_vals(int levels) { return levels * PCR_LEVEL_VALS + BLK_PACK; }
 
+// The wave-uniform table as the kernel holds it: BLK_TAB_REGS fp64 registers per lane, constant k in lane k % BLK_TAB_ROW of
+// EVERY 16-lane row of register k / BLK_TAB_ROW (a DPP row broadcast reads inside the reader's own row, so each of the four
+// rows of a wave carries the whole table); the slots past the table repeat its zero pad.
+constexpr int BLK_TAB_ROW = 16;
+constexpr int BLK_TAB_REGS = (BU_N + BLK_TAB_ROW - 1) / BLK_TAB_ROW;   // 5
+__host__ __device__ constexpr int blk_tab_index(int reg, int lane) {   // the table entry that `lane` holds in register `reg`
+    return BLK_TAB_ROW * reg + (lane & (BLK_TAB_ROW - 1)) < BU_N - 1 ? BLK_TAB_ROW * reg + (lane & (BLK_TAB_ROW - 1)) : BU_N - 1;
+}
+
+#if defined(__HIPCC__)
+// ---- multiply-adds whose wave-uniform constant is a DPP row broadcast of the register table: no load, no SGPR, no wait.
+// gfx950 has exactly one fp64 arithmetic instruction with a DPP source, the VOP2 v_fmac_f64 (d += src0 * src1, src0 through
+// row_newbcast:N = lane N of the reader's row, sign by the source modifier); v_mov_b64 has the same source for a plain copy.
+// The asm is not volatile: it is a pure function of its operands, the compiler may schedule and hoist it.  The compiler
+// does not see the DPP in it and inserts no wait states for one: `tab` must have been written long before (lean_blocked_body).
+// acc -= u[OFF] * x
+template <int OFF, typename T>
+__device__ __forceinline__ void blk_bc_fnma(const T (&tab)[BLK_TAB_REGS], T x, T& acc) {
+    static_assert(OFF >= 0 && OFF < BU_N, "table offset");
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("v_fmac_f64_dpp %0, -%1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
+        : "+v"(acc) : "v"(tab[OFF / BLK_TAB_ROW]), "v"(x), "n"(OFF % BLK_TAB_ROW));
+#else
+    acc -= tab[OFF / BLK_TAB_ROW] * x;
+#endif
+}
+// acc += u[OFF] * x
+template <int OFF, typename T>
+__device__ __forceinline__ void blk_bc_fma(const T (&tab)[BLK_TAB_REGS], T x, T& acc) {
+    static_assert(OFF >= 0 && OFF < BU_N, "table offset");
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
+        : "+v"(acc) : "v"(tab[OFF / BLK_TAB_ROW]), "v"(x), "n"(OFF % BLK_TAB_ROW));
+#else
+    acc += tab[OFF / BLK_TAB_ROW] * x;
+#endif
+}
+// u[OFF] in every lane (for the few products that head a sum: only the multiply-ADD has the broadcast form)
+template <int OFF, typename T>
+__device__ __forceinline__ T blk_bc_copy(const T (&tab)[BLK_TAB_REGS]) {
+    static_assert(OFF >= 0 && OFF < BU_N, "table offset");
+#if defined(__HIP_DEVICE_COMPILE__)
+    T d;
+    asm("v_mov_b64_dpp %0, %1 row_newbcast:%2 row_mask:0xf bank_mask:0xf" : "=v"(d) : "v"(tab[OFF / BLK_TAB_ROW]), "n"(OFF % BLK_TAB_ROW));
+    return d;
+#else
+    return tab[OFF / BLK_TAB_ROW];
+#endif
+}
+// o -= u[OFF .. OFF+4] v, the roundings of blk_sub_mul below: each component one chain of fused multiply-adds
+template <int OFF, typename T>
+__device__ __forceinline__ void blk_bc_sub_mul(const T (&tab)[BLK_TAB_REGS], const T v[3], T o[3]) {
+    blk_bc_fnma<OFF + 0>(tab, v[0], o[0]);
+    blk_bc_fnma<OFF + 1>(tab, v[1], o[1]);
+    blk_bc_fnma<OFF + 2>(tab, v[2], o[1]);
+    blk_bc_fnma<OFF + 3>(tab, v[1], o[2]);
+    blk_bc_fnma<OFF + 4>(tab, v[2], o[2]);
+}
+#endif
+
 // ---- apply a 5-pack to a 3-vector [u, w, phi]
-// (P: a plain or a constant-address-space pointer -- the kernel reads the table through scalar loads)
+// (P: a plain or a constant-address-space pointer)
 template <typename T, typename P = const T*>
 __host__ __device__ __forceinline__ void blk_mul(P m, const T v[3], T o[3]) {
     o[0] = m[0] * v[0];

@@ -215,15 +215,27 @@ __device__ __forceinline__ void lean_rhs(const ElemCoef<T>& ec, T dragc, bool co
 //   offsets instead of 24 DPP moves; the pads, zeroed once, are the 0 that a bound_ctrl shift brings in past the root and the
 //   tip, so the results are bitwise those of the shifts).  No barrier in the step loop: a wave's LDS accesses execute in order.
 //   A workgroup is four independent beam walkers.
-// Wave-uniform constants (the interior's factors, W_L / W_R, A_s / C_s, the element pack, the drag factor) are read by scalar
-// loads through a pointer laundered per stage, so that they are not held across the loop; the per-lane separator tables sit
-// in LDS (shared by the four waves, [value pair][lane] records) and are read level by level.  LS = separator levels.
+// The solve's 75 wave-uniform constants (the interior's factors, W_L / W_R, A_s / C_s) sit in five fp64 registers per lane,
+// loaded once per launch: constant k in lane k % 16 of every 16-lane row of register k / 16 (crb_blocked.h: BLK_TAB_*).  The 66
+// multiply-adds per stage that use one take it as the DPP row-broadcast source of v_fmac_f64 (blk_bc_fma / blk_bc_fnma: no
+// load, no SGPR, no wait); the nine products that head a sum multiply by a copy made before the walk loop (blk_bc_copy, 18
+// registers).  Read as scalar loads pack by pack they were 31 of the stage's 38 s_load and 15 of its 21 full lgkmcnt(0) drains,
+// each exposing most of a scalar load's latency on the wave's serial chain; held in SGPRs they overflow the scalar file.  Each sum keeps
+// the order the compiler gave the scalar-operand form, so the results are bitwise those of blk_interior_solve's roundings.
+// Checked in the ISA of this kernel (a DPP inside asm gets no wait states from the compiler): the five table pairs and the
+// nine copies are written by nothing but their loads / moves ahead of the walk loop; no VALU instruction of the step loop
+// writes EXEC (no v_cmpx, no v_readlane into it); the step loop has 264 v_fmac_f64_dpp per step and no scalar load of the table.
+// The element pack, the drag factor and the launch parameters stay scalar loads through the kernarg pointer laundered per
+// stage (they feed VOP3 instructions); the per-lane separator tables sit in LDS (shared by the four waves, [value pair][lane]
+// records) and are read level by level.  LS = separator levels.
 // Measured at 4096 x 256: 549 vector instructions per beam and stage against 868 (4 waves x 217), 16.3 against
 // 27.1 us per step with every level by DPP; the strip takes that to 501 and 16.53 to 16.15 us per step (strides 2 and 4 through
 // the strip: 477 and 16.17).  The impulse behind scalar branches instead of a selector FMA per component, and RK4 sums started by
 // stage 0: 410 -> 393 executed fp64 instructions per stage, no SGPR spill left (52 before), 16.25 -> 15.41 us per step (the shipped
 // library against its parent's, one box, alternating); 210 VGPRs, no scratch, two waves per SIMD.  DESIGN.md §4 has the
-// stage's fp64 budget per phase.  The next beam's state is not prefetched as in the one-node-per-lane
+// stage's fp64 budget per phase.  The uniform constants as row broadcasts and the first level's table read under the interior
+// solve: 38 -> 7.5 scalar loads and 21 -> 6.5 full drains per stage, 238 VGPRs, 15.21 -> 15.00 us per step (-1.35 %; the
+// broadcasts alone -0.7 %), outputs bitwise equal (DESIGN.md §4 has the probe of the instruction and the variants).  The next beam's state is not prefetched as in the one-node-per-lane
 // form: four nodes' records are 48 more registers than the budget of two waves per SIMD holds.
 constexpr int BLK_STRIP_PAD = 4;   // the stride of the separator level that goes through the wave's LDS strip (the third)
 constexpr int BLK_STRIP_W = BLK_STRIP_PAD + BLK_LANES + BLK_STRIP_PAD;
@@ -237,11 +249,9 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
     static_assert(LS == 3 && (1 << (LS - 1)) == BLK_STRIP_PAD, "the strip carries the third separator level, stride 4");
     constexpr int NP = BLK_NPL, NV = blk_sep_vals(LS), NV2 = (NV + 1) / 2;
 #if defined(__HIP_DEVICE_COMPILE__)
-    typedef const __attribute__((address_space(4))) T* CP;
     typedef const __attribute__((address_space(4))) SlotConst<T>* CS;
 #define CRB_BFRESH(ptr) asm volatile("" : "+s"(ptr))
 #else
-    typedef const T* CP;
     typedef const SlotConst<T>* CS;
 #define CRB_BFRESH(ptr) (void)(ptr)
 #endif
@@ -273,6 +283,14 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
     typedef volatile T* SP;
 #endif
     const SP strip = (SP)(strips + wave * 3 * BLK_STRIP_W + BLK_STRIP_PAD + lane);
+    // the wave-uniform table, once per launch: constant k in lane k % 16 of every row of tab[k / 16] (crb_blocked.h), and
+    // broadcast copies of the nine constants that multiply without adding (the first product of each blk_mul sum)
+    T tab[BLK_TAB_REGS];
+#pragma unroll
+    for (int i = 0; i < BLK_TAB_REGS; ++i) tab[i] = p.blocked[blk_tab_index(i, lane)];
+    const T cD2[3] = {blk_bc_copy<BU_D2>(tab), blk_bc_copy<BU_D2 + 2>(tab), blk_bc_copy<BU_D2 + 4>(tab)};
+    const T cD1[3] = {blk_bc_copy<BU_U1>(tab), blk_bc_copy<BU_D1 + 2>(tab), blk_bc_copy<BU_D1 + 4>(tab)};
+    const T cD0[3] = {blk_bc_copy<BU_U0>(tab), blk_bc_copy<BU_D0 + 2>(tab), blk_bc_copy<BU_D0 + 4>(tab)};
     __syncthreads();   // (the only barrier: the waves walk over their beams independently from here on)
     const int n_groups = (p.B + 3) / 4;
     for (int grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
@@ -328,7 +346,6 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                 const bool imp_on = ts < q.duration;
                 const T w = (s == 0 || s == 3) ? T(1) : T(2);
                 const T cs = (s == 2) ? dt : hdt;
-                const CP U = (CP)q.blocked;
                 const CS SC = (CS)q.slot;
                 T ec[6];
 #pragma unroll
@@ -403,34 +420,52 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                         r[k][c] = h - ((k + 1 < NP) ? fl[k + 1][c] : flR);
                     }
                 }
-                // -- mass solve: interior, separator right-hand side, separator levels, back substitution
-                // (at: the table behind a pointer laundered on the value that the pack is applied to, so that a pack's scalar
-                //  loads are issued where it is needed: loaded all at once, the 75 constants overflow the scalar file)
-                auto at = [&](int off, T dep) { CP q = U; asm volatile("" : "+s"(q) : "v"(dep)); return q + off; };
+                // -- mass solve: interior, separator right-hand side, separator levels, back substitution.  Every wave-uniform
+                //    constant is a row broadcast of `tab` inside a multiply-add (66 per stage), or one of the nine copies; each
+                //    sum in the order the compiler contracts blk_interior_solve's (crb_blocked.h) with scalar operands: a blk_mul
+                //    row is fma(m1, v1, m2 v2), and the axial row of a blk_mul / blk_sub_mul pair is fma(d, v, -(u w))
                 T y[3][3], z1[3], z2[3], g[3], y0R[3];
+                // (the first separator level's table is requested here, under the interior solve, which has no wait of its own:
+                //  the lane index is laundered through the right-hand side, so that the reads are issued where the solve starts)
+                int li = lane;
+                T cf0[PCR_LEVEL_VALS];
+                asm volatile("" : "+v"(li) : "v"(r[0][0]));
+#pragma unroll
+                for (int i = 0; i < PCR_LEVEL_VALS; i += 2) {
+                    const pair2 e = sepL[(i / 2) * 64 + li];
+                    cf0[i] = e[0]; cf0[i + 1] = e[1];
+                }
 #pragma unroll
                 for (int c = 0; c < 3; ++c) { z1[c] = r[1][c]; z2[c] = r[2][c]; g[c] = r[NP - 1][c]; }
-                blk_sub_mul<T, CP>(at(BU_L1, r[0][1]), r[0], z1);
-                blk_sub_mul<T, CP>(at(BU_L2, z1[1]), z1, z2);
-                blk_mul<T, CP>(at(BU_D2, z2[1]), z2, y[2]);
-                blk_mul<T, CP>(at(BU_D1, z2[1]), z1, y[1]);
-                blk_sub_mul<T, CP>(at(BU_U1, y[2][1]), y[2], y[1]);
-                blk_mul<T, CP>(at(BU_D0, y[1][1]), r[0], y[0]);
-                blk_sub_mul<T, CP>(at(BU_U0, y[1][1]), y[1], y[0]);
+                blk_bc_sub_mul<BU_L1>(tab, r[0], z1);
+                blk_bc_sub_mul<BU_L2>(tab, z1, z2);
+                y[2][0] = cD2[0] * z2[0];                       // y_2 = D2 z_2
+                y[2][1] = cD2[1] * z2[2]; blk_bc_fma<BU_D2 + 1>(tab, z2[1], y[2][1]);
+                y[2][2] = cD2[2] * z2[2]; blk_bc_fma<BU_D2 + 3>(tab, z2[1], y[2][2]);
+                y[1][0] = -(cD1[0] * y[2][0]); blk_bc_fma<BU_D1>(tab, z1[0], y[1][0]);   // y_1 = D1 z_1 - U1 y_2
+                y[1][1] = cD1[1] * z1[2]; blk_bc_fma<BU_D1 + 1>(tab, z1[1], y[1][1]);
+                y[1][2] = cD1[2] * z1[2]; blk_bc_fma<BU_D1 + 3>(tab, z1[1], y[1][2]);
+                blk_bc_fnma<BU_U1 + 1>(tab, y[2][1], y[1][1]); blk_bc_fnma<BU_U1 + 2>(tab, y[2][2], y[1][1]);
+                blk_bc_fnma<BU_U1 + 3>(tab, y[2][1], y[1][2]); blk_bc_fnma<BU_U1 + 4>(tab, y[2][2], y[1][2]);
+                y[0][0] = -(cD0[0] * y[1][0]); blk_bc_fma<BU_D0>(tab, r[0][0], y[0][0]);   // y_0 = D0 r_0 - U0 y_1
+                y[0][1] = cD0[1] * r[0][2]; blk_bc_fma<BU_D0 + 1>(tab, r[0][1], y[0][1]);
+                y[0][2] = cD0[2] * r[0][2]; blk_bc_fma<BU_D0 + 3>(tab, r[0][1], y[0][2]);
+                blk_bc_fnma<BU_U0 + 1>(tab, y[1][1], y[0][1]); blk_bc_fnma<BU_U0 + 2>(tab, y[1][2], y[0][1]);
+                blk_bc_fnma<BU_U0 + 3>(tab, y[1][1], y[0][2]); blk_bc_fnma<BU_U0 + 4>(tab, y[1][2], y[0][2]);
 #pragma unroll
                 for (int c = 0; c < 3; ++c) y0R[c] = dpp_from_higher(y[0][c]);
-                blk_sub_mul<T, CP>(at(BU_AS, y[2][1]), y[2], g);
-                blk_sub_mul<T, CP>(at(BU_CS, y0R[1]), y0R, g);
-                int li = lane;
+                blk_bc_sub_mul<BU_AS>(tab, y[2], g);
+                blk_bc_sub_mul<BU_CS>(tab, y0R, g);
 #pragma unroll
                 for (int l = 0; l < LS; ++l) {
-                    // (the lane index is laundered through this level's input, so that the table loads of a level are issued
-                    //  when it starts instead of all at the top of the loop: the tables would otherwise take 70 registers)
+                    // (the lane index is laundered through this level's input, so that the table loads of the later levels are
+                    //  issued when they start instead of all at the top of the loop: the tables would otherwise take 70 registers)
                     asm volatile("" : "+v"(li) : "v"(g[0]));
                     T cf[PCR_LEVEL_VALS];
 #pragma unroll
                     for (int i = 0; i < PCR_LEVEL_VALS; i += 2) {
                         const int v = l * PCR_LEVEL_VALS + i;   // (even: PCR_LEVEL_VALS is)
+                        if (l == 0) { cf[i] = cf0[i]; cf[i + 1] = cf0[i + 1]; continue; }
                         const pair2 e = sepL[(v / 2) * 64 + li];
                         cf[i] = e[0]; cf[i + 1] = e[1];
                     }
@@ -462,12 +497,16 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                 for (int c = 0; c < 3; ++c) xsL[c] = dpp_from_lower(xs[c]);
                 T a[NP][3];
 #pragma unroll
-                for (int k = 0; k < NP - 1; ++k) {
+                for (int k = 0; k < NP - 1; ++k)
 #pragma unroll
                     for (int c = 0; c < 3; ++c) a[k][c] = y[k][c];
-                    blk_sub_mul<T, CP>(at(BU_WL + BLK_PACK * k, k ? a[k - 1][1] : xsL[1]), xsL, a[k]);
-                    blk_sub_mul<T, CP>(at(BU_WR + BLK_PACK * k, a[k][1]), xs, a[k]);
-                }
+                static_assert(NP == 4, "three interior nodes, written out: the table offsets are template arguments");
+                blk_bc_sub_mul<BU_WL>(tab, xsL, a[0]);
+                blk_bc_sub_mul<BU_WR>(tab, xs, a[0]);
+                blk_bc_sub_mul<BU_WL + BLK_PACK>(tab, xsL, a[1]);
+                blk_bc_sub_mul<BU_WR + BLK_PACK>(tab, xs, a[1]);
+                blk_bc_sub_mul<BU_WL + 2 * BLK_PACK>(tab, xsL, a[2]);
+                blk_bc_sub_mul<BU_WR + 2 * BLK_PACK>(tab, xs, a[2]);
 #pragma unroll
                 for (int c = 0; c < 3; ++c) a[NP - 1][c] = xs[c];
                 // -- RK4 bookkeeping

@@ -235,7 +235,15 @@ __device__ __forceinline__ void lean_rhs(const ElemCoef<T>& ec, T dragc, bool co
 // library against its parent's, one box, alternating); 210 VGPRs, no scratch, two waves per SIMD.  DESIGN.md §4 has the
 // stage's fp64 budget per phase.  The uniform constants as row broadcasts and the first level's table read under the interior
 // solve: 38 -> 7.5 scalar loads and 21 -> 6.5 full drains per stage, 238 VGPRs, 15.21 -> 15.00 us per step (-1.35 %; the
-// broadcasts alone -0.7 %), outputs bitwise equal (DESIGN.md §4 has the probe of the instruction and the variants).  The next beam's state is not prefetched as in the one-node-per-lane
+// broadcasts alone -0.7 %), outputs bitwise equal (DESIGN.md §4 has the probe of the instruction and the variants).
+// The nonlinear instance takes the element's axial pair regrouped (crb_math.h: elem_force_nonlinear_regrouped): an element
+// hands out f2 = cA1 E and cA1 W with f1 + f2 = cA1 W, a node's axial right-hand side is (f2(k+1) - f2(k)) - cA1 W(k+1), and
+// only the lane's first element forms f1 = cA1 W - f2 itself, for lane-1's last node.  10 fp64 instructions per element and
+// node instead of 14 in the source, 1617 -> 1557 emitted per step (15 per stage), 240 VGPRs, 98 SGPRs, no spill, no scratch;
+// the roundings of the axial right-hand side change in order (not in number or size), so this instance is no longer bitwise
+// its parent's -- it agrees with it, with the one-node-per-lane stepper and with the oracle to rounding (DESIGN.md §4 has
+// the figures).  The linear instance and every other kernel keep their code line for line.
+// The next beam's state is not prefetched as in the one-node-per-lane
 // form: four nodes' records are 48 more registers than the budget of two waves per SIMD holds.
 constexpr int BLK_STRIP_PAD = 4;   // the stride of the separator level that goes through the wave's LDS strip (the third)
 constexpr int BLK_STRIP_W = BLK_STRIP_PAD + BLK_LANES + BLK_STRIP_PAD;
@@ -248,6 +256,9 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
     static_assert(sizeof(T) == 8, "the blocked stepper is fp64");
     static_assert(LS == 3 && (1 << (LS - 1)) == BLK_STRIP_PAD, "the strip carries the third separator level, stride 4");
     constexpr int NP = BLK_NPL, NV = blk_sep_vals(LS), NV2 = (NV + 1) / 2;
+    // the nonlinear element's axial pair regrouped (crb_math.h: elem_force_nonlinear_regrouped), 10 fp64 instructions per element
+    // and node instead of 14; the literal polynomial (-DCRB_LITERAL_POLY=1) has no such form
+    constexpr bool REGROUP = EM == EM_NONLINEAR && !CRB_LITERAL_POLY;
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef const __attribute__((address_space(4))) SlotConst<T>* CS;
 #define CRB_BFRESH(ptr) asm volatile("" : "+s"(ptr))
@@ -367,18 +378,33 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                 CRB_SETPRIO(P_FORCE);
                 T fl[NP][3], r[NP][3];
                 T fr[NP][3];
+                T f2[NP], cW[NP];   // (REGROUP: the axial pair as f2 and W, crb_math.h)
 #pragma unroll
                 for (int k = 0; k < NP; ++k) {
-                    if (EM == EM_NONLINEAR) elem_force_nonlinear<T>(ec, k ? sq[k - 1] : qL, sq[k], false, fl[k], fr[k]);
+                    if constexpr (REGROUP) {
+                        const ElemForceRegrouped<T> e = elem_force_nonlinear_regrouped<T>(ec, k ? sq[k - 1] : qL, sq[k]);
+                        f2[k] = e.f2; cW[k] = ec[1] * e.W;
+                        fl[k][1] = e.f3; fr[k][1] = -e.f3; fl[k][2] = e.m_left; fr[k][2] = e.m_right;
+                    } else if (EM == EM_NONLINEAR) elem_force_nonlinear<T>(ec, k ? sq[k - 1] : qL, sq[k], false, fl[k], fr[k]);
                     else elem_force_linear<T>(ec, k ? sq[k - 1] : qL, sq[k], fl[k], fr[k]);
                 }
-                // -- the impulse: fr - amp on its one (node, dof), so that r = (amp - fr) - fl there and -fr - fl everywhere else,
+                if constexpr (REGROUP) {
+                    // the axial right-hand side less its last product, negated: fr[k][0] enters r as -fr[k][0] below, as the
+                    // right half f2(k) does in the other form, so the impulse block acts on it with the same sign.  The last
+                    // node's is the explicit left half f1 = cA1 W - f2 of lane+1's first element (one per lane, not four)
+                    fl[0][0] = cW[0] - f2[0];
+#pragma unroll
+                    for (int k = 0; k + 1 < NP; ++k) fr[k][0] = f2[k] - f2[k + 1];
+                    fr[NP - 1][0] = dpp_from_higher(fl[0][0]);   // (-f2(3) - this below: the impulse's -amp lands on either term alike)
+                }
+                // -- the impulse: fr - amp on its one (node, dof), so that r = (amp - fr) - fl there and -fr - fl everywhere else
+                //    (REGROUP, axial dof: fr[k][0] is the difference / the shifted-in f1 above, entering r with the same sign),
                 //    instead of one r = sel * amp - fr per component (12 fp64 FMAs per stage for one lane's one component).  The
                 //    selector is wave-uniform, so the choice is scalar compares and branches around ONE v_add_f64; they are
                 //    written as an opaque block per node because a C++ branch here splits the stage's straight-line code, which
                 //    the scheduler then no longer interleaves with the solve (measured: 50 spilled VGPRs).  No lane shift inside.
-                //    After a compiler upgrade re-check with `make resource-usage`: this kernel at 0 SGPR spills, <= 256 VGPRs, no
-                //    scratch.  The block can go back to the C++ form of the host branch below once that no longer splits the
+                //    After a compiler upgrade re-check with `make resource-usage`: this kernel at 0 SGPR spills, <= 256 VGPRs
+                //    (240 with the regrouped axial pair, 98 SGPRs), no scratch.  The block can go back to the C++ form of the host branch below once that no longer splits the
                 //    schedule (same resource figures, same step time).
                 {
                     const int kon = imp_on ? kimp : -1, dof = q.imp_dof;
@@ -412,6 +438,11 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                 // -- right-hand side: the left half of the lane's first element belongs to lane-1's last node (0 past the tip)
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
+                    if (REGROUP && c == 0) {   // r_u[k] = (f2(k+1) - f2(k)) - cA1 W(k+1); the last node's -f2(3) - f1 of lane+1
+#pragma unroll
+                        for (int k = 0; k < NP; ++k) r[k][0] = (k + 1 < NP) ? (-fr[k][0] - cW[k + 1]) : (-f2[k] - fr[k][0]);
+                        continue;
+                    }
                     const T flR = dpp_from_higher(fl[0][c]);
 #pragma unroll
                     for (int k = 0; k < NP; ++k) {

@@ -189,6 +189,57 @@ CRB_HD void elem_force_nonlinear_sym(const T* c, const T ql[3], const T qr[3], b
     fr[2] = X - Y;
 }
 
+// The symmetric form again, for a caller that assembles the node right-hand sides of a CHAIN of elements itself (the
+// blocked stepper, crb_lean.h), with the axial pair regrouped.  For the shipped f1 (corrected == false) two identities hold
+// exactly in real arithmetic:
+//   P + dw T0 = s^2/15 - (s dw)/10 - p/6 + 0.6 dw^2        (s dw is there already: R uses it)
+//   f1 + f2   = cA1 u2 (L - T0) = cA1 u2 (L + 0.05 s - 0.6 dw)
+// so an element hands out  f2 = cA1 E,  E = s^2/15 - L du - (s dw)/10 - p/6 + 0.6 dw^2   (5 flops)  and
+// W = u2 (L + 0.05 s - 0.6 dw)   (3 flops),  and the axial right-hand side of the node between elements k and k+1 is
+//   -f2(k) - f1(k+1) = (f2(k+1) - f2(k)) - cA1 W(k+1)      (2 flops)
+// 10 flops per element and node against 14 (T0 2, P 4, f2 3, f1 4, the sum 1).  Where f1 itself is wanted it is
+// cA1 W - f2.  The roundings differ from elem_force_nonlinear_sym's in order, not in number or size: both carry errors of
+// eps cA1 L |u|, the size of the node's own axial force (tests/test_axial_regrouped_cpu.py bounds both against exact
+// rational arithmetic).  f3 and the rotation pair fl[2] / fr[2] are elem_force_nonlinear_sym's, operation by operation.
+// There is no corrected form: with f1 = -f2 nothing is shared and elem_force_nonlinear_sym is the cheaper one.
+template <typename T>
+struct ElemForceRegrouped {
+    T f2, W, f3, m_left, m_right;   // f2, W as above; f3 (on w1; -f3 on w2); the moments on th1 and th2
+};
+template <typename T>
+CRB_HD ElemForceRegrouped<T> elem_force_nonlinear_regrouped(const T* c, const T ql[3], const T qr[3]) {
+    const T L = c[0], cA1 = c[1], cA3 = c[2], cD3 = c[3], cA4 = c[4], cD4 = c[5];
+    const T u1 = ql[0], u2 = qr[0];
+    const T a = ql[2] * L, b = qr[2] * L;
+    const T du = u1 - u2, dw = ql[1] - qr[1];
+    const T s = a + b, d = a - b, p = a * b;
+    const T s2 = s * s, dw2 = dw * dw, Ldu = L * du, sdw = s * dw;
+
+    T E = T(1.0 / 15.0) * s2 - Ldu;
+    E = E - T(0.1) * sdw;
+    E = E - T(1.0 / 6.0) * p;
+    E = E + T(0.6) * dw2;
+    T LT = L + T(0.05) * s;
+    LT = LT - T(0.6) * dw;
+
+    const T P3 = s * (T(1.0 / 28.0) * (s2 - T(6.0) * p) + Ldu - T(27.0 / 7.0) * dw2) +
+                 dw * (T(9.0 / 7.0) * (s2 - T(2.0) * p) - T(12.0) * Ldu + T(72.0 / 7.0) * dw2);
+    const T g = T(3.0) * s - T(6.0) * dw;
+    const T S = s * (T(1.0 / 40.0) * s2 - T(11.0 / 140.0) * p - T(0.1) * Ldu + T(9.0 / 70.0) * dw2) +
+                dw * (T(0.2) * Ldu - T(3.0 / 70.0) * p - T(9.0 / 35.0) * dw2);
+    const T R = T(9.0 / 280.0) * s2 - T(0.05) * p + T(3.0 / 140.0) * sdw - T(1.0 / 6.0) * Ldu + T(9.0 / 70.0) * dw2;
+    const T X = cA4 * S + cD4 * g;
+    const T Y = d * (cA4 * R + cD4);
+
+    ElemForceRegrouped<T> o;
+    o.f2 = cA1 * E;
+    o.W = u2 * LT;
+    o.f3 = cA3 * P3 - cD3 * g;
+    o.m_left = X + Y;
+    o.m_right = X - Y;
+    return o;
+}
+
 #ifndef CRB_LITERAL_POLY
 #define CRB_LITERAL_POLY 0
 #endif

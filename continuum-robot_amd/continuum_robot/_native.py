@@ -72,6 +72,12 @@ class InputCotangent(C.Structure):
     _fields_ = [("amp_bar", C.c_void_p), ("f_held_bar", C.c_void_p)]
 
 
+class InputSchedule(C.Structure):
+    """crb_input_schedule: a piecewise-constant control sequence, device [n_intervals][B][n_node][4], each vector held for
+    ``hold`` RK4 steps"""
+    _fields_ = [("f_sched", C.c_void_p), ("n_intervals", C.c_int32), ("hold", C.c_int32)]
+
+
 class ParamCotangent(C.Structure):
     """crb_param_cotangent: accumulated cotangents of the rod's parameters, device [n_cot][B][n_node][8]"""
     _fields_ = [("param_bar", C.c_void_p)]
@@ -177,6 +183,18 @@ def load():
                                               C.POINTER(RecordDesc), C.POINTER(InputCotangent), C.POINTER(ParamCotangent), vp,
                                               vp]
     L.crb_plan_get_grav_transpose.argtypes = [vp, i32, vp, vp, vp]
+    sched = C.POINTER(InputSchedule)
+    L.crb_step_rk4_sched.argtypes = [vp, vp, C.c_double, C.c_double, i32, C.POINTER(InputDesc), sched, C.POINTER(RecordDesc),
+                                     _dp, vp]
+    L.crb_step_rk4_tangent_sched.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, i32, C.POINTER(InputDesc),
+                                             C.POINTER(InputTangent), sched, vp, _dp, vp]
+    L.crb_step_rk4_checkpoint_sched.argtypes = [vp, vp, C.c_double, C.c_double, i32, i32, C.POINTER(InputDesc), sched,
+                                                C.POINTER(RecordDesc), vp, _dp, vp]
+    L.crb_step_rk4_adjoint_sched.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, i32, i32, C.POINTER(InputDesc),
+                                             C.POINTER(RecordDesc), C.POINTER(InputCotangent), sched, vp, vp, vp]
+    L.crb_step_rk4_adjoint_params_sched.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, i32, i32, C.POINTER(InputDesc),
+                                                    C.POINTER(RecordDesc), C.POINTER(InputCotangent),
+                                                    C.POINTER(ParamCotangent), sched, vp, vp, vp]
     L.crb_step_rk4_feedback.argtypes = [vp, vp, C.c_double, C.c_double, i32, vp, vp, C.POINTER(InputDesc), vp,
                                         C.POINTER(C.c_double), vp]
     _lib = L

@@ -33,6 +33,15 @@ _PARAM = {"u": 0, "w": 1, "phi": 2}
 STATIC_RTOL = 1e-6
 
 
+class ControlSchedule(NamedTuple):
+    """A piecewise-constant control sequence for the RK4 rollout family (crb_input_schedule): ``control`` reduced [K, B, n],
+    vector k held for RK4 steps k * hold .. (k + 1) * hold - 1 of the call.  ``step``, ``step_adjoint_params`` and ``rollout``
+    take it as ``control=`` / ``control_hold=``; every method of the family -- ``step_tangent`` and ``step_adjoint`` this way
+    only -- takes it in place of a held force, ``held_force=ControlSchedule(U, hold)``."""
+    control: object
+    hold: int
+
+
 class StaticSolution(NamedTuple):
     """Result of BeamEnsemble.solve_static: reduced positions [B, n], and per beam whether it converged, the Newton
     iterations it used (-1 not converged, -2 non-finite) and its final scaled residual."""
@@ -257,6 +266,11 @@ class BeamEnsemble:
     def _ptr(t):
         return C.c_void_p(t.data_ptr()) if t is not None else None
 
+    @staticmethod
+    def _ref(struct):
+        """an optional descriptor struct of a library call by reference (None = NULL)"""
+        return C.byref(struct) if struct is not None else None
+
     def reduced_index(self, node: int, param: str, beam: int = 0) -> int:
         """Reduced position index of (node, 'u'|'w'|'phi') in beam ``beam``; KeyError when constrained or absent
         (reference: EulerBernoulliBeam.get_dof_index, euler_bernoulli_beam.py:404-420)."""
@@ -400,6 +414,38 @@ class BeamEnsemble:
         samples = torch.zeros((self.n_beams, n_samples), dtype=self.dtype, device=self.device)
         return nat.RecordDesc(int(vel), int(node), _PARAM[param[1:-3] if vel else param], int(every), samples.data_ptr()), samples
 
+    def _control(self, held_force, control, control_hold, n_steps, who):
+        """The held force or the control schedule of a call of the RK4 rollout family: (held_force, None) or
+        (None, (control [K, B, n] on the device, hold)).  A schedule comes as ``control`` / ``control_hold`` or as
+        ``held_force=ControlSchedule(control, hold)``."""
+        if isinstance(held_force, ControlSchedule):
+            if control is not None or control_hold is not None:
+                raise ValueError(f"{who}: a ControlSchedule as held_force and control= are given together")
+            held_force, control, control_hold = None, held_force.control, held_force.hold
+        if control is None:
+            if control_hold is not None:
+                raise ValueError(f"{who}: control_hold needs control")
+            return held_force, None
+        if held_force is not None:
+            raise ValueError(f"{who}: control and held_force are given together (a schedule takes the held force's place)")
+        if control_hold is None or int(control_hold) != control_hold or int(control_hold) < 1:
+            raise ValueError(f"{who}: control_hold must be an integer >= 1 (RK4 steps per interval)")
+        U = torch.as_tensor(control, dtype=self.dtype, device=self.device)
+        if U.dim() != 3 or tuple(U.shape[1:]) != (self.n_beams, self.n) or U.shape[0] < 1:
+            raise ValueError(f"{who}: control must be [K >= 1, {self.n_beams}, {self.n}], got {tuple(U.shape)}")
+        if int(n_steps) > U.shape[0] * int(control_hold):
+            raise ValueError(f"{who}: n_steps = {int(n_steps)} exceeds K * control_hold = {U.shape[0]} * {int(control_hold)}")
+        return None, (U, int(control_hold))
+
+    def _sched_desc(self, sch):
+        """The crb_input_schedule of (control [K, B, n], hold) and its packed device buffer [K, B, n_node, 4] (one scatter for
+        the whole sequence; it must outlive the asynchronous launch); (None, None) for None"""
+        if sch is None:
+            return None, None
+        U, hold = sch
+        packed = self._pack_dirs(U.detach().contiguous(), False)
+        return nat.InputSchedule(packed.data_ptr(), int(U.shape[0]), int(hold)), packed
+
     # ------------------------------------------------------------------ the hot path
     def internal_force(self, q_red) -> torch.Tensor:
         """k(q) for every beam, reduced [B, n]."""
@@ -487,29 +533,36 @@ class BeamEnsemble:
         return self.unpack_state(self.rhs_device(x, u))
 
     def step(self, n_steps: int, dt: float, impulse_amp=None, impulse_duration: float = 0.01,
-             impulse_index: int = -2, held_force=None, t0: Optional[float] = None, record=None, record_every: int = 1):
+             impulse_index: int = -2, held_force=None, t0: Optional[float] = None, record=None, record_every: int = 1,
+             control=None, control_hold: Optional[int] = None):
         """Advance the resident state by ``n_steps`` RK4 steps in one kernel launch.
 
         impulse_amp    per-beam amplitudes [B] of the examples' forcing: that value on reduced
                        position index ``impulse_index`` (-2 = tip w, example_utilities.py:147)
                        while t < impulse_duration
         held_force     reduced [B, n] generalised force held constant over the call
+        control        reduced [K, B, n] control sequence, vector k held for ``control_hold`` steps (step i of the call applies
+                       control[i // control_hold]; n_steps <= K * control_hold); switched inside the kernel, still one
+                       launch, bitwise the chain of one call per interval with ``held_force=control[k]``.  Not together with
+                       ``held_force``.
         record         (node, 'u'|'w'|'phi'|'du_dt'|'dw_dt'|'dphi_dt'): sample that DOF on the device after
                        every ``record_every``-th step (the t_eval output of the reference's solve_ivp
                        calls); the call then returns (clock, samples[B, n_steps // record_every]).
                        "all": whole-state snapshots instead, (clock, snaps[n_rec, B, 2, n_node, 4])
         Returns the clock after the call (accumulated by addition, as the oracle does).
         """
+        held_force, sch = self._control(held_force, control, control_hold, n_steps, "step")
         if t0 is not None:
             self.time = float(t0)
         desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index, held_force)
         rec, samples = self._record_desc(record, n_steps, record_every)
         keep.append(samples)
         t_end = C.c_double(0.0)
-        with self._on_device():
-            nat.check(self._lib.crb_step_rk4_rec(self.plan.h, self._ptr(self.state), self.time, float(dt), int(n_steps),
-                                                 C.byref(desc), C.byref(rec) if rec is not None else None,
-                                                 C.byref(t_end), self._stream()))
+        sd, packed = self._sched_desc(sch)
+        keep.append(packed)
+        with self._on_device():   # (without a schedule, sd None, this is crb_step_rk4_rec)
+            nat.check(self._lib.crb_step_rk4_sched(self.plan.h, self._ptr(self.state), self.time, float(dt), int(n_steps),
+                                                   C.byref(desc), self._ref(sd), self._ref(rec), C.byref(t_end), self._stream()))
         self._keep = keep  # device buffers must outlive the asynchronous launch
         self.time = t_end.value
         return (self.time, samples) if record is not None else self.time
@@ -613,9 +666,12 @@ class BeamEnsemble:
         of ``dx0_red`` ([B, 2n] or D directions [D, B, 2n], one launch).  An identity batch of seeds (D = 2n) gives the
         state-transition matrix.  ``d_impulse_amp`` [B] / [D, B] and ``d_held_force`` [B, n] / [D, B, n] are the tangents of
         ``impulse_amp`` and ``held_force`` (None = 0; a [B] / [B, n] tangent is used for every direction).  The derivative is
-        that of the discrete RK4 map itself, exact.  fp64 ensembles only."""
+        that of the discrete RK4 map itself, exact.  fp64 ensembles only.
+        ``held_force=ControlSchedule(U, hold)`` runs a control sequence U [K, B, n] as step(control=U, control_hold=hold)
+        does; ``d_held_force`` is then its tangent, [K, B, n] or [D, K, B, n]."""
         dx, single = self._dirs(dx0_red, 2 * self.n, "step_tangent: dx0_red")
         D = dx.shape[0]
+        held_force, sch = self._control(held_force, None, None, n_steps, "step_tangent")
         t_start = self.time if t0 is None else float(t0)   # (``time`` moves only when the launch is accepted)
         if d_impulse_amp is not None and impulse_amp is None:
             impulse_amp = torch.zeros((self.n_beams,), dtype=self.dtype, device=self.device)
@@ -629,7 +685,18 @@ class BeamEnsemble:
             da = da.expand(D, self.n_beams).contiguous()
             tan.d_amp = da.data_ptr()
             keep.append(da)
-        if d_held_force is not None:
+        dsd = None
+        if d_held_force is not None and sch is not None:   # the tangent of the schedule, [D, K, B, n_node, 4] in one scatter
+            K = sch[0].shape[0]
+            dU = torch.as_tensor(d_held_force, dtype=self.dtype, device=self.device)
+            if dU.dim() == 3:
+                dU = dU.unsqueeze(0)
+            if dU.dim() != 4 or tuple(dU.shape[1:]) != (K, self.n_beams, self.n) or dU.shape[0] not in (1, D):
+                raise ValueError(f"step_tangent: the tangent of a control schedule must be [{K}, {self.n_beams}, {self.n}] or "
+                                 f"[{D}, {K}, {self.n_beams}, {self.n}], got {tuple(dU.shape)}")
+            dsd = self._pack_dirs(dU.expand(D, -1, -1, -1).reshape(D * K, self.n_beams, self.n), False)
+            keep.append(dsd)
+        elif d_held_force is not None:
             dh, _ = self._dirs(d_held_force, self.n, "step_tangent: d_held_force")
             if dh.shape[0] not in (1, D):
                 raise ValueError("step_tangent: d_held_force must have the directions of dx0_red")
@@ -637,10 +704,12 @@ class BeamEnsemble:
             tan.df_held = dhd.data_ptr()
             keep.append(dhd)
         t_end = C.c_double(0.0)
-        with self._on_device():
-            nat.check(self._lib.crb_step_rk4_tangent(self.plan.h, self._ptr(self.state), self._ptr(dxd), int(D), t_start,
-                                                     float(dt), int(n_steps), C.byref(desc), C.byref(tan), C.byref(t_end),
-                                                     self._stream()))
+        sd, packed = self._sched_desc(sch)
+        keep.append(packed)
+        with self._on_device():   # (without a schedule, sd and dsd None, this is crb_step_rk4_tangent)
+            nat.check(self._lib.crb_step_rk4_tangent_sched(self.plan.h, self._ptr(self.state), self._ptr(dxd), int(D), t_start,
+                                                           float(dt), int(n_steps), C.byref(desc), C.byref(tan), self._ref(sd),
+                                                           self._ptr(dsd), C.byref(t_end), self._stream()))
         self._keep = keep + [dxd]
         self.time = t_end.value
         out = self._unpack_dirs(dxd)
@@ -656,6 +725,11 @@ class BeamEnsemble:
         D = v.shape[0]
         flat = torch.cat([v.reshape(D, -1), torch.zeros((D, 1), dtype=self.dtype, device=self.device)], dim=1)
         return flat[:, fidx].reshape(D, self.n_beams, self.n)
+
+    def _unpack_sched_dirs(self, v: torch.Tensor) -> torch.Tensor:
+        """device layout [D, K, B, n_node, 4] -> reduced [D, K, B, n] (padding entries 0), one gather for all intervals"""
+        D, K = v.shape[0], v.shape[1]
+        return self._unpack_force_dirs(v.reshape((D * K,) + tuple(v.shape[2:]))).reshape(D, K, self.n_beams, self.n)
 
     def rhs_vjp(self, lam_red, x_red=None, u_red=None):
         """Reverse-mode derivative of the RHS (crb_rhs_vjp): returns (xbar, ubar) = ((df/dx)^T lam, (df/du)^T lam) for the
@@ -694,40 +768,45 @@ class BeamEnsemble:
             every -= 1
         return every
 
-    def _checkpoint(self, x, n_steps, dt, t0, desc, every, rec):
-        """crb_step_rk4_checkpoint on the device state ``x`` (advanced in place): returns the checkpoint buffer"""
+    def _checkpoint(self, x, n_steps, dt, t0, desc, every, rec, sd=None):
+        """crb_step_rk4_checkpoint (with the crb_input_schedule ``sd``: crb_step_rk4_checkpoint_sched) on the device state
+        ``x`` (advanced in place): returns the checkpoint buffer"""
         nseg = max(1, -(-int(n_steps) // every))
         ckpt = torch.empty((nseg,) + tuple(self.state.shape), dtype=self.dtype, device=self.device)
         t_end = C.c_double(0.0)
         with self._on_device():
-            nat.check(self._lib.crb_step_rk4_checkpoint(self.plan.h, self._ptr(x), float(t0), float(dt), int(n_steps),
-                                                        int(every), C.byref(desc), C.byref(rec) if rec is not None else None,
-                                                        self._ptr(ckpt), C.byref(t_end), self._stream()))
+            nat.check(self._lib.crb_step_rk4_checkpoint_sched(self.plan.h, self._ptr(x), float(t0), float(dt), int(n_steps),
+                                                              int(every), C.byref(desc), self._ref(sd), self._ref(rec),
+                                                              self._ptr(ckpt), C.byref(t_end), self._stream()))
         return ckpt
 
-    def _adjoint(self, ckpt, lamd, n_steps, dt, t0, desc, every, rec_bar, want_amp, want_params=False):
+    def _adjoint(self, ckpt, lamd, n_steps, dt, t0, desc, every, rec_bar, want_amp, want_params=False, sd=None):
         """crb_step_rk4_adjoint: lamd [D, B, 2, n_node, 4] in place; returns (amp_bar [D, B] or None, f_bar [D, B, n_node, 4]).
-        ``want_params``: crb_step_rk4_adjoint_params instead, and a third return param_bar [D, B, n_node, 8]."""
+        ``want_params``: crb_step_rk4_adjoint_params instead, and a third return param_bar [D, B, n_node, 8].
+        ``sd``: the crb_input_schedule of the forward pass -- the *_sched calls, and f_bar is the schedule's cotangent
+        [D, K, B, n_node, 4]."""
         D = lamd.shape[0]
         grad = nat.InputCotangent()
         amp_bar = torch.zeros((D, self.n_beams), dtype=self.dtype, device=self.device) if want_amp else None
-        f_bar = torch.zeros((D, self.n_beams, self.n_node, 4), dtype=self.dtype, device=self.device)
+        f_bar = torch.zeros((D,) + (() if sd is None else (int(sd.n_intervals),)) + (self.n_beams, self.n_node, 4),
+                            dtype=self.dtype, device=self.device)
         grad.amp_bar = amp_bar.data_ptr() if amp_bar is not None else None
-        grad.f_held_bar = f_bar.data_ptr()
+        grad.f_held_bar = f_bar.data_ptr() if sd is None else None
         if want_params:
-            return self._adjoint_params(ckpt, lamd, n_steps, dt, t0, desc, every, rec_bar, grad, amp_bar, f_bar)
+            return self._adjoint_params(ckpt, lamd, n_steps, dt, t0, desc, every, rec_bar, grad, amp_bar, f_bar, sd)
         work = torch.empty((max(1, int(self._lib.crb_rk4_adjoint_work_bytes(self.plan.h, every))) + 7) // 8,
                            dtype=torch.float64, device=self.device)
-        with self._on_device():
-            nat.check(self._lib.crb_step_rk4_adjoint(self.plan.h, self._ptr(ckpt), self._ptr(lamd), int(D), float(t0),
-                                                     float(dt), int(n_steps), int(every), C.byref(desc),
-                                                     C.byref(rec_bar) if rec_bar is not None else None, C.byref(grad),
-                                                     self._ptr(work), self._stream()))
+        with self._on_device():   # (f_bar is grad.f_held_bar without a schedule, sched_bar with one)
+            nat.check(self._lib.crb_step_rk4_adjoint_sched(self.plan.h, self._ptr(ckpt), self._ptr(lamd), int(D), float(t0),
+                                                           float(dt), int(n_steps), int(every), C.byref(desc), self._ref(rec_bar),
+                                                           C.byref(grad), self._ref(sd), self._ptr(f_bar if sd is not None else None),
+                                                           self._ptr(work), self._stream()))
         self._keep = [work, ckpt, lamd, amp_bar, f_bar]
         return amp_bar, f_bar
 
-    def _adjoint_params(self, ckpt, lamd, n_steps, dt, t0, desc, every, rec_bar, grad, amp_bar, f_bar):
-        """crb_step_rk4_adjoint_params on _adjoint's buffers: returns (amp_bar, f_bar, param_bar [D, B, n_node, 8])"""
+    def _adjoint_params(self, ckpt, lamd, n_steps, dt, t0, desc, every, rec_bar, grad, amp_bar, f_bar, sd=None):
+        """crb_step_rk4_adjoint_params (with ``sd``: ..._sched) on _adjoint's buffers: returns (amp_bar, f_bar, param_bar
+        [D, B, n_node, 8])"""
         D = lamd.shape[0]
         pgrad = nat.ParamCotangent()
         param_bar = torch.zeros((D, self.n_beams, self.n_node, 8), dtype=self.dtype, device=self.device)
@@ -735,10 +814,11 @@ class BeamEnsemble:
         work = torch.empty((max(1, int(self._lib.crb_rk4_adjoint_params_work_bytes(self.plan.h, every, int(D)))) + 7) // 8,
                            dtype=torch.float64, device=self.device)
         with self._on_device():
-            nat.check(self._lib.crb_step_rk4_adjoint_params(self.plan.h, self._ptr(ckpt), self._ptr(lamd), int(D), float(t0),
-                                                            float(dt), int(n_steps), int(every), C.byref(desc),
-                                                            C.byref(rec_bar) if rec_bar is not None else None,
-                                                            C.byref(grad), C.byref(pgrad), self._ptr(work), self._stream()))
+            nat.check(self._lib.crb_step_rk4_adjoint_params_sched(self.plan.h, self._ptr(ckpt), self._ptr(lamd), int(D),
+                                                                  float(t0), float(dt), int(n_steps), int(every), C.byref(desc),
+                                                                  self._ref(rec_bar), C.byref(grad), C.byref(pgrad),
+                                                                  self._ref(sd), self._ptr(f_bar if sd is not None else None),
+                                                                  self._ptr(work), self._stream()))
         self._keep = [work, ckpt, lamd, amp_bar, f_bar, param_bar]
         return amp_bar, f_bar, param_bar
 
@@ -813,6 +893,9 @@ class BeamEnsemble:
         resident state) and clock ``t0`` (None: ``time``); ``state``, ``time`` and ``status`` are left alone.
         ``checkpoint_every``: steps per checkpoint segment (checkpoint_interval); the result does not depend on it, bitwise.
         The derivative is the exact transpose of the discrete RK4 map.  fp64 ensembles only.
+        ``held_force=ControlSchedule(U, hold)`` differentiates the rollout of step(control=U, control_hold=hold): the third
+        return is then dL/d control, [K, B, n] ([D, K, B, n]); intervals the rollout does not reach, and entries past a beam's
+        own DOF count in mixed-topology ensembles, are zero.
         ``step_adjoint_params`` also gives the gradient with respect to the rod's own parameters."""
         return self._step_adjoint(False, n_steps, dt, lam_red, x0_red, impulse_amp, impulse_duration, impulse_index, held_force,
                                   t0, record, record_every, lam_record, checkpoint_every)
@@ -820,8 +903,9 @@ class BeamEnsemble:
     def step_adjoint_params(self, n_steps: int, dt: float, lam_red, x0_red=None, impulse_amp=None,
                             impulse_duration: float = 0.01, impulse_index: int = -2, held_force=None,
                             t0: Optional[float] = None, record=None, record_every: int = 1, lam_record=None,
-                            checkpoint_every: Optional[int] = None):
-        """``step_adjoint`` (the same arguments; the first three returns are bitwise its returns) with a fourth return: the
+                            checkpoint_every: Optional[int] = None, control=None, control_hold: Optional[int] = None):
+        """``step_adjoint`` (the same arguments, ``control`` [K, B, n] / ``control_hold`` for
+        ``held_force=ControlSchedule(control, control_hold)``; the first three returns are bitwise its returns) with a fourth return: the
         gradient of the loss with respect to the rod itself -- stiffness per element, drag, gravity -- as fitting a rod to a
         recorded trajectory needs it (crb_step_rk4_adjoint_params: the same sweep, storing its per-stage M^-T lambda_v, and one
         reduction launch per segment).  A dict of tensors, each with a leading D axis when ``lam_red`` has one:
@@ -837,23 +921,25 @@ class BeamEnsemble:
         respect to length, cross_area and density (they enter the mass matrix and its reduction tables), parameters as
         autograd inputs of ``rollout`` (its forward would need parameter overrides), and the closed loop."""
         return self._step_adjoint(True, n_steps, dt, lam_red, x0_red, impulse_amp, impulse_duration, impulse_index, held_force,
-                                  t0, record, record_every, lam_record, checkpoint_every)
+                                  t0, record, record_every, lam_record, checkpoint_every, control, control_hold)
 
     def _step_adjoint(self, param_grads, n_steps, dt, lam_red, x0_red, impulse_amp, impulse_duration, impulse_index, held_force,
-                      t0, record, record_every, lam_record, checkpoint_every):
+                      t0, record, record_every, lam_record, checkpoint_every, control=None, control_hold=None):
         lam, single = self._dirs(lam_red, 2 * self.n, "step_adjoint: lam_red")
         D = lam.shape[0]
+        held_force, sch = self._control(held_force, control, control_hold, n_steps, "step_adjoint")
         t0 = self.time if t0 is None else float(t0)
         every = self.checkpoint_interval(n_steps, checkpoint_every, D if param_grads else None)
         desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index, held_force)
+        sd, packed = self._sched_desc(sch)
         x = self.state.clone() if x0_red is None else self.pack_state(x0_red)
-        ckpt = self._checkpoint(x, n_steps, dt, t0, desc, every, None)
+        ckpt = self._checkpoint(x, n_steps, dt, t0, desc, every, None, sd)
         rec_bar, cot = self._record_cotangent(record, n_steps, record_every, lam_record, D)
         lamd = self._pack_dirs(lam, True)
-        res = self._adjoint(ckpt, lamd, n_steps, dt, t0, desc, every, rec_bar, impulse_amp is not None, param_grads)
+        res = self._adjoint(ckpt, lamd, n_steps, dt, t0, desc, every, rec_bar, impulse_amp is not None, param_grads, sd)
         amp_bar, f_bar = res[0], res[1]
-        self._keep += keep + [x, cot]
-        xb, fb = self._unpack_dirs(lamd), self._unpack_force_dirs(f_bar)
+        self._keep += keep + [x, cot, packed]
+        xb, fb = self._unpack_dirs(lamd), (self._unpack_force_dirs(f_bar) if sd is None else self._unpack_sched_dirs(f_bar))
         out = (xb[0], (amp_bar[0] if amp_bar is not None else None), fb[0]) if single else (xb, amp_bar, fb)
         if param_grads:
             pd = self._param_dict(res[2])
@@ -862,19 +948,22 @@ class BeamEnsemble:
 
     def rollout(self, x0_red, n_steps: int, dt: float, impulse_amp=None, held_force=None, impulse_duration: float = 0.01,
                 impulse_index: int = -2, t0: float = 0.0, record=None, record_every: int = 1,
-                checkpoint_every: Optional[int] = None):
+                checkpoint_every: Optional[int] = None, control=None, control_hold: Optional[int] = None):
         """A differentiable RK4 rollout: x(T) reduced [B, 2n] from ``x0_red`` after ``n_steps`` steps of ``step()``'s map
         (and the ``record`` samples as step() returns them), as a torch.autograd.Function whose backward is the adjoint
-        (crb_step_rk4_adjoint) -- ``loss.backward()`` reaches whichever of ``x0_red``, ``impulse_amp`` [B] and
-        ``held_force`` [B, n] require grad.  The forward is the checkpoint pass, whose checkpoints backward reuses.  Leaves
-        ``state`` and ``time`` alone.  fp64 ensembles only; once differentiable."""
+        (crb_step_rk4_adjoint) -- ``loss.backward()`` reaches whichever of ``x0_red``, ``impulse_amp`` [B],
+        ``held_force`` [B, n] and ``control`` [K, B, n] (held ``control_hold`` steps each, as in step()) require grad: the
+        whole control sequence in one backward sweep.  The forward is the checkpoint pass, whose checkpoints backward reuses.
+        Leaves ``state`` and ``time`` alone.  fp64 ensembles only; once differentiable."""
         x0 = torch.as_tensor(x0_red, dtype=self.dtype, device=self.device)
         amp = None if impulse_amp is None else torch.as_tensor(impulse_amp, dtype=self.dtype, device=self.device)
+        held_force, sch = self._control(held_force, control, control_hold, n_steps, "rollout")
         held = None if held_force is None else torch.as_tensor(held_force, dtype=self.dtype, device=self.device)
+        ctrl, hold = (None, None) if sch is None else sch
         opts = dict(n_steps=int(n_steps), dt=float(dt), t0=float(t0), duration=float(impulse_duration),
                     index=int(impulse_index), record=record, record_every=int(record_every),
-                    every=self.checkpoint_interval(n_steps, checkpoint_every))
-        xT, samples = _Rollout.apply(self, opts, x0, amp, held)
+                    every=self.checkpoint_interval(n_steps, checkpoint_every), hold=hold)
+        xT, samples = _Rollout.apply(self, opts, x0, amp, held, ctrl)
         return (xT, samples) if record is not None else xT
 
     def step_implicit(self, n_steps: int, h: float, n_iter: int = 2, impulse_amp=None, impulse_duration: float = 0.01,
@@ -1426,16 +1515,17 @@ class _Rollout(torch.autograd.Function):
     """BeamEnsemble.rollout: forward = crb_step_rk4_checkpoint, backward = crb_step_rk4_adjoint on the saved checkpoints"""
 
     @staticmethod
-    def forward(ctx, ens, opts, x0, amp, held):
+    def forward(ctx, ens, opts, x0, amp, held, ctrl):
         desc, keep = ens._input_desc(None if amp is None else amp.detach(), opts["duration"], opts["index"],
                                      None if held is None else held.detach())
+        sd, packed = ens._sched_desc(None if ctrl is None else (ctrl.detach(), opts["hold"]))
         x = ens.pack_state(x0.detach())
         rec, samples = ens._record_desc(opts["record"], opts["n_steps"], opts["record_every"])
-        ckpt = ens._checkpoint(x, opts["n_steps"], opts["dt"], opts["t0"], desc, opts["every"], rec)
-        ens._keep = keep + [x, samples]
+        ckpt = ens._checkpoint(x, opts["n_steps"], opts["dt"], opts["t0"], desc, opts["every"], rec, sd)
+        ens._keep = keep + [x, samples, packed]
         ctx.ens, ctx.opts = ens, opts
-        ctx.has_amp, ctx.has_held = amp is not None, held is not None
-        ctx.save_for_backward(ckpt, None if amp is None else amp.detach(), None if held is None else held.detach())
+        ctx.has_amp, ctx.has_held, ctx.has_ctrl = amp is not None, held is not None, ctrl is not None
+        ctx.save_for_backward(ckpt, None if amp is None else amp.detach(), None if held is None else held.detach(), packed)
         if samples is None:
             samples = torch.zeros(0, dtype=ens.dtype, device=ens.device)
         if opts["record"] is None:
@@ -1446,15 +1536,18 @@ class _Rollout(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g_x, g_samples):
         ens, o = ctx.ens, ctx.opts
-        ckpt, amp, held = ctx.saved_tensors
+        ckpt, amp, held, packed = ctx.saved_tensors
         desc, keep = ens._input_desc(amp, o["duration"], o["index"], held)
+        sd = nat.InputSchedule(packed.data_ptr(), int(packed.shape[0]), int(o["hold"])) if ctx.has_ctrl else None
         g_x = torch.zeros((ens.n_beams, 2 * ens.n), dtype=ens.dtype, device=ens.device) if g_x is None else g_x
         lamd = ens._pack_dirs(g_x.to(ens.dtype).reshape(1, ens.n_beams, 2 * ens.n).contiguous(), True)
         rec_bar, cot = ens._record_cotangent(o["record"], o["n_steps"], o["record_every"],
                                              g_samples if o["record"] is not None else None, 1)
-        amp_bar, f_bar = ens._adjoint(ckpt, lamd, o["n_steps"], o["dt"], o["t0"], desc, o["every"], rec_bar, ctx.has_amp)
-        ens._keep += keep + [cot]
+        amp_bar, f_bar = ens._adjoint(ckpt, lamd, o["n_steps"], o["dt"], o["t0"], desc, o["every"], rec_bar, ctx.has_amp,
+                                      False, sd)
+        ens._keep += keep + [cot, packed]
         gx0 = ens._unpack_dirs(lamd)[0] if ctx.needs_input_grad[2] else None
         gamp = amp_bar[0] if (ctx.has_amp and ctx.needs_input_grad[3]) else None
         gheld = ens._unpack_force_dirs(f_bar)[0] if (ctx.has_held and ctx.needs_input_grad[4]) else None
-        return None, None, gx0, gamp, gheld
+        gctrl = ens._unpack_sched_dirs(f_bar)[0] if (ctx.has_ctrl and ctx.needs_input_grad[5]) else None
+        return None, None, gx0, gamp, gheld, gctrl

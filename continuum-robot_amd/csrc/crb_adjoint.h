@@ -85,6 +85,9 @@ struct AdjParams {
     // ADJ_BWD_STORE writes, crb_param_grad_kernel reads (last, so that the fields above keep their kernel-argument offsets)
     T* rbar;                    // [n_steps][4][n_cot][B][n_node][4] the masked rbar = M^-T lambda_v of every stage of the segment
     T* param_bar;               // [n_cot][B][n_node][8] crb_param_grad_kernel's accumulators (crb_param_cotangent)
+    // control schedule (KParams sched_stride / sched_hold): f_bar is [n_cot][n_intervals][B][n_node][4] and points at the
+    // interval of the segment's LAST step; fbar_cot_stride = elements from one cotangent's records to the next (0 = B * n_node * 4)
+    size_t fbar_cot_stride;
 };
 
 // LDS: q [3][NT], rbar [3][NT], element left halves / element forces [3][NT], segment gravity / phibar [2][NT], reduction
@@ -409,7 +412,9 @@ __global__ void __launch_bounds__(ADJ_MAX_NT) crb_adj_kernel(const KParams<T> p,
     const size_t xoff = size_t(tp.beam) * 2 * plane + node * 4;
     const size_t state_sz = size_t(p.B) * 2 * plane;
     const size_t loff = d * state_sz + xoff;
-    const size_t uoff = size_t(tp.beam) * plane + node * 4, luoff = d * size_t(p.B) * plane + uoff;
+    const size_t uoff = size_t(tp.beam) * plane + node * 4;
+    const size_t luoff = d * size_t(p.B) * plane + uoff;                                                 // ubar, rbar
+    const size_t fboff = d * (aq.fbar_cot_stride ? aq.fbar_cot_stride : size_t(p.B) * plane) + uoff;    // f_bar
     const bool zero_node0 = p.off == 1 && tp.j == 0;   // node 0 (FIXED in every beam, no slot) is written zero
     T uh[3] = {T(0), T(0), T(0)};
     T amp = T(0);
@@ -477,7 +482,20 @@ __global__ void __launch_bounds__(ADJ_MAX_NT) crb_adj_kernel(const KParams<T> p,
 #pragma unroll
             for (int c = 0; c < 3; ++c) { x[c] = p.x[xoff + c] * sc.mask[c]; x[3 + c] = p.x[xoff + plane + c] * sc.mask[c]; }
         double tc = p.t0;
+        // control schedule: steps until the next interval's force takes uh's place (the host hands every launch the interval
+        // and the phase it starts in); never 0 without a schedule.  One scalar and the lane's address stay live across a step.
+        int sched_left = p.sched_stride ? p.sched_first : -1;
+        const T* sched_u = p.u_held + uoff;
+        asm volatile("" : "+v"(sched_u));
         for (int step = 0; step < p.n_steps; ++step) {
+            if (sched_left == 0) {   // (wave-uniform)
+                sched_left = p.sched_hold;
+                sched_u += p.sched_stride;
+                if (valid)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) uh[c] = sched_u[c];
+            }
+            --sched_left;
             T* stage_out = nullptr;
             if (aq.stage_pts) {   // the recompute: every step's four stage points, states[step][s]
                 if (valid) stage_out = aq.states + size_t(step) * 4 * state_sz + xoff;
@@ -524,14 +542,14 @@ __global__ void __launch_bounds__(ADJ_MAX_NT) crb_adj_kernel(const KParams<T> p,
         for (int c = 0; c < 3; ++c) {
             lam[c] = aq.lam[loff + c] * sc.mask[c];
             lam[3 + c] = aq.lam[loff + plane + c] * sc.mask[c];
-            if (aq.f_bar) fb[c] = aq.f_bar[luoff + c];
+            if (aq.f_bar) fb[c] = aq.f_bar[fboff + c];
         }
         if (aq.amp_bar && imp_here) ab = aq.amp_bar[d * size_t(p.B) + tp.beam];
     }
     // this lane's addresses of the sweep's uniform-base buffers, formed once and held in vector registers (as scalars they
     // stay live across the sweep next to its loop constants, past the scalar register file)
     T* lam_p = aq.lam + loff;
-    T* fb_p = aq.f_bar ? aq.f_bar + luoff : nullptr;
+    T* fb_p = (aq.f_bar && valid) ? aq.f_bar + fboff : nullptr;
     T* ab_p = (aq.amp_bar && imp_here) ? aq.amp_bar + d * size_t(p.B) + tp.beam : nullptr;
     const T* rec_p = nullptr;
     if (p.rec_out)
@@ -611,6 +629,18 @@ __global__ void __launch_bounds__(ADJ_MAX_NT) crb_adj_kernel(const KParams<T> p,
         }
 #pragma unroll
         for (int c = 0; c < 6; ++c) lam[c] = lam[c] + sum[c];
+        // control schedule: the step just swept was its interval's first, and the launch goes on below it -- this interval's
+        // sum is complete: store it, move the lane address down one interval and take up the record there (accumulated: a
+        // later segment may have left a partial sum)
+        int hold = p.sched_hold;
+        asm volatile("" : "+s"(hold));
+        if (p.sched_stride && i > 0 && kstep % hold == 0 && fb_p) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) fb_p[c] = fb[c];
+            fb_p -= p.sched_stride;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) fb[c] = fb_p[c];
+        }
     }
     if (!valid) return;
     T* const lo = lam_p;

@@ -95,6 +95,12 @@ struct KParams {
     // the beam's state writes `status_value` there (the number of steps the ensemble has taken by the end of that launch)
     int32_t* status;
     int32_t status_value;
+    // control schedule (crb_input_schedule; the RK4 rollout family): u_held points at the force of the interval the launch
+    // starts in, which holds for the launch's first sched_first steps; then the record sched_stride elements further takes
+    // its place, and the next one after every sched_hold steps more.  sched_stride == 0: no schedule, u_held for the whole
+    // launch.  (Last, so that every field above keeps its kernel-argument offset.)
+    size_t sched_stride;
+    int sched_first, sched_hold;
 };
 
 // (end of a stepper launch) a thread whose node came out non-finite marks its beam, once: NaN / Inf never turn finite again,
@@ -654,7 +660,20 @@ __global__ void __launch_bounds__(MAXT, MINW) crb_beam_kernel(const KParams<T> p
     // ---- classical RK4, state resident in registers across all steps
     const T dt = T(p.dt), hdt = T(0.5 * p.dt), dt6 = T(p.dt / 6.0);
     double tc = p.t0;
+    // control schedule: steps until the next interval's force takes uh's place; never 0 without a schedule
+    int sched_left = (!LEAN && !FB && p.sched_stride) ? p.sched_first : -1;
+    const T* sched_u = p.u_held + (valid ? size_t(beam) * plane + node * 4 : 0);   // this node's record of the current interval
     for (int step = 0; step < p.n_steps; ++step) {
+        if (!LEAN && !FB) {
+            if (sched_left == 0) {   // (wave-uniform; three loads per lane at an interval's first step)
+                sched_left = p.sched_hold;
+                sched_u += p.sched_stride;
+                if (valid)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) uh[c] = sched_u[c];
+            }
+            --sched_left;
+        }
         const double t_half = __dadd_rn(tc, 0.5 * p.dt), t_full = __dadd_rn(tc, p.dt);
         T acc[6] = {T(0), T(0), T(0), T(0), T(0), T(0)};
         T xs[6];

@@ -842,7 +842,31 @@ crb_step_lean_kernel(const KParams<T> p_formal) {
 
     double tc = p.t0;
     T accq[3], accv[3], sq[3], sv[3];  // RK4 accumulators and stage state
+    // HELD, control schedule (crb_input_schedule): a run-time test in the HELD instantiations -- steps until the next
+    // interval's force takes uh's place (never 0 without a schedule), and that interval's index.  Only these two scalars
+    // stay live across the stages: what the reload needs of the launch parameters is re-read through a laundered kernarg
+    // pointer inside the branch, and the loads are waited for there, not at uh's first use in every step.
+    int sched_left = (HELD && p.sched_stride) ? p.sched_first : -1, sched_k = 0;
     for (int step = 0; step < p.n_steps; ++step) {
+        if constexpr (HELD) {
+            if (sched_left == 0) {   // (wave-uniform)
+                auto kq = kp;
+                CRB_FRESH(kq);
+                const KParams<T>& q = CRB_PARAMS(kq);
+                sched_left = q.sched_hold;
+                ++sched_k;
+                if (valid) {
+                    const T* const u = q.u_held + size_t(sched_k) * q.sched_stride + (size_t(beam) * size_t(q.n_node) + node) * 4;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) uh[c] = u[c];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) asm volatile("" : "+v"(uh[c]));
+#endif
+                }
+            }
+            --sched_left;
+        }
         const double t_half = __dadd_rn(tc, 0.5 * p.dt), t_full = __dadd_rn(tc, p.dt);
 #pragma unroll
         for (int c = 0; c < 3; ++c) { accq[c] = T(0); accv[c] = T(0); sq[c] = xq[c]; sv[c] = xv[c]; }

@@ -48,6 +48,8 @@ struct TangentParams {
     T* dxdot;           // MODE_RHS: [n_dir][B][2][n_node][4] tangent of the RHS
     const T* du_held;   // [n_dir][B][n_node][4] tangent of the held force, or nullptr (= 0)
     const T* d_amp;     // [n_dir][B] tangent of the impulse amplitude, or nullptr (= 0)
+    size_t du_dir_stride;   // elements from one direction of du_held to the next; 0 = B * n_node * 4.  With a control schedule
+                            //  (KParams sched_*) du_held is [n_dir][n_intervals][B][n_node][4] and switches with u_held
 };
 
 // LDS: q + eps dq [6][NT], element halves [6][NT], segment gravity [4][NT], reduction exchange r0 / r1 [6][NT] each.
@@ -239,7 +241,8 @@ __global__ void __launch_bounds__(TANGENT_MAX_NT) crb_jvp_kernel(const KParams<T
     const size_t plane = size_t(p.n_node) * 4, node = size_t(tp.j + p.off);
     const size_t xoff = size_t(tp.beam) * 2 * plane + node * 4;            // the base's record
     const size_t dxoff = d * size_t(p.B) * 2 * plane + xoff;              // this direction's record
-    const size_t uoff = size_t(tp.beam) * plane + node * 4, duoff = d * size_t(p.B) * plane + uoff;
+    const size_t uoff = size_t(tp.beam) * plane + node * 4;
+    const size_t duoff = d * (tq.du_dir_stride ? tq.du_dir_stride : size_t(p.B) * plane) + uoff;
     const T* const xin = (MODE == MODE_STEP) ? tq.x0 : p.x;
     T x[6] = {T(0), T(0), T(0), T(0), T(0), T(0)}, dx[6] = {T(0), T(0), T(0), T(0), T(0), T(0)};
     T uh[3] = {T(0), T(0), T(0)}, duh[3] = {T(0), T(0), T(0)};
@@ -288,7 +291,21 @@ __global__ void __launch_bounds__(TANGENT_MAX_NT) crb_jvp_kernel(const KParams<T
     // ---- classical RK4 on (x, dx): crb_beam_kernel's MODE_STEP with the tangent alongside
     const T dt = T(p.dt), hdt = T(0.5 * p.dt), dt6 = T(p.dt / 6.0);
     double tc = p.t0;
+    // control schedule: steps until the next interval's force (and its tangent) take over; never 0 without a schedule
+    int sched_left = p.sched_stride ? p.sched_first : -1;
+    size_t sched_off = 0;
     for (int step = 0; step < p.n_steps; ++step) {
+        if (sched_left == 0) {   // (wave-uniform)
+            sched_left = p.sched_hold;
+            sched_off += p.sched_stride;
+            if (valid)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    uh[c] = p.u_held[sched_off + uoff + c];
+                    if (tq.du_held) duh[c] = tq.du_held[sched_off + duoff + c] * sc.mask[c];
+                }
+        }
+        --sched_left;
         const double t_half = __dadd_rn(tc, 0.5 * p.dt), t_full = __dadd_rn(tc, p.dt);
         T acc[6] = {T(0), T(0), T(0), T(0), T(0), T(0)}, dacc[6] = {T(0), T(0), T(0), T(0), T(0), T(0)};
         T xs[6], dxs[6];

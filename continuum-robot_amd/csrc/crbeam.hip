@@ -991,6 +991,38 @@ void set_io(KParams<T>& k, const Forcing& f, const Recording* r = nullptr) {
     if (r) { k.rec_out = static_cast<T*>(r->out); k.rec_slot = r->slot; k.rec_comp = r->comp; k.rec_every = r->every; k.rec_n = r->count; }
 }
 
+// The control schedule of a call (crb_input_schedule), checked against the call's steps and input; f == nullptr: none.
+struct Schedule {
+    const void* f = nullptr;
+    int K = 0, hold = 0;
+};
+int decode_schedule(const crb_input_schedule* s, const crb_input_desc* in, int n_steps, const char* who_c, Schedule* out) {
+    *out = Schedule();
+    if (!s) return CRB_OK;
+    const std::string who(who_c);
+    if (!s->f_sched) return fail(CRB_EINVAL, who + ": f_sched of the schedule is null");
+    if (s->n_intervals < 1) return fail(CRB_EINVAL, who + ": n_intervals of the schedule must be >= 1");
+    if (s->hold < 1) return fail(CRB_EINVAL, who + ": hold of the schedule must be >= 1");
+    if ((long long)n_steps > (long long)s->n_intervals * (long long)s->hold)
+        return fail(CRB_EINVAL, who + ": n_steps exceeds the schedule's n_intervals * hold");
+    if (in && in->f_held) return fail(CRB_EINVAL, who + ": a schedule and input->f_held are given together");
+    out->f = s->f_sched;
+    out->K = s->n_intervals;
+    out->hold = s->hold;
+    return CRB_OK;
+}
+// elements from one interval of a schedule-shaped tensor [K][B][n_node][4] to the next
+size_t sched_interval_elems(const crb_plan* p) { return size_t(p->B) * size_t(p->n_node) * 4; }
+// the schedule in the parameter block of a launch whose first step is step `first_step` of the call
+template <typename T>
+void set_sched(const crb_plan* p, KParams<T>& k, const Schedule& s, int first_step) {
+    if (!s.f) return;
+    k.sched_stride = sched_interval_elems(p);
+    k.sched_hold = s.hold;
+    k.sched_first = s.hold - first_step % s.hold;
+    k.u_held = static_cast<const T*>(s.f) + size_t(first_step / s.hold) * k.sched_stride;
+}
+
 // ---- which kernel a call runs: the condition of every path, side by side.  The shapes the lean kernels are built for are
 // stated once per family next to its launcher (lean_*_built, controlled_built, loop_built in crb_*_launch.h: the launchers
 // instantiate exactly those); a predicate here asks that function and adds what only a plan knows -- beams per wave,
@@ -1247,10 +1279,12 @@ extern "C" int crb_step_rk4(const crb_plan* p, void* x, double t0, double dt, in
 
 namespace {
 template <typename T>
-int step_rk4_impl(const crb_plan* p, void* x, double t0, double dt, int n_steps, const Forcing& f, const Recording& r, hipStream_t st) {
+int step_rk4_impl(const crb_plan* p, void* x, double t0, double dt, int n_steps, const Forcing& f, const Schedule& sc,
+                  const Recording& r, hipStream_t st) {
     KParams<T> k = base_params<T>(p);
     k.x = static_cast<T*>(x);
     set_io(k, f, &r);
+    set_sched(p, k, sc, 0);   // (a held input of its own: never the lean forms without one, nor the register-blocked stepper)
     k.t0 = t0; k.dt = dt; k.n_steps = n_steps;
     arm_status(p, k, n_steps);
     if constexpr (sizeof(T) == 8) {
@@ -1267,6 +1301,16 @@ int step_rk4_impl(const crb_plan* p, void* x, double t0, double dt, int n_steps,
 
 extern "C" int crb_step_rk4_rec(const crb_plan* p, void* x, double t0, double dt, int n_steps, const crb_input_desc* in,
                                 const crb_record_desc* rec, double* t_end, void* stream) {
+    return crb_step_rk4_sched(p, x, t0, dt, n_steps, in, nullptr, rec, t_end, stream);
+}
+
+extern "C" int crb_step_rk4_sched(const crb_plan* p, void* x, double t0, double dt, int n_steps, const crb_input_desc* in,
+                                  const crb_input_schedule* sched, const crb_record_desc* rec, double* t_end, void* stream) {
+    Schedule sc;
+    if (sched) {   // (refused before the device is touched)
+        if (!p) return fail(CRB_EINVAL, "crb_step_rk4_sched: null plan");
+        if (int rc = decode_schedule(sched, in, n_steps, "crb_step_rk4_sched", &sc)) return rc;
+    }
     if (int rc = need_device(p, "crb_step_rk4")) return rc;
     Recording r;
     if (int rc = decode_record(p, rec, n_steps, true, "crb_step_rk4", &r)) return rc;
@@ -1278,8 +1322,8 @@ extern "C" int crb_step_rk4_rec(const crb_plan* p, void* x, double t0, double dt
     if (t_end) *t_end = clock_after(t0, dt, n_steps);
     if (n_steps == 0) return CRB_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return p->dtype == CRB_F64 ? step_rk4_impl<double>(p, x, t0, dt, n_steps, f, r, st)
-                               : step_rk4_impl<float>(p, x, t0, dt, n_steps, f, r, st);
+    return p->dtype == CRB_F64 ? step_rk4_impl<double>(p, x, t0, dt, n_steps, f, sc, r, st)
+                               : step_rk4_impl<float>(p, x, t0, dt, n_steps, f, sc, r, st);
 }
 
 // ------------------------------------------------------------------ host-vector entry points (single-beam closures)
@@ -2336,6 +2380,21 @@ extern "C" int crb_rhs_jvp(const crb_plan* p, const void* x, const void* u, cons
 
 extern "C" int crb_step_rk4_tangent(const crb_plan* p, void* x, void* dx, int n_dir, double t0, double dt, int n_steps,
                                     const crb_input_desc* in, const crb_input_tangent* din, double* t_end, void* stream) {
+    return crb_step_rk4_tangent_sched(p, x, dx, n_dir, t0, dt, n_steps, in, din, nullptr, nullptr, t_end, stream);
+}
+
+extern "C" int crb_step_rk4_tangent_sched(const crb_plan* p, void* x, void* dx, int n_dir, double t0, double dt, int n_steps,
+                                          const crb_input_desc* in, const crb_input_tangent* din, const crb_input_schedule* sched,
+                                          const void* d_sched, double* t_end, void* stream) {
+    Schedule sc;
+    if (sched || d_sched) {   // (refused before the device is touched)
+        const char* who = "crb_step_rk4_tangent_sched";
+        if (!p) return fail(CRB_EINVAL, std::string(who) + ": null plan");
+        if (p->dtype != CRB_F64) return fail(CRB_EUNSUPPORTED, std::string(who) + ": the tangent kernels need an fp64 plan");
+        if (!sched) return fail(CRB_EINVAL, std::string(who) + ": d_sched needs a schedule (sched is null)");
+        if (int rc = decode_schedule(sched, in, n_steps, who, &sc)) return rc;
+        if (din && din->df_held) return fail(CRB_EINVAL, std::string(who) + ": a schedule and dinput->df_held are given together");
+    }
     if (int rc = tangent_checks(p, n_dir, "crb_step_rk4_tangent")) return rc;
     if (!x || !dx) return fail(CRB_EINVAL, "crb_step_rk4_tangent: null state or tangent");
     if (n_steps < 0) return fail(CRB_EINVAL, "crb_step_rk4_tangent: n_steps must be >= 0");
@@ -2364,6 +2423,11 @@ extern "C" int crb_step_rk4_tangent(const crb_plan* p, void* x, void* dx, int n_
     if (din) {
         q.du_held = static_cast<const double*>(din->df_held);
         q.d_amp = static_cast<const double*>(din->d_amp);
+    }
+    if (sc.f) {
+        set_sched(p, k, sc, 0);
+        q.du_held = static_cast<const double*>(d_sched);
+        q.du_dir_stride = size_t(sc.K) * sched_interval_elems(p);
     }
     HIP_TRY(crb::launch_jvp_step(k, q, (p->B + p->G - 1) / p->G, n_dir, p->NT, st));
     return CRB_OK;
@@ -2504,7 +2568,15 @@ extern "C" size_t crb_rk4_adjoint_work_bytes(const crb_plan* p, int every) {
 extern "C" int crb_step_rk4_checkpoint(const crb_plan* p, void* x, double t0, double dt, int n_steps, int every,
                                        const crb_input_desc* in, const crb_record_desc* rec, void* ckpt, double* t_end,
                                        void* stream) {
+    return crb_step_rk4_checkpoint_sched(p, x, t0, dt, n_steps, every, in, nullptr, rec, ckpt, t_end, stream);
+}
+
+extern "C" int crb_step_rk4_checkpoint_sched(const crb_plan* p, void* x, double t0, double dt, int n_steps, int every,
+                                             const crb_input_desc* in, const crb_input_schedule* sched,
+                                             const crb_record_desc* rec, void* ckpt, double* t_end, void* stream) {
     if (int rc = adjoint_checks(p, 1, "crb_step_rk4_checkpoint")) return rc;
+    Schedule sc;
+    if (int rc = decode_schedule(sched, in, n_steps, "crb_step_rk4_checkpoint_sched", &sc)) return rc;
     if (!x || !ckpt) return fail(CRB_EINVAL, "crb_step_rk4_checkpoint: null state or checkpoint buffer");
     if (x == ckpt) return fail(CRB_EINVAL, "crb_step_rk4_checkpoint: the checkpoint buffer must not alias the state");
     if (n_steps < 0) return fail(CRB_EINVAL, "crb_step_rk4_checkpoint: n_steps must be >= 0");
@@ -2521,6 +2593,7 @@ extern "C" int crb_step_rk4_checkpoint(const crb_plan* p, void* x, double t0, do
     KParams<double> k = base_params<double>(p);
     k.x = static_cast<double*>(x);
     set_io(k, f, &r);
+    set_sched(p, k, sc, 0);
     k.t0 = t0; k.dt = dt; k.n_steps = n_steps;
     AdjParams<double> q = adj_params(p);
     q.states = static_cast<double*>(ckpt);
@@ -2535,9 +2608,17 @@ namespace {
 // latter with the storing sweep and crb_param_grad_kernel after each
 int adjoint_rollout(const char* who_c, const crb_plan* p, const void* ckpt, void* lam, int n_cot, double t0, double dt, int n_steps,
                     int every, const crb_input_desc* in, const crb_record_desc* rec_bar, const crb_input_cotangent* grad,
-                    bool want_params, const crb_param_cotangent* pgrad, void* work, void* stream) {
+                    bool want_params, const crb_param_cotangent* pgrad, const crb_input_schedule* sched, void* sched_bar,
+                    void* work, void* stream) {
     const std::string who(who_c);
     if (int rc = adjoint_checks(p, n_cot, who_c)) return rc;
+    Schedule sc;
+    if (int rc = decode_schedule(sched, in, n_steps, who_c, &sc)) return rc;
+    if (sched_bar && !sc.f) return fail(CRB_EINVAL, who + ": sched_bar needs a schedule (sched is null)");
+    if (sc.f && grad && grad->f_held_bar)
+        return fail(CRB_EINVAL, who + ": a schedule and grad->f_held_bar are given together (sched_bar takes its place)");
+    if (sched_bar && (sched_bar == lam || sched_bar == work || sched_bar == ckpt || sched_bar == sc.f))
+        return fail(CRB_EINVAL, who + ": sched_bar must not alias lam, the work buffer, the checkpoints or f_sched");
     if (!ckpt || !lam) return fail(CRB_EINVAL, who + ": null checkpoint buffer or cotangent");
     if (want_params && (!pgrad || !pgrad->param_bar))
         return fail(CRB_EINVAL, who + ": null parameter cotangent (crb_param_cotangent.param_bar)");
@@ -2556,14 +2637,15 @@ int adjoint_rollout(const char* who_c, const crb_plan* p, const void* ckpt, void
     Forcing f;
     if (int rc = decode_input(p, in, who_c, &f)) return rc;
     void* amp_bar = grad ? grad->amp_bar : nullptr;
-    void* f_bar = grad ? grad->f_held_bar : nullptr;
+    void* f_bar = sc.f ? sched_bar : (grad ? grad->f_held_bar : nullptr);   // (one accumulator in the sweep: the interval's record)
     if (amp_bar && !f.impulse)
         return fail(CRB_EINVAL, who + ": amp_bar needs an impulse input (its amplitude is what it differentiates)");
-    const void* bufs[6] = {ckpt, work, amp_bar, f_bar, r.out, f.held};
+    const void* bufs[7] = {ckpt, work, amp_bar, f_bar, r.out, f.held, sc.f};
     for (const void* b : bufs)
         if (b && b == lam) return fail(CRB_EINVAL, who + ": lam must not alias another buffer of the call");
     if ((amp_bar && (amp_bar == work || amp_bar == ckpt || amp_bar == f_bar)) || (f_bar && (f_bar == work || f_bar == ckpt)) ||
-        work == ckpt || (param_bar && (param_bar == amp_bar || param_bar == f_bar || param_bar == r.out || param_bar == f.held)))
+        work == ckpt || (sc.f && (sc.f == work || sc.f == amp_bar || sc.f == param_bar)) ||
+        (param_bar && (param_bar == amp_bar || param_bar == f_bar || param_bar == r.out || param_bar == f.held)))
         return fail(CRB_EINVAL, who + ": the output and work buffers must not alias each other or the checkpoints");
     if (n_steps == 0) return CRB_OK;
     if (int rc = ensure_gadj(p, who_c)) return rc;
@@ -2579,6 +2661,7 @@ int adjoint_rollout(const char* who_c, const crb_plan* p, const void* ckpt, void
         const double tg = clock_after(t0, dt, k0);   // (the checkpoint pass's clock at the segment start: the same additions)
         KParams<double> k = base_params<double>(p);
         set_io(k, f);
+        set_sched(p, k, sc, k0);   // (the recompute starts mid-rollout: its interval and phase)
         k.dt = dt; k.t0 = tg; k.n_steps = n;
         // 1. the segment's stage points from its checkpoint
         k.x = const_cast<double*>(static_cast<const double*>(ckpt)) + size_t(g) * sd;
@@ -2596,6 +2679,10 @@ int adjoint_rollout(const char* who_c, const crb_plan* p, const void* ckpt, void
         b.lam = static_cast<double*>(lam);
         b.amp_bar = static_cast<double*>(amp_bar);
         b.f_bar = static_cast<double*>(f_bar);
+        if (sc.f && f_bar) {   // the sweep starts in the interval of the segment's last step and walks down from there
+            b.f_bar += size_t((k0 + n - 1) / sc.hold) * sched_interval_elems(p);
+            b.fbar_cot_stride = size_t(sc.K) * sched_interval_elems(p);
+        }
         b.step0 = k0;
         if (!want_params) {
             HIP_TRY(crb::launch_adj_backward(k, b, groups, n_cot, p->NT, st));
@@ -2615,7 +2702,15 @@ extern "C" int crb_step_rk4_adjoint(const crb_plan* p, const void* ckpt, void* l
                                     int every, const crb_input_desc* in, const crb_record_desc* rec_bar,
                                     const crb_input_cotangent* grad, void* work, void* stream) {
     return adjoint_rollout("crb_step_rk4_adjoint", p, ckpt, lam, n_cot, t0, dt, n_steps, every, in, rec_bar, grad, false, nullptr,
-                           work, stream);
+                           nullptr, nullptr, work, stream);
+}
+
+extern "C" int crb_step_rk4_adjoint_sched(const crb_plan* p, const void* ckpt, void* lam, int n_cot, double t0, double dt,
+                                          int n_steps, int every, const crb_input_desc* in, const crb_record_desc* rec_bar,
+                                          const crb_input_cotangent* grad, const crb_input_schedule* sched, void* sched_bar,
+                                          void* work, void* stream) {
+    return adjoint_rollout(sched ? "crb_step_rk4_adjoint_sched" : "crb_step_rk4_adjoint", p, ckpt, lam, n_cot, t0, dt, n_steps,
+                           every, in, rec_bar, grad, false, nullptr, sched, sched_bar, work, stream);
 }
 
 extern "C" size_t crb_rk4_adjoint_params_work_bytes(const crb_plan* p, int every, int n_cot) {
@@ -2629,5 +2724,14 @@ extern "C" int crb_step_rk4_adjoint_params(const crb_plan* p, const void* ckpt, 
                                            const crb_input_cotangent* grad, const crb_param_cotangent* pgrad, void* work,
                                            void* stream) {
     return adjoint_rollout("crb_step_rk4_adjoint_params", p, ckpt, lam, n_cot, t0, dt, n_steps, every, in, rec_bar, grad, true,
-                           pgrad, work, stream);
+                           pgrad, nullptr, nullptr, work, stream);
+}
+
+extern "C" int crb_step_rk4_adjoint_params_sched(const crb_plan* p, const void* ckpt, void* lam, int n_cot, double t0, double dt,
+                                                 int n_steps, int every, const crb_input_desc* in,
+                                                 const crb_record_desc* rec_bar, const crb_input_cotangent* grad,
+                                                 const crb_param_cotangent* pgrad, const crb_input_schedule* sched,
+                                                 void* sched_bar, void* work, void* stream) {
+    return adjoint_rollout(sched ? "crb_step_rk4_adjoint_params_sched" : "crb_step_rk4_adjoint_params", p, ckpt, lam, n_cot, t0,
+                           dt, n_steps, every, in, rec_bar, grad, true, pgrad, sched, sched_bar, work, stream);
 }

@@ -495,6 +495,50 @@ int crb_step_rk4_feedback(const crb_plan* plan, void* x, double t0, double dt, i
 int crb_step_rk4_rec(const crb_plan* plan, void* x, double t0, double dt, int n_steps, const crb_input_desc* input,
                      const crb_record_desc* rec, double* t_end, void* stream);
 
+/* A piecewise-constant control sequence for the RK4 rollout family: the `u` of get_dynamic_system()(t, x, u)
+ * (dynamic_beam_model.py:343-362) as a zero-order hold, what the u(t) closures of lqr_control.py:33-41 hand the integrator --
+ * here a whole shooting / MPC horizon in one call.  Step i of the call (counted from the call's first step) applies vector
+ * i / hold in all four RK4 stages, on top of the impulse if there is one; n_steps <= n_intervals * hold, the last interval may
+ * be cut short.  n_intervals = 1, hold >= n_steps is crb_input_desc.f_held.  A schedule and input->f_held together are refused. */
+typedef struct crb_input_schedule {
+    const void* f_sched;   /* device [n_intervals][B][n_node][4], plan dtype */
+    int32_t n_intervals;   /* K >= 1 */
+    int32_t hold;          /* RK4 steps per interval, >= 1 */
+} crb_input_schedule;
+
+/* The RK4 rollout family with a control schedule: each call is its counterpart above (the same arguments, clock, impulse
+ * window, recording and status; bitwise the chain of one call per interval with f_held = that interval's vector) and, with
+ * sched == NULL, exactly that call.  The schedule is switched inside the kernels: one launch (one launch pair per checkpoint
+ * segment for the adjoint), whatever n_intervals.  Checked before the device is touched, so that host-only plans show them
+ * (valid calls on those: CRB_ENODEV): CRB_EINVAL for a NULL f_sched, n_intervals < 1, hold < 1, n_steps > n_intervals * hold,
+ * a schedule together with input->f_held (or with its tangent df_held / cotangent f_held_bar), d_sched / sched_bar without a
+ * schedule, sched_bar aliasing lam, work, ckpt or f_sched; CRB_EUNSUPPORTED for fp32 plans in the tangent and adjoint calls.
+ * crb_last_error() names the offending argument.
+ *   crb_step_rk4_sched            crb_step_rk4_rec; fp64 and fp32 plans
+ *   crb_step_rk4_tangent_sched    crb_step_rk4_tangent; d_sched: device [n_dir][n_intervals][B][n_node][4], the tangent of the
+ *                                 schedule per direction, or NULL (= 0)
+ *   crb_step_rk4_checkpoint_sched crb_step_rk4_checkpoint
+ *   crb_step_rk4_adjoint_sched    crb_step_rk4_adjoint run after crb_step_rk4_checkpoint_sched with the same schedule;
+ *                                 sched_bar: device [n_cot][n_intervals][B][n_node][4], dL/d f_sched, ACCUMULATED as
+ *                                 f_held_bar is (intervals the rollout does not reach are left as they are), or NULL
+ *   crb_step_rk4_adjoint_params_sched  crb_step_rk4_adjoint_params likewise */
+int crb_step_rk4_sched(const crb_plan* plan, void* x, double t0, double dt, int n_steps, const crb_input_desc* input,
+                       const crb_input_schedule* sched, const crb_record_desc* rec, double* t_end, void* stream);
+int crb_step_rk4_tangent_sched(const crb_plan* plan, void* x, void* dx, int n_dir, double t0, double dt, int n_steps,
+                               const crb_input_desc* input, const crb_input_tangent* dinput, const crb_input_schedule* sched,
+                               const void* d_sched, double* t_end, void* stream);
+int crb_step_rk4_checkpoint_sched(const crb_plan* plan, void* x, double t0, double dt, int n_steps, int every,
+                                  const crb_input_desc* input, const crb_input_schedule* sched, const crb_record_desc* rec,
+                                  void* ckpt, double* t_end, void* stream);
+int crb_step_rk4_adjoint_sched(const crb_plan* plan, const void* ckpt, void* lam, int n_cot, double t0, double dt, int n_steps,
+                               int every, const crb_input_desc* input, const crb_record_desc* rec_bar,
+                               const crb_input_cotangent* grad, const crb_input_schedule* sched, void* sched_bar, void* work,
+                               void* stream);
+int crb_step_rk4_adjoint_params_sched(const crb_plan* plan, const void* ckpt, void* lam, int n_cot, double t0, double dt,
+                                      int n_steps, int every, const crb_input_desc* input, const crb_record_desc* rec_bar,
+                                      const crb_input_cotangent* grad, const crb_param_cotangent* pgrad,
+                                      const crb_input_schedule* sched, void* sched_bar, void* work, void* stream);
+
 /* out[b] = x[b][plane][node][dof]  (e.g. tip displacement = plane 0, node n_elem, dof 1;
  * lqr_control.py:168) */
 int crb_gather_dof(const crb_plan* plan, const void* x, int plane, int node, int dof, void* out, void* stream);

@@ -243,8 +243,24 @@ __device__ __forceinline__ void lean_rhs(const ElemCoef<T>& ec, T dragc, bool co
 // the roundings of the axial right-hand side change in order (not in number or size), so this instance is no longer bitwise
 // its parent's -- it agrees with it, with the one-node-per-lane stepper and with the oracle to rounding (DESIGN.md §4 has
 // the figures).  The linear instance and every other kernel keep their code line for line.
+// The element polynomials are evaluated in chord-relative variables (crb_math.h: elem_force_nonlinear_chord; e = s - 2 dw,
+// d, dw, L du: the monomials that cancel between s^2, p and s dw are never formed), and RK4 carries the positions on the
+// accelerations (crb_math.h: Rk4Pos): q_2 and q + dt v at the top of stage 0, then one multiply-add of dt^2/4, dt^2/2, dt^2/6
+// times the stage's acceleration per position, so the stage velocities of u and phi and the sum accq are gone; the drag's
+// stage velocity of w is the only one formed, and the next stage's positions are known at the top of each stage as before
+// (the last node's still rides the q exchange).  The state between steps is (xq, xv) and nothing else, unscaled, so chunked
+// launches stay bitwise.  1557 -> 1498 fp64 instructions per step (chord forces alone 1513, the RK4 form alone 1542), VALU
+// 2101 -> 2032, 250 VGPRs, 90 SGPRs, no spill, no scratch; the linear instance takes the RK4 form too (238 VGPRs, 58 SGPRs).
+// Outputs agree with the parent's to rounding.  CRB_BLK_CHORD / CRB_BLK_RK4_POS (=0 in the tuning build)
+// switch either item off for timing.
 // The next beam's state is not prefetched as in the one-node-per-lane
 // form: four nodes' records are 48 more registers than the budget of two waves per SIMD holds.
+#ifndef CRB_BLK_CHORD
+#define CRB_BLK_CHORD 1
+#endif
+#ifndef CRB_BLK_RK4_POS
+#define CRB_BLK_RK4_POS 1
+#endif
 constexpr int BLK_STRIP_PAD = 4;   // the stride of the separator level that goes through the wave's LDS strip (the third)
 constexpr int BLK_STRIP_W = BLK_STRIP_PAD + BLK_LANES + BLK_STRIP_PAD;
 // dynamic LDS of the blocked stepper: the separator tables (value pairs per lane), then per wave a strip [3][W] of fp64
@@ -259,6 +275,10 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
     // the nonlinear element's axial pair regrouped (crb_math.h: elem_force_nonlinear_regrouped), 10 fp64 instructions per element
     // and node instead of 14; the literal polynomial (-DCRB_LITERAL_POLY=1) has no such form
     constexpr bool REGROUP = EM == EM_NONLINEAR && !CRB_LITERAL_POLY;
+    // tuning-build switches (make fast EXTRA=-D...=0): the chord-relative element polynomials (crb_math.h:
+    // elem_force_nonlinear_chord) instead of elem_force_nonlinear_regrouped, and the RK4 positions carried on the
+    // accelerations (crb_math.h: Rk4Pos) instead of on stage velocities of every component
+    constexpr bool CHORD = CRB_BLK_CHORD, RKPOS = CRB_BLK_RK4_POS;
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef const __attribute__((address_space(4))) SlotConst<T>* CS;
 #define CRB_BFRESH(ptr) asm volatile("" : "+s"(ptr))
@@ -331,8 +351,13 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) qL[c] = dpp_from_lower(xq[NP - 1][c]);
         const T dt = T(p.dt), hdt = T(0.5 * p.dt), dt6 = T(p.dt / 6.0);
+        [[maybe_unused]] const T c6 = T(p.dt * p.dt / 6.0), c4 = T(0.25 * p.dt * p.dt), c2 = T(0.5 * p.dt * p.dt);   // (RKPOS)
         double tc = p.t0;
-        T accq[NP][3], accv[NP][3], sq[NP][3], sv[NP][3];
+        // RKPOS: sq is the stage's positions, rk the next stage's and the running sums, sv[.][1] the stage velocity of w (the
+        // only one a force reads: the drag); xv is updated by stage 3 itself.  Otherwise accq / sv carry every component
+        [[maybe_unused]] T accq[NP][3], accv[NP][3];
+        T sq[NP][3], sv[NP][3];
+        [[maybe_unused]] Rk4Pos<T> rk[NP][3];
         for (int step = 0; step < p.n_steps; ++step) {
             double t_half, t_full;
             {
@@ -364,15 +389,27 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                 const T drag_all = SC->drag;   // (loaded whatever the flag: a load under a branch costs a wait of its own)
                 const T dragc = (q.flags & 1u) ? drag_all : T(0);
                 // -- positions of the next stage: the last node's ride on this stage's q exchange
-                T qn3[3], qLn[3];
+                [[maybe_unused]] T qn3[3];
+                T qLn[3];
+                if constexpr (RKPOS) {
+                    if (s == 0) {
 #pragma unroll
-                for (int k = 0; k < NP; ++k)
+                        for (int k = 0; k < NP; ++k)
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) accq[k][c] = (s == 0) ? sv[k][c] : accq[k][c] + w * sv[k][c];   // (stage 0 starts the sum: no 0 + x)
+                            for (int c = 0; c < 3; ++c) rk4_begin<T>(rk[k][c], xq[k][c], xv[k][c], hdt, dt);
+                    }
 #pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    qn3[c] = (s == 3) ? (xq[NP - 1][c] + dt6 * accq[NP - 1][c]) : (xq[NP - 1][c] + cs * sv[NP - 1][c]);
-                    qLn[c] = dpp_from_lower(qn3[c]);
+                    for (int c = 0; c < 3; ++c) qLn[c] = dpp_from_lower(rk[NP - 1][c].next);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < NP; ++k)
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) accq[k][c] = (s == 0) ? sv[k][c] : accq[k][c] + w * sv[k][c];   // (stage 0 starts the sum: no 0 + x)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        qn3[c] = (s == 3) ? (xq[NP - 1][c] + dt6 * accq[NP - 1][c]) : (xq[NP - 1][c] + cs * sv[NP - 1][c]);
+                        qLn[c] = dpp_from_lower(qn3[c]);
+                    }
                 }
                 // -- the four elements left of this lane's nodes (element k joins node k-1 -- lane-1's last for k = 0 -- and node k)
                 CRB_SETPRIO(P_FORCE);
@@ -382,7 +419,8 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
 #pragma unroll
                 for (int k = 0; k < NP; ++k) {
                     if constexpr (REGROUP) {
-                        const ElemForceRegrouped<T> e = elem_force_nonlinear_regrouped<T>(ec, k ? sq[k - 1] : qL, sq[k]);
+                        const ElemForceRegrouped<T> e = CHORD ? elem_force_nonlinear_chord<T>(ec, k ? sq[k - 1] : qL, sq[k])
+                                                              : elem_force_nonlinear_regrouped<T>(ec, k ? sq[k - 1] : qL, sq[k]);
                         f2[k] = e.f2; cW[k] = ec[1] * e.W;
                         fl[k][1] = e.f3; fr[k][1] = -e.f3; fl[k][2] = e.m_left; fr[k][2] = e.m_right;
                     } else if (EM == EM_NONLINEAR) elem_force_nonlinear<T>(ec, k ? sq[k - 1] : qL, sq[k], false, fl[k], fr[k]);
@@ -404,7 +442,7 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                 //    written as an opaque block per node because a C++ branch here splits the stage's straight-line code, which
                 //    the scheduler then no longer interleaves with the solve (measured: 50 spilled VGPRs).  No lane shift inside.
                 //    After a compiler upgrade re-check with `make resource-usage`: this kernel at 0 SGPR spills, <= 256 VGPRs
-                //    (240 with the regrouped axial pair, 98 SGPRs), no scratch.  The block can go back to the C++ form of the host branch below once that no longer splits the
+                //    (250 with the chord forces and the RK4 positions on the accelerations, 90 SGPRs), no scratch.  The block can go back to the C++ form of the host branch below once that no longer splits the
                 //    schedule (same resource figures, same step time).
                 {
                     const int kon = imp_on ? kimp : -1, dof = q.imp_dof;
@@ -545,10 +583,19 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                 for (int k = 0; k < NP; ++k)
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
-                        accv[k][c] = (s == 0) ? a[k][c] : accv[k][c] + w * a[k][c];
-                        if (k == NP - 1) sq[k][c] = qn3[c];
-                        else sq[k][c] = (s == 3) ? (xq[k][c] + dt6 * accq[k][c]) : (xq[k][c] + cs * sv[k][c]);
-                        sv[k][c] = (s == 3) ? (xv[k][c] + dt6 * accv[k][c]) : (xv[k][c] + cs * a[k][c]);
+                        if constexpr (RKPOS) {
+                            sq[k][c] = rk[k][c].next;
+                            if (s == 0) rk4_end0<T>(rk[k][c], a[k][c], c6, c4);
+                            else if (s == 1) rk4_end1<T>(rk[k][c], a[k][c], c6, c2);
+                            else if (s == 2) rk4_end2<T>(rk[k][c], a[k][c], c6);
+                            else xv[k][c] = rk4_end3<T>(rk[k][c], xv[k][c], a[k][c], dt6);
+                            if (c == 1 && s < 3) sv[k][1] = rk4_stage_velocity<T>(xv[k][1], cs, a[k][1]);
+                        } else {
+                            accv[k][c] = (s == 0) ? a[k][c] : accv[k][c] + w * a[k][c];
+                            if (k == NP - 1) sq[k][c] = qn3[c];
+                            else sq[k][c] = (s == 3) ? (xq[k][c] + dt6 * accq[k][c]) : (xq[k][c] + cs * sv[k][c]);
+                            sv[k][c] = (s == 3) ? (xv[k][c] + dt6 * accv[k][c]) : (xv[k][c] + cs * a[k][c]);
+                        }
                     }
 #pragma unroll
                 for (int c = 0; c < 3; ++c) qL[c] = qLn[c];
@@ -556,7 +603,10 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
 #pragma unroll
             for (int k = 0; k < NP; ++k)
 #pragma unroll
-                for (int c = 0; c < 3; ++c) { xq[k][c] = sq[k][c]; xv[k][c] = sv[k][c]; }
+                for (int c = 0; c < 3; ++c) {
+                    xq[k][c] = sq[k][c];
+                    if (!RKPOS) xv[k][c] = sv[k][c];
+                }
             tc = t_full;
             KPT kr_ = kp;
             CRB_BFRESH(kr_);

@@ -240,6 +240,110 @@ CRB_HD ElemForceRegrouped<T> elem_force_nonlinear_regrouped(const T* c, const T 
     return o;
 }
 
+// The regrouped form once more, in chord-relative variables: e = s - 2 dw is L times the sum of the two end rotations
+// measured from the element's chord (3 e is the g above), d = a - b as before, U = L du.  With s = e + 2 dw and
+// p = (s^2 - d^2) / 4 every polynomial loses monomials, and neither p nor s dw is formed:
+//   E  = dw^2/2 - U + d^2/24 + e^2/40                                      (f2 = cA1 E)
+//   LT = L + e/20 - dw/2                                                    (W = u2 LT)
+//   P3 = e (U + 3/56 d^2 - 3/2 dw^2 - e^2/56) + dw (3/4 d^2 - 10 U + 5 dw^2 + 15/28 e^2)
+//   S  = e (11/560 d^2 - U/10 + 3/20 dw^2 + 3/560 e^2) + dw (d^2/20 + 3/140 e^2)
+//   R  = d^2/80 - U/6 + 11/560 e^2 + dw (dw/4 + e/10)
+// identically equal to the polynomials of elem_force_nonlinear_regrouped in rational arithmetic (tests/test_chord_forces_cpu.py
+// checks the identities and bounds the rounding of both forms against exact values).  48 fp64 instructions per element
+// against 52; the roundings differ from the other forms' in order and are fewer.  Every sum is an explicit chain, so that host
+// and device round alike up to contraction.  The blocked stepper (crb_lean.h) is the caller; the same five values come back.
+template <typename T>
+CRB_HD ElemForceRegrouped<T> elem_force_nonlinear_chord(const T* c, const T ql[3], const T qr[3]) {
+    const T L = c[0], cA1 = c[1], cA3 = c[2], cD3 = c[3], cA4 = c[4], cD4 = c[5];
+    const T u2 = qr[0];
+    const T a = ql[2] * L, b = qr[2] * L;
+    const T du = ql[0] - u2, dw = ql[1] - qr[1];
+    const T s = a + b, d = a - b;
+    const T e = s - T(2.0) * dw;
+    const T e2 = e * e, d2 = d * d, dw2 = dw * dw, U = L * du;
+
+    T E = T(0.5) * dw2 - U;
+    E = E + T(1.0 / 24.0) * d2;
+    E = E + T(1.0 / 40.0) * e2;
+    T LT = L + T(0.05) * e;
+    LT = LT - T(0.5) * dw;
+
+    T P3e = U + T(3.0 / 56.0) * d2;
+    P3e = P3e - T(1.5) * dw2;
+    P3e = P3e - T(1.0 / 56.0) * e2;
+    T P3w = T(0.75) * d2 - T(10.0) * U;
+    P3w = P3w + T(5.0) * dw2;
+    P3w = P3w + T(15.0 / 28.0) * e2;
+    const T P3 = e * P3e + dw * P3w;
+    const T g = T(3.0) * e;
+    T Se = T(11.0 / 560.0) * d2 - T(0.1) * U;
+    Se = Se + T(0.15) * dw2;
+    Se = Se + T(3.0 / 560.0) * e2;
+    const T Sw = T(0.05) * d2 + T(3.0 / 140.0) * e2;
+    const T S = e * Se + dw * Sw;
+    T R = T(1.0 / 80.0) * d2 - T(1.0 / 6.0) * U;
+    R = R + T(11.0 / 560.0) * e2;
+    R = R + dw * (T(0.25) * dw + T(0.1) * e);
+    const T X = cA4 * S + cD4 * g;
+    const T Y = d * (cA4 * R + cD4);
+
+    ElemForceRegrouped<T> o;
+    o.f2 = cA1 * E;
+    o.W = u2 * LT;
+    o.f3 = cA3 * P3 - cD3 * g;
+    o.m_left = X + Y;
+    o.m_right = X - Y;
+    return o;
+}
+
+// Classical RK4 of a second-order system q' = v, v' = a(q, v), per component, with the position side carried on the
+// accelerations alone: with a_i the acceleration of stage i (evaluated at q_i and the stage velocity v_i),
+//   q_2 = q + dt/2 v     q_3 = q_2 + dt^2/4 a_1     q_4 = (q + dt v) + dt^2/2 a_2
+//   q'  = (q + dt v) + dt^2/6 (a_1 + a_2 + a_3)     v' = v + dt/6 (a_1 + 2 a_2 + 2 a_3 + a_4)
+// which is what the velocity sums of the textbook bookkeeping (sv = v + cs a, accq += w sv) expand to.  A caller whose force
+// reads the stage velocity of some components only (the drag: w) forms v_i = v + cs a_{i-1} (rk4_stage_velocity) for those
+// alone.  Rk4Pos is one component's registers over a step; the four stage ends take the stage's acceleration.  The next
+// stage's position is `next` from the top of each stage on, and the state after the step is (next, v) after rk4_end3.
+//   c6, c4, c2 = dt^2/6, dt^2/4, dt^2/2; hdt, dt6 = dt/2, dt/6.
+template <typename T>
+struct Rk4Pos {
+    T next;   // the next stage's position: q_2, q_3, q_4, q'
+    T full;   // q + dt v, then q_4 in its place
+    T sum;    // q + dt v + dt^2/6 (a_1 [+ a_2]), the running q'
+    T accv;   // a_1 + 2 a_2 + 2 a_3
+};
+template <typename T>
+CRB_HD void rk4_begin(Rk4Pos<T>& r, T q, T v, T hdt, T dt) {
+    r.next = q + hdt * v;
+    r.full = q + dt * v;
+}
+template <typename T>
+CRB_HD void rk4_end0(Rk4Pos<T>& r, T a, T c6, T c4) {
+    r.accv = a;
+    r.sum = r.full + c6 * a;
+    r.next = r.next + c4 * a;
+}
+template <typename T>
+CRB_HD void rk4_end1(Rk4Pos<T>& r, T a, T c6, T c2) {
+    r.accv = r.accv + T(2) * a;
+    r.sum = r.sum + c6 * a;
+    r.full = r.full + c2 * a;
+    r.next = r.full;
+}
+template <typename T>
+CRB_HD void rk4_end2(Rk4Pos<T>& r, T a, T c6) {
+    r.accv = r.accv + T(2) * a;
+    r.next = r.sum + c6 * a;
+}
+template <typename T>
+CRB_HD T rk4_end3(const Rk4Pos<T>& r, T v, T a, T dt6) {   // v'
+    return v + dt6 * (r.accv + a);
+}
+template <typename T>
+CRB_HD T rk4_stage_velocity(T v, T cs, T a) {
+    return v + cs * a;
+}
+
 #ifndef CRB_LITERAL_POLY
 #define CRB_LITERAL_POLY 0
 #endif

@@ -83,6 +83,12 @@ class ParamCotangent(C.Structure):
     _fields_ = [("param_bar", C.c_void_p)]
 
 
+class FeedbackCotangent(C.Structure):
+    """crb_feedback_cotangent: accumulated cotangents of the closed loop's gain ([n_cot][n][2n]) and reference ([n_cot][B][2n]
+    reduced), device pointers or None"""
+    _fields_ = [("gain_bar", C.c_void_p), ("ref_bar", C.c_void_p)]
+
+
 class RecordDesc(C.Structure):
     _fields_ = [("plane", C.c_int32), ("node", C.c_int32), ("dof", C.c_int32), ("every", C.c_int32), ("out", C.c_void_p)]
 
@@ -195,6 +201,12 @@ def load():
     L.crb_step_rk4_adjoint_params_sched.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, i32, i32, C.POINTER(InputDesc),
                                                     C.POINTER(RecordDesc), C.POINTER(InputCotangent),
                                                     C.POINTER(ParamCotangent), sched, vp, vp, vp]
+    L.crb_rk4_feedback_adjoint_work_bytes.restype = C.c_size_t
+    L.crb_rk4_feedback_adjoint_work_bytes.argtypes = [vp, i32, i32]
+    L.crb_step_rk4_feedback_checkpoint.argtypes = [vp, vp, C.c_double, C.c_double, i32, i32, vp, vp, C.POINTER(InputDesc),
+                                                   C.POINTER(RecordDesc), vp, vp, _dp, vp]
+    L.crb_step_rk4_feedback_adjoint.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, i32, i32, vp, vp, C.POINTER(InputDesc),
+                                                C.POINTER(RecordDesc), C.POINTER(FeedbackCotangent), vp, vp]
     L.crb_step_rk4_feedback.argtypes = [vp, vp, C.c_double, C.c_double, i32, vp, vp, C.POINTER(InputDesc), vp,
                                         C.POINTER(C.c_double), vp]
     _lib = L

@@ -750,17 +750,22 @@ class BeamEnsemble:
         return (xb[0], ub[0]) if single else (xb, ub)
 
     def checkpoint_interval(self, n_steps: int, checkpoint_every: Optional[int] = None,
-                            param_cotangents: Optional[int] = None) -> int:
+                            param_cotangents: Optional[int] = None, feedback_cotangents: Optional[int] = None) -> int:
         """Steps per checkpoint segment of an adjoint rollout: ``checkpoint_every``, or ceil(sqrt(n_steps)) lowered until the
         work buffer of crb_step_rk4_adjoint (crb_rk4_adjoint_work_bytes) fits ADJOINT_WORK_BUDGET.  ``param_cotangents``: the
         number of cotangents of a ``step_adjoint_params`` call, whose work buffer
-        (crb_rk4_adjoint_params_work_bytes) is sized instead."""
+        (crb_rk4_adjoint_params_work_bytes) is sized instead; ``feedback_cotangents``: that of a ``step_feedback_adjoint`` call
+        (crb_rk4_feedback_adjoint_work_bytes)."""
         if checkpoint_every is not None:
             if int(checkpoint_every) < 1:
                 raise ValueError("checkpoint_every must be >= 1")
             return int(checkpoint_every)
         every = max(1, int(np.ceil(np.sqrt(max(int(n_steps), 1)))))
-        if param_cotangents is None:
+        if feedback_cotangents is not None:
+            if param_cotangents is not None:
+                raise ValueError("checkpoint_interval: param_cotangents and feedback_cotangents are given together")
+            work_bytes = lambda e: self._lib.crb_rk4_feedback_adjoint_work_bytes(self.plan.h, e, int(feedback_cotangents))  # noqa: E731
+        elif param_cotangents is None:
             work_bytes = lambda e: self._lib.crb_rk4_adjoint_work_bytes(self.plan.h, e)  # noqa: E731
         else:
             work_bytes = lambda e: self._lib.crb_rk4_adjoint_params_work_bytes(self.plan.h, e, int(param_cotangents))  # noqa: E731
@@ -919,7 +924,7 @@ class BeamEnsemble:
           gravity         [B, 2]          dL/d (g_x, g_y), summed over the segments
         Entries past a beam's own element / node count (mixed-topology ensembles) are zero.  Not available: gradients with
         respect to length, cross_area and density (they enter the mass matrix and its reduction tables), parameters as
-        autograd inputs of ``rollout`` (its forward would need parameter overrides), and the closed loop."""
+        autograd inputs of ``rollout`` (its forward would need parameter overrides)."""
         return self._step_adjoint(True, n_steps, dt, lam_red, x0_red, impulse_amp, impulse_duration, impulse_index, held_force,
                                   t0, record, record_every, lam_record, checkpoint_every, control, control_hold)
 
@@ -964,6 +969,109 @@ class BeamEnsemble:
                     index=int(impulse_index), record=record, record_every=int(record_every),
                     every=self.checkpoint_interval(n_steps, checkpoint_every), hold=hold)
         xT, samples = _Rollout.apply(self, opts, x0, amp, held, ctrl)
+        return (xT, samples) if record is not None else xT
+
+    # ------------------------------------------------------------------ adjoint of the closed loop (crb_feedback_adjoint.h)
+    def _feedback_gain(self, gain, who):
+        """the one [n, 2n] gain of a differentiable closed loop on the device"""
+        if isinstance(gain, (list, tuple)):
+            raise NotImplementedError(f"{who}: a list of gains (per-beam or grouped gains) is not differentiable; pass one "
+                                      f"[{self.n}, {2 * self.n}] gain for the whole ensemble")
+        return self._dev(gain.detach() if isinstance(gain, torch.Tensor) else gain, (self.n, 2 * self.n))
+
+    def _feedback_adjoint_work(self, every, n_cot):
+        nbytes = int(self._lib.crb_rk4_feedback_adjoint_work_bytes(self.plan.h, int(every), int(n_cot)))
+        return torch.empty((max(1, nbytes) + 7) // 8, dtype=torch.float64, device=self.device)
+
+    def _feedback_checkpoint(self, x, n_steps, dt, t0, K, ref, desc, every, rec):
+        """crb_step_rk4_feedback_checkpoint on the device state ``x`` (advanced in place): returns the checkpoint buffer"""
+        nseg = max(1, -(-int(n_steps) // every))
+        ckpt = torch.empty((nseg,) + tuple(self.state.shape), dtype=self.dtype, device=self.device)
+        work = self._feedback_adjoint_work(every, 1)
+        t_end = C.c_double(0.0)
+        with self._on_device():
+            nat.check(self._lib.crb_step_rk4_feedback_checkpoint(self.plan.h, self._ptr(x), float(t0), float(dt), int(n_steps),
+                                                                 int(every), self._ptr(K), self._ptr(ref), C.byref(desc),
+                                                                 self._ref(rec), self._ptr(ckpt), self._ptr(work),
+                                                                 C.byref(t_end), self._stream()))
+        self._keep = [work, K, ref, x]
+        return ckpt
+
+    def _feedback_adjoint(self, ckpt, lamd, n_steps, dt, t0, K, ref, desc, every, rec_bar, want_gain=True):
+        """crb_step_rk4_feedback_adjoint: lamd [D, B, 2, n_node, 4] in place; returns (gain_bar [D, n, 2n] or None,
+        ref_bar [D, B, 2n])"""
+        D = lamd.shape[0]
+        grad = nat.FeedbackCotangent()
+        gain_bar = torch.zeros((D, self.n, 2 * self.n), dtype=self.dtype, device=self.device) if want_gain else None
+        ref_bar = torch.zeros((D, self.n_beams, 2 * self.n), dtype=self.dtype, device=self.device)
+        grad.gain_bar = gain_bar.data_ptr() if gain_bar is not None else None
+        grad.ref_bar = ref_bar.data_ptr()
+        work = self._feedback_adjoint_work(every, D)
+        with self._on_device():
+            nat.check(self._lib.crb_step_rk4_feedback_adjoint(self.plan.h, self._ptr(ckpt), self._ptr(lamd), int(D), float(t0),
+                                                              float(dt), int(n_steps), int(every), self._ptr(K), self._ptr(ref),
+                                                              C.byref(desc), self._ref(rec_bar), C.byref(grad), self._ptr(work),
+                                                              self._stream()))
+        self._keep = [work, ckpt, lamd, K, ref, gain_bar, ref_bar]
+        return gain_bar, ref_bar
+
+    def step_feedback_adjoint(self, n_steps: int, dt: float, lam_red, gain, reference=None, x0_red=None, impulse_amp=None,
+                              impulse_duration: float = 0.01, impulse_index: int = -2, held_force=None,
+                              t0: Optional[float] = None, record=None, record_every: int = 1, lam_record=None,
+                              checkpoint_every: Optional[int] = None, want_gain: bool = True):
+        """Gradient of a scalar loss through the closed-loop rollout of ``step_feedback`` -- u = K (r - x) in every RK4 stage,
+        examples/lqr_control.py:95-125 -- with respect to the start state, the gain and the reference, in ONE backward sweep
+        (crb_step_rk4_feedback_checkpoint + crb_step_rk4_feedback_adjoint): for the cotangent ``lam_red`` = dL/dx(T) (reduced
+        [B, 2n], or D cotangents [D, B, 2n]) and, with ``record`` = (node, name) as in step(), ``lam_record`` = dL/d samples,
+        returns (xbar0 [B, 2n], gain_bar [n, 2n], ref_bar [B, 2n]), with a leading D axis when ``lam_red`` has one.
+        ``gain`` [n, 2n] is one gain for the whole ensemble (a list of gains raises NotImplementedError); ``reference``
+        [B, 2n] or None (= 0; ref_bar is returned all the same).  ``impulse_amp`` and ``held_force`` [B, n] are disturbances
+        added to u; they are not differentiated.  The rollout starts at ``x0_red`` (None: the resident state) and clock
+        ``t0`` (None: ``time``) and always runs the stage-split launches; ``state``, ``time`` and ``status`` are left alone.
+        ``checkpoint_every``: steps per checkpoint segment; the result does not depend on it, bitwise.  ``want_gain=False``
+        skips the gain-gradient product (gain_bar is None; the other returns are bitwise the same).  A non-finite cotangent
+        of one beam stays in that beam's rows of xbar0 and ref_bar but reaches gain_bar, a sum over the beams.  fp64
+        ensembles with one free-DOF set only."""
+        lam, single = self._dirs(lam_red, 2 * self.n, "step_feedback_adjoint: lam_red")
+        D = lam.shape[0]
+        K = self._feedback_gain(gain, "step_feedback_adjoint")
+        ref = None if reference is None else self._dev(reference, (self.n_beams, 2 * self.n))
+        if record is not None and isinstance(record, str):
+            raise NotImplementedError("step_feedback_adjoint: whole-state snapshots (record='all') are not available in the closed loop")
+        t0 = self.time if t0 is None else float(t0)
+        every = self.checkpoint_interval(n_steps, checkpoint_every, feedback_cotangents=D)
+        desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index, held_force)
+        x = self.state.clone() if x0_red is None else self.pack_state(x0_red)
+        ckpt = self._feedback_checkpoint(x, n_steps, dt, t0, K, ref, desc, every, None)
+        rec_bar, cot = self._record_cotangent(record, n_steps, record_every, lam_record, D)
+        lamd = self._pack_dirs(lam, True)
+        gain_bar, ref_bar = self._feedback_adjoint(ckpt, lamd, n_steps, dt, t0, K, ref, desc, every, rec_bar, want_gain)
+        self._keep += keep + [x, cot]
+        xb = self._unpack_dirs(lamd)
+        if single:
+            return xb[0], (gain_bar[0] if gain_bar is not None else None), ref_bar[0]
+        return xb, gain_bar, ref_bar
+
+    def rollout_feedback(self, x0_red, n_steps: int, dt: float, gain, reference=None, impulse_amp=None,
+                         impulse_duration: float = 0.01, impulse_index: int = -2, held_force=None, t0: float = 0.0,
+                         record=None, record_every: int = 1, checkpoint_every: Optional[int] = None):
+        """A differentiable closed-loop rollout: x(T) reduced [B, 2n] from ``x0_red`` after ``n_steps`` RK4 steps with
+        u = K (r - x) in every stage (``step_feedback``'s map in its stage-split form; and the ``record`` = (node, name)
+        samples [B, n_steps // record_every]), as a torch.autograd.Function whose backward is crb_step_rk4_feedback_adjoint:
+        ``loss.backward()`` reaches whichever of ``x0_red``, ``gain`` [n, 2n] and ``reference`` [B, 2n] require grad -- tuning
+        an LQR gain on the nonlinear rod (examples/tune_gain.py).  ``impulse_amp`` and ``held_force`` are disturbances, not
+        differentiated.  Leaves ``state``, ``time`` and ``status`` alone.  fp64 ensembles only; once differentiable."""
+        if isinstance(gain, (list, tuple)):
+            self._feedback_gain(gain, "rollout_feedback")
+        if record is not None and isinstance(record, str):
+            raise NotImplementedError("rollout_feedback: whole-state snapshots (record='all') are not available in the closed loop")
+        x0 = torch.as_tensor(x0_red, dtype=self.dtype, device=self.device)
+        K = torch.as_tensor(gain, dtype=self.dtype, device=self.device)
+        ref = None if reference is None else torch.as_tensor(reference, dtype=self.dtype, device=self.device)
+        opts = dict(n_steps=int(n_steps), dt=float(dt), t0=float(t0), amp=impulse_amp, duration=float(impulse_duration),
+                    index=int(impulse_index), held=held_force, record=record, record_every=int(record_every),
+                    every=self.checkpoint_interval(n_steps, checkpoint_every, feedback_cotangents=1))
+        xT, samples = _FeedbackRollout.apply(self, opts, x0, K, ref)
         return (xT, samples) if record is not None else xT
 
     def step_implicit(self, n_steps: int, h: float, n_iter: int = 2, impulse_amp=None, impulse_duration: float = 0.01,
@@ -1551,3 +1659,43 @@ class _Rollout(torch.autograd.Function):
         gheld = ens._unpack_force_dirs(f_bar)[0] if (ctx.has_held and ctx.needs_input_grad[4]) else None
         gctrl = ens._unpack_sched_dirs(f_bar)[0] if (ctx.has_ctrl and ctx.needs_input_grad[5]) else None
         return None, None, gx0, gamp, gheld, gctrl
+
+
+class _FeedbackRollout(torch.autograd.Function):
+    """BeamEnsemble.rollout_feedback: forward = crb_step_rk4_feedback_checkpoint, backward = crb_step_rk4_feedback_adjoint on
+    the saved checkpoints"""
+
+    @staticmethod
+    def forward(ctx, ens, opts, x0, gain, ref):
+        K = ens._feedback_gain(gain, "rollout_feedback")
+        r = None if ref is None else ens._dev(ref.detach(), (ens.n_beams, 2 * ens.n))
+        desc, keep = ens._input_desc(opts["amp"], opts["duration"], opts["index"], opts["held"])
+        x = ens.pack_state(x0.detach())
+        rec, samples = ens._record_desc(opts["record"], opts["n_steps"], opts["record_every"])
+        ckpt = ens._feedback_checkpoint(x, opts["n_steps"], opts["dt"], opts["t0"], K, r, desc, opts["every"], rec)
+        ens._keep += keep + [samples]
+        ctx.ens, ctx.opts, ctx.has_ref = ens, opts, ref is not None
+        ctx.save_for_backward(ckpt, K, r)
+        if samples is None:
+            samples = torch.zeros(0, dtype=ens.dtype, device=ens.device)
+        if opts["record"] is None:
+            ctx.mark_non_differentiable(samples)
+        return ens.unpack_state(x), samples
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_x, g_samples):
+        ens, o = ctx.ens, ctx.opts
+        ckpt, K, r = ctx.saved_tensors
+        desc, keep = ens._input_desc(o["amp"], o["duration"], o["index"], o["held"])
+        g_x = torch.zeros((ens.n_beams, 2 * ens.n), dtype=ens.dtype, device=ens.device) if g_x is None else g_x
+        lamd = ens._pack_dirs(g_x.to(ens.dtype).reshape(1, ens.n_beams, 2 * ens.n).contiguous(), True)
+        rec_bar, cot = ens._record_cotangent(o["record"], o["n_steps"], o["record_every"],
+                                             g_samples if o["record"] is not None else None, 1)
+        gain_bar, ref_bar = ens._feedback_adjoint(ckpt, lamd, o["n_steps"], o["dt"], o["t0"], K, r, desc, o["every"], rec_bar,
+                                                  ctx.needs_input_grad[3])
+        ens._keep += keep + [cot]
+        gx0 = ens._unpack_dirs(lamd)[0] if ctx.needs_input_grad[2] else None
+        ggain = gain_bar[0] if ctx.needs_input_grad[3] else None
+        gref = ref_bar[0] if (ctx.has_ref and ctx.needs_input_grad[4]) else None
+        return None, None, gx0, ggain, gref

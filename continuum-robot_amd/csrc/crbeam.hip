@@ -19,6 +19,7 @@
 #include "crb_static_launch.h"
 #include "crb_tangent_launch.h"
 #include "crb_adjoint_launch.h"
+#include "crb_feedback_adjoint_launch.h"
 #include "crb_host.h"
 #include "crb_blocked.h"
 
@@ -1836,22 +1837,23 @@ namespace {
 // force: the forcing's f_held is not read here
 template <typename T>
 int rk4_stage_impl(const crb_plan* p, void* x, const void* xs, void* acc, void* xs_next, const void* u_stage, int stage,
-                   double t_stage, double dt, const Forcing& f, hipStream_t st) {
+                   double t_stage, double dt, const Forcing& f, hipStream_t st, bool report) {
     KParams<T> k = base_params<T>(p);
     k.x = static_cast<T*>(x); k.xs = static_cast<const T*>(xs); k.acc = static_cast<T*>(acc);
     k.out = static_cast<T*>(xs_next);
     set_io(k, f);
     k.u_held = static_cast<const T*>(u_stage);
     k.stage = stage; k.t0 = t_stage; k.dt = dt;
-    if (stage == 3) arm_status(p, k, 1);
+    if (stage == 3 && report) arm_status(p, k, 1);
     if (lean_stage_ok(p)) return launch_stage_lean<T>(p, k, st);
     return launch_beam<T, MODE_STAGE>(p, k, st);
 }
+// report: stage 3 marks non-finite beams in the plan's status words (the differentiable rollouts leave the status alone)
 int rk4_stage(const crb_plan* p, void* x, const void* xs, void* acc, void* xs_next, const void* u_stage, int stage, double t_stage,
-              double dt, const Forcing& f, void* stream) {
+              double dt, const Forcing& f, void* stream, bool report = true) {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return p->dtype == CRB_F64 ? rk4_stage_impl<double>(p, x, xs, acc, xs_next, u_stage, stage, t_stage, dt, f, st)
-                               : rk4_stage_impl<float>(p, x, xs, acc, xs_next, u_stage, stage, t_stage, dt, f, st);
+    return p->dtype == CRB_F64 ? rk4_stage_impl<double>(p, x, xs, acc, xs_next, u_stage, stage, t_stage, dt, f, st, report)
+                               : rk4_stage_impl<float>(p, x, xs, acc, xs_next, u_stage, stage, t_stage, dt, f, st, report);
 }
 
 // The stage-split closed loop: per RK4 stage the feedback force of the stage state (force(xs, u): one GEMM over the ensemble,
@@ -2734,4 +2736,219 @@ extern "C" int crb_step_rk4_adjoint_params_sched(const crb_plan* p, const void* 
                                                  void* sched_bar, void* work, void* stream) {
     return adjoint_rollout(sched ? "crb_step_rk4_adjoint_params_sched" : "crb_step_rk4_adjoint_params", p, ckpt, lam, n_cot, t0,
                            dt, n_steps, every, in, rec_bar, grad, true, pgrad, sched, sched_bar, work, stream);
+}
+
+// ------------------------------------------------------------------ adjoint of the closed loop (crb_feedback_adjoint.h)
+namespace {
+// The work buffer of the closed-loop checkpoint pass and adjoint (crb_rk4_feedback_adjoint_work_bytes), in doubles.
+struct FbAdjWork {
+    double *stages, *acc, *xcur, *u, *seed, *xbar, *sum, *ubar, *partial;
+};
+// doubles of the gain gradient's partial tiles (0 while one slice covers the beam reduction)
+size_t fb_adj_partial_doubles(const crb_plan* p, int n_cot) {
+    const int slices = crb::feedback_gain_grad_slices(p->B, p->n_free);
+    return slices > 1 ? size_t(n_cot) * size_t(slices) * size_t(p->n_free) * size_t(2 * p->n_free) : 0;
+}
+FbAdjWork fb_adj_work(const crb_plan* p, void* work, int every, int n_cot) {
+    const size_t S = state_doubles(p), F = S / 2;
+    FbAdjWork w;
+    w.stages = static_cast<double*>(work);
+    w.acc = w.stages + size_t(every) * 4 * S;
+    w.xcur = w.acc + S;
+    w.u = w.xcur + S;
+    w.seed = w.u + F;
+    w.xbar = w.seed + size_t(n_cot) * S;
+    w.sum = w.xbar + size_t(n_cot) * S;
+    w.ubar = w.sum + size_t(n_cot) * S;
+    w.partial = w.ubar + size_t(n_cot) * F;
+    return w;
+}
+
+// the plan, size and input checks both calls share, before the device is touched
+int fb_adj_checks(const crb_plan* p, int n_cot, const void* gain, const crb_input_desc* in, const crb_record_desc* rec, int n_steps,
+                  int every, double dt, const std::string& who) {
+    if (int rc = adjoint_checks(p, n_cot, who.c_str())) return rc;
+    if (p->mixed_topology)
+        return fail(CRB_EUNSUPPORTED, who + ": one gain for the ensemble needs one free-DOF set (the plan has mixed topology)");
+    if (p->flags & CRB_FORCE_GRAVITY) {
+        std::vector<GravAdj> lists;
+        for (const auto& tab : p->h_grav_topo) {
+            int ms = 0, mp = 0;
+            if (!grav_transpose(tab, lists, &ms, &mp))
+                return fail(CRB_EUNSUPPORTED, who + ": the gravity index table has a fan-in of " + std::to_string(ms) + " / " +
+                                                  std::to_string(mp) + ", beyond the adjoint's lists (crb_rhs_vjp refuses the plan)");
+        }
+    }
+    if (rec && rec->node == CRB_RECORD_ALL)
+        return fail(CRB_EUNSUPPORTED, who + ": rec with CRB_RECORD_ALL (whole-state snapshots) is not supported in the closed loop");
+    if (!gain) return fail(CRB_EINVAL, who + ": gain is null");
+    if (n_steps < 0) return fail(CRB_EINVAL, who + ": n_steps must be >= 0");
+    if (every < 1) return fail(CRB_EINVAL, who + ": every must be >= 1");
+    if (!(dt > 0)) return fail(CRB_EINVAL, who + ": dt must be positive");
+    return CRB_OK;
+}
+
+// one RK4 step of the stage-split closed loop from xcur (advanced in place): feedback_rollout's launches (plus the held
+// disturbance, if any, added to each stage's force), the stage states
+// X_2 .. X_4 written to s1 .. s3 (stage 3's unused xs_next goes to `spare`)
+int fb_adj_step(const crb_plan* p, void* xcur, double* s1, double* s2, double* s3, double* spare, const FbAdjWork& w, double t,
+                double dt, const void* gain, const void* ref, const Forcing& f, void* stream) {
+    const double th = t + 0.5 * dt, t1 = t + dt;   // same clock convention as crb_step_rk4
+    const double ts[4] = {t, th, th, t1};
+    void* const nxt[4] = {s1, s2, s3, spare};
+    const void* cur = xcur;
+    for (int stage = 0; stage < 4; ++stage) {
+        if (int rc = crb_feedback_force(p, cur, gain, ref, w.u, stream)) return rc;
+        if (f.held)   // (a held disturbance: crb_rk4_stage reads the stage force in the held force's place)
+            HIP_TRY(crb::launch_feedback_held(w.u, static_cast<const double*>(f.held), p->d_row_off, p->n_free, p->B,
+                                              size_t(p->n_node) * 4, static_cast<hipStream_t>(stream)));
+        if (int rc = rk4_stage(p, xcur, cur, w.acc, nxt[stage], w.u, stage, ts[stage], dt, f, stream, false)) return rc;
+        cur = nxt[stage];
+    }
+    return CRB_OK;
+}
+}  // namespace
+
+extern "C" size_t crb_rk4_feedback_adjoint_work_bytes(const crb_plan* p, int every, int n_cot) {
+    if (!p || every < 1 || n_cot < 1) return 0;
+    const size_t S = state_doubles(p), F = S / 2;
+    return ((size_t(4) * size_t(every) + 2 + 3 * size_t(n_cot)) * S + (1 + size_t(n_cot)) * F + fb_adj_partial_doubles(p, n_cot)) *
+           sizeof(double);
+}
+
+extern "C" int crb_step_rk4_feedback_checkpoint(const crb_plan* p, void* x, double t0, double dt, int n_steps, int every,
+                                                const void* gain, const void* ref, const crb_input_desc* in,
+                                                const crb_record_desc* rec, void* ckpt, void* work, double* t_end, void* stream) {
+    const std::string who("crb_step_rk4_feedback_checkpoint");
+    if (int rc = fb_adj_checks(p, 1, gain, in, rec, n_steps, every, dt, who)) return rc;
+    if (!x) return fail(CRB_EINVAL, who + ": x is null");
+    if (!ckpt) return fail(CRB_EINVAL, who + ": ckpt is null");
+    if (!work) return fail(CRB_EINVAL, who + ": work is null (crb_rk4_feedback_adjoint_work_bytes)");
+    const void* ins[4] = {gain, ref, rec ? rec->out : nullptr, in ? in->f_held : nullptr};
+    for (const void* b : ins)
+        if (b && (b == x || b == ckpt || b == work)) return fail(CRB_EINVAL, who + ": x, ckpt and work must not alias gain, ref, rec->out or input->f_held");
+    if (x == ckpt || x == work || ckpt == work) return fail(CRB_EINVAL, who + ": x, ckpt and work must not alias each other");
+    if (int rc = need_device(p, who.c_str())) return rc;
+    Recording r;
+    if (int rc = decode_record(p, rec, n_steps, true, who.c_str(), &r)) return rc;
+    Forcing f;
+    if (int rc = decode_input(p, in, who.c_str(), &f)) return rc;
+    if (t_end) *t_end = clock_after(t0, dt, n_steps);
+    if (n_steps == 0) return CRB_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t S = state_doubles(p), x_stride = size_t(2) * p->n_node * 4;
+    const FbAdjWork w = fb_adj_work(p, work, 1, 1);
+    HIP_TRY(hipMemsetAsync(w.u, 0, S / 2 * sizeof(double), st));   // (entries of u no product writes must read as zero)
+    const size_t rec_off = r.slot >= 0 ? (size_t(r.comp / 3) * p->n_node + size_t(r.slot + p->off)) * 4 + size_t(r.comp % 3) : 0;
+    double t = t0;
+    for (int s = 0; s < n_steps; ++s) {
+        if (s % every == 0)
+            HIP_TRY(hipMemcpyAsync(static_cast<double*>(ckpt) + size_t(s / every) * S, x, S * sizeof(double), hipMemcpyDeviceToDevice, st));
+        if (int rc = fb_adj_step(p, x, w.stages, w.stages + S, w.stages + 2 * S, w.stages + 3 * S, w, t, dt, gain, ref, f, stream)) return rc;
+        t = t + dt;
+        if (r.slot >= 0 && (s + 1) % r.every == 0 && (s + 1) / r.every <= r.count)
+            HIP_TRY(crb::launch_feedback_record(static_cast<const double*>(x), x_stride, rec_off, p->B, static_cast<double*>(r.out),
+                                                r.count, (s + 1) / r.every - 1, st));
+    }
+    return CRB_OK;
+}
+
+extern "C" int crb_step_rk4_feedback_adjoint(const crb_plan* p, const void* ckpt, void* lam, int n_cot, double t0, double dt,
+                                             int n_steps, int every, const void* gain, const void* ref, const crb_input_desc* in,
+                                             const crb_record_desc* rec_bar, const crb_feedback_cotangent* grad, void* work,
+                                             void* stream) {
+    const std::string who("crb_step_rk4_feedback_adjoint");
+    if (int rc = fb_adj_checks(p, n_cot, gain, in, rec_bar, n_steps, every, dt, who)) return rc;
+    if (!lam) return fail(CRB_EINVAL, who + ": lam is null");
+    if (!ckpt) return fail(CRB_EINVAL, who + ": ckpt is null");
+    if (!work) return fail(CRB_EINVAL, who + ": work is null (crb_rk4_feedback_adjoint_work_bytes)");
+    if (!grad) return fail(CRB_EINVAL, who + ": grad is null (crb_feedback_cotangent; its members may be null)");
+    const void* const outs[3] = {lam, grad->gain_bar, grad->ref_bar};
+    const char* const out_names[3] = {"lam", "grad->gain_bar", "grad->ref_bar"};
+    const void* const ins[6] = {ckpt, work, gain, ref, rec_bar ? rec_bar->out : nullptr, in ? in->f_held : nullptr};
+    for (int i = 0; i < 3; ++i) {
+        if (!outs[i]) continue;
+        for (const void* b : ins)
+            if (b && b == outs[i])
+                return fail(CRB_EINVAL, who + ": " + out_names[i] + " must not alias ckpt, work, gain, ref, rec_bar->out or input->f_held");
+        for (int j = i + 1; j < 3; ++j)
+            if (outs[j] == outs[i]) return fail(CRB_EINVAL, who + ": " + out_names[i] + " must not alias " + out_names[j]);
+    }
+    if (work == ckpt || work == gain || work == ref) return fail(CRB_EINVAL, who + ": work must not alias ckpt, gain or ref");
+    if (int rc = need_device(p, who.c_str())) return rc;
+    Recording r;
+    if (int rc = decode_record(p, rec_bar, n_steps, true, who.c_str(), &r)) return rc;
+    Forcing f;
+    if (int rc = decode_input(p, in, who.c_str(), &f)) return rc;
+    if (n_steps == 0) return CRB_OK;
+    if (int rc = ensure_gadj(p, who.c_str())) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int groups = (p->B + p->G - 1) / p->G;
+    const size_t S = state_doubles(p), x_stride = size_t(2) * p->n_node * 4;
+    const FbAdjWork w = fb_adj_work(p, work, every, n_cot);
+    // a sample of a constrained DOF has no cotangent to hand on (the state holds 0 there)
+    const bool rec_on = r.slot >= 0 && p->any_free[size_t(3) * size_t(r.slot + p->off) + size_t(r.comp % 3)];
+    const size_t rec_off = rec_on ? (size_t(r.comp / 3) * p->n_node + size_t(r.slot + p->off)) * 4 + size_t(r.comp % 3) : 0;
+
+    FeedbackAdjParams q;
+    std::memset(&q, 0, sizeof(q));
+    q.ubar = w.ubar;
+    q.col_off = p->d_col_off;
+    q.row_off = p->d_row_off;
+    q.rows = n_cot * p->B; q.B = p->B; q.n = p->n_free; q.n2 = 2 * p->n_free;
+    q.x_stride = x_stride;
+    q.u_stride = size_t(p->n_node) * 4;
+    q.gain = static_cast<const double*>(gain);
+    q.xbar = w.xbar;
+    q.lam = static_cast<double*>(lam);
+    q.sum = w.sum;
+    q.seed = w.seed;
+    q.ref_bar = static_cast<double*>(grad->ref_bar);
+    q.ref = static_cast<const double*>(ref);
+    q.gain_bar = static_cast<double*>(grad->gain_bar);
+    q.partial = w.partial;
+    // the seeds of DESIGN 10: kbar4 = dt/6 l+, kbar3 = dt/3 l+ + dt s4, kbar2 = dt/3 l+ + dt/2 s3, kbar1 = dt/6 l+ + dt/2 s2;
+    // the launch after stage s forms the seed of stage s - 1
+    const double ca_next[4] = {0.0, dt / 6.0, dt / 3.0, dt / 3.0}, cb_next[4] = {0.0, 0.5 * dt, 0.5 * dt, dt};
+
+    const int nseg = (n_steps + every - 1) / every;
+    for (int g = nseg - 1; g >= 0; --g) {
+        const int k0 = g * every, n = (n_steps - k0) < every ? (n_steps - k0) : every;
+        // 1. the segment's stage states from its checkpoint, straight into the work buffer
+        HIP_TRY(hipMemcpyAsync(w.xcur, static_cast<const double*>(ckpt) + size_t(g) * S, S * sizeof(double), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemsetAsync(w.u, 0, S / 2 * sizeof(double), st));
+        double t = clock_after(t0, dt, k0);   // (the checkpoint pass's clock at the segment start: the same additions)
+        for (int i = 0; i < n; ++i) {
+            double* const X = w.stages + size_t(i) * 4 * S;
+            HIP_TRY(hipMemcpyAsync(X, w.xcur, S * sizeof(double), hipMemcpyDeviceToDevice, st));
+            if (int rc = fb_adj_step(p, w.xcur, X + S, X + 2 * S, X + 3 * S, w.xbar, w, t, dt, gain, ref, f, stream)) return rc;
+            t = t + dt;
+        }
+        // 2. the sweep back over it, every cotangent: per stage crb_rhs_vjp, the transposed product, the gain gradient
+        for (int i = n - 1; i >= 0; --i) {
+            const int kstep = k0 + i;
+            const bool sample = rec_on && (kstep + 1) % r.every == 0 && (kstep + 1) / r.every <= r.count;
+            HIP_TRY(crb::launch_feedback_seed(q.lam, w.seed, size_t(q.rows) * x_stride, x_stride, dt / 6.0,
+                                              sample ? static_cast<const double*>(r.out) : nullptr, rec_off, r.count,
+                                              sample ? (kstep + 1) / r.every - 1 : 0, st));
+            for (int s = 3; s >= 0; --s) {
+                double* const X = w.stages + (size_t(i) * 4 + size_t(s)) * S;
+                KParams<double> k = base_params<double>(p);
+                k.x = X;
+                AdjParams<double> a = adj_params(p);
+                a.lam_in = w.seed;
+                a.xbar = w.xbar;
+                a.ubar = w.ubar;
+                HIP_TRY(crb::launch_adj_rhs(k, a, groups, n_cot, p->NT, st));
+                q.first = s == 3; q.last = s == 0;
+                q.ca = ca_next[s]; q.cb = cb_next[s];
+                HIP_TRY(crb::launch_feedback_transpose(q, st));
+                if (q.gain_bar) {
+                    q.xs = X;
+                    HIP_TRY(crb::launch_feedback_gain_grad(q, st));
+                }
+            }
+        }
+    }
+    return CRB_OK;
 }

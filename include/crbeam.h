@@ -491,6 +491,63 @@ int crb_feedback_status(const crb_plan* plan, const void* work, int32_t* status,
 int crb_step_rk4_feedback(const crb_plan* plan, void* x, double t0, double dt, int n_steps, const void* gain,
                           const void* ref, const crb_input_desc* input, void* work, double* t_end, void* stream);
 
+/* ---- Adjoint of the closed loop: gradients of a rollout of crb_step_rk4_feedback with respect to the gain and the reference.
+ * The controller of examples/lqr_control.py:95-125 (u = K (r - x) in every RK4 stage, FullStateLinear.compute_input,
+ * control/full_state_linear.py:81) designs K on the linear model and runs it on the nonlinear rod; these entry points give
+ * dL/dK and dL/dr of a loss over that run in one backward sweep instead of two closed-loop rollouts per gain entry. */
+
+/* Cotangents of the controller, ACCUMULATED by crb_step_rk4_feedback_adjoint (device, fp64; NULL = not wanted)
+ * (lqr_control.py:95-125, full_state_linear.py:81: the K and the reference of compute_input). */
+typedef struct crb_feedback_cotangent {
+    void* gain_bar;  /* device [n_cot][n][2n], ACCUMULATED, or NULL */
+    void* ref_bar;   /* device [n_cot][B][2n] reduced, ACCUMULATED, or NULL */
+} crb_feedback_cotangent;
+
+/* Device bytes of the work buffer of crb_step_rk4_feedback_checkpoint / _adjoint (lqr_control.py:95-125,
+ * full_state_linear.py:81).  With S = B * 2 * n_node * 4 doubles (a state) and F = S / 2 (a force), in this order:
+ *   every * 4 * S   the four RK4 stage states of every step of one segment (stage 0 = the step's start state)
+ *   S, S, F         the RK4 accumulator, the running state of the recompute, the stage's feedback force
+ *   n_cot * S  x 3  the stage's seed cotangent, its (df/dx)^T, the running sum of the step's stage cotangents
+ *   n_cot * F       the stage's (df/du)^T
+ *   n_cot * Z * n * 2n   the gain gradient's partial tiles, only when its beam reduction runs in Z > 1 slices:
+ *                   Z = min(ceil(B / 32), ceil(1536 / (ceil(n / 32) * ceil(2n / 32)))), n = n_free
+ * = ((4 every + 2 + 3 n_cot) S + (1 + n_cot) F + [Z > 1] n_cot Z n 2n) * sizeof(double).  0 for every < 1 or n_cot < 1. */
+size_t crb_rk4_feedback_adjoint_work_bytes(const crb_plan* plan, int every, int n_cot);
+
+/* The forward pass of a differentiable closed-loop rollout (lqr_control.py:95-125, full_state_linear.py:81): n_steps RK4 steps
+ * with u = K (ref - x) in every stage, ALWAYS in the stage-split form (crb_feedback_force + crb_rk4_stage per stage, whatever
+ * crb_feedback_path says), so x(T) is bitwise crb_step_rk4_feedback with CRB_FUSED_FEEDBACK=0 CRB_LOOP=0.  Writes the state at
+ * the start of steps 0, every, 2 every, ... to ckpt [ceil(n_steps / every)][B][2][n_node][4].  rec: one DOF every rec->every
+ * steps into out[B][floor(n_steps / every)] as crb_step_rk4_rec takes it (may be NULL); CRB_RECORD_ALL: CRB_EUNSUPPORTED.
+ * input: the impulse and / or a held force, both disturbances d(t) added to u and not differentiated (without a held force the
+ * launches are exactly those of the stage-split crb_step_rk4_feedback).  work: crb_rk4_feedback_adjoint_work_bytes(plan, every, 1) device bytes are enough.  Does not report to
+ * crb_plan_set_status.  Limits and codes as crb_step_rk4_feedback_adjoint. */
+int crb_step_rk4_feedback_checkpoint(const crb_plan* plan, void* x, double t0, double dt, int n_steps, int every,
+                                     const void* gain, const void* ref, const crb_input_desc* input, const crb_record_desc* rec,
+                                     void* ckpt, void* work, double* t_end, void* stream);
+
+/* Adjoint of the rollout crb_step_rk4_feedback_checkpoint ran from t0 (the same dt, n_steps, every, gain, ref and input;
+ * lqr_control.py:95-125, full_state_linear.py:81): for n_cot cotangents,
+ *   lam      device [n_cot][B][2][n_node][4], in place: dL/dx(T) on entry, dL/dx(0) on exit (only free-DOF entries change)
+ *   rec_bar  the record of the forward pass with out = its cotangent [n_cot][B][n_rec], or NULL
+ *   grad     gain_bar += dL/dK, ref_bar += dL/d ref; gain_bar == NULL skips its product
+ * Segments last to first: each is recomputed from its checkpoint (the stage states go straight into work), then swept back
+ * per stage: crb_rhs_vjp at the stage state, P = ubar . K with s = xbar - P, ref_bar += P and the next stage's seed in its
+ * epilogue, gain_bar += sum_b ubar_b (x) (ref_b - X_b) -- both products on v_mfma_f64_16x16x4_f64, about 12 launches per step (the
+ * beam reduction of large ensembles runs in slices whose partial tiles a second launch sums in a fixed order).
+ * The RHS is affine in u, so only the stage STATES are needed, not the stage forces.  Every sum has a fixed order (no atomics)
+ * and every stage accumulates in place in sweep order: lam, gain_bar and ref_bar are bitwise independent of `every`, D
+ * cotangents in one call are bitwise D calls of one, and two identical calls agree bitwise.  A non-finite cotangent of one beam
+ * stays in that beam's rows of lam and ref_bar; it reaches gain_bar (a sum over beams).
+ * Checked before the device is touched (host-only plans show them; valid calls there: CRB_ENODEV): CRB_EUNSUPPORTED for fp32
+ * plans, plans with more than one free-DOF set (mixed topology), beams of more than 256 thread-carried nodes, a gravity table
+ * crb_rhs_vjp refuses and CRB_RECORD_ALL; CRB_EINVAL for n_cot outside 1 .. 65535, a NULL gain, lam, ckpt, work or
+ * grad, bad n_steps / every / dt, and lam, gain_bar or ref_bar aliasing ckpt, work, gain, ref or each other.  crb_last_error()
+ * names the argument. */
+int crb_step_rk4_feedback_adjoint(const crb_plan* plan, const void* ckpt, void* lam, int n_cot, double t0, double dt,
+                                  int n_steps, int every, const void* gain, const void* ref, const crb_input_desc* input,
+                                  const crb_record_desc* rec_bar, const crb_feedback_cotangent* grad, void* work, void* stream);
+
 /* crb_step_rk4 plus strided recording of one DOF (rec may be NULL). */
 int crb_step_rk4_rec(const crb_plan* plan, void* x, double t0, double dt, int n_steps, const crb_input_desc* input,
                      const crb_record_desc* rec, double* t_end, void* stream);

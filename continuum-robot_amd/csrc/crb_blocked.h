@@ -34,6 +34,9 @@ enum : int {
 // per-lane separator table: `levels` level records of PCR_LEVEL_VALS, then the final inverse (5); stored value-major
 // [value][lane] so that a wave reads one value of every lane with one conflict-free access
 __host__ __device__ constexpr int blk_sep_vals(int levels) { return levels * PCR_LEVEL_VALS + BLK_PACK; }
+// plans of nonlinear elements: the folded force constants (crb_math.h: elem_fold_build, FK_N values) follow the separator
+// tables of the plan's `levels` in the blocked table buffer
+__host__ __device__ constexpr int blk_fold_offset(int levels) { return BU_N + blk_sep_vals(levels) * BLK_LANES; }
 
 // The wave-uniform table as the kernel holds it: BLK_TAB_REGS fp64 registers per lane, constant k in lane k % BLK_TAB_ROW of
 // EVERY 16-lane row of register k / BLK_TAB_ROW (a DPP row broadcast reads inside the reader's own row, so each of the four

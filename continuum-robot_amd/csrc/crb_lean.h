@@ -253,10 +253,24 @@ __device__ __forceinline__ void lean_rhs(const ElemCoef<T>& ec, T dragc, bool co
 // 2101 -> 2032, 250 VGPRs, 90 SGPRs, no spill, no scratch; the linear instance takes the RK4 form too (238 VGPRs, 58 SGPRs).
 // Outputs agree with the parent's to rounding.  CRB_BLK_CHORD / CRB_BLK_RK4_POS (=0 in the tuning build)
 // switch either item off for timing.
+// The nonlinear instance evaluates the element polynomials with the pack's prefactors folded into their coefficients
+// (crb_math.h: elem_force_nonlinear_folded): the blocked stepper only takes plans of 256 equal elements, so phi L, L du, 3 e
+// and the products with cA1, cA3, cD3, cA4, cD4 are one number per plan, multiplied into 30 constants when the plan is built
+// (elem_fold_build, each rounded once) and stored behind the blocked tables (crb_blocked.h: blk_fold_offset).  A stage reads
+// them as scalar loads in the batch that read the element pack, which they replace (three s_load_dwordx16, one x8, one x4
+// under the stage's one wait; the four constants that head a sum take a v_mov_b64 each per stage, since an instruction has one
+// scalar operand).  41 fp64 instructions per element; 1498 -> 1386 per step (add +48: sigma and delta are additions now,
+// phi L +- was fused; mul -112, FMA -48), VALU 2032 -> 1928, 256 VGPRs, 100 SGPRs, no spill, no scratch, two waves per SIMD;
+// the compiler no longer holds the chord form's rationals in SGPR pairs across the loop.  Outputs agree with the parent's to
+// rounding (DESIGN.md §4 has the timings of this build, of its parent and of the tuning build with CRB_BLK_FOLD=0, the chord
+// form, and the counters).  The linear instance is untouched.
 // The next beam's state is not prefetched as in the one-node-per-lane
 // form: four nodes' records are 48 more registers than the budget of two waves per SIMD holds.
 #ifndef CRB_BLK_CHORD
 #define CRB_BLK_CHORD 1
+#endif
+#ifndef CRB_BLK_FOLD
+#define CRB_BLK_FOLD 1
 #endif
 #ifndef CRB_BLK_RK4_POS
 #define CRB_BLK_RK4_POS 1
@@ -279,11 +293,16 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
     // elem_force_nonlinear_chord) instead of elem_force_nonlinear_regrouped, and the RK4 positions carried on the
     // accelerations (crb_math.h: Rk4Pos) instead of on stage velocities of every component
     constexpr bool CHORD = CRB_BLK_CHORD, RKPOS = CRB_BLK_RK4_POS;
+    // the element polynomials with the pack's prefactors folded into their coefficients (crb_math.h: elem_force_nonlinear_folded;
+    // the plan's FK_N constants behind the blocked tables, crb_blocked.h: blk_fold_offset) instead of the chord form
+    constexpr bool FOLD = REGROUP && CRB_BLK_FOLD;
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef const __attribute__((address_space(4))) SlotConst<T>* CS;
+    typedef const __attribute__((address_space(4))) T* CK;
 #define CRB_BFRESH(ptr) asm volatile("" : "+s"(ptr))
 #else
     typedef const SlotConst<T>* CS;
+    typedef const T* CK;
 #define CRB_BFRESH(ptr) (void)(ptr)
 #endif
     typedef T rec4 __attribute__((ext_vector_type(4)));
@@ -383,9 +402,16 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                 const T w = (s == 0 || s == 3) ? T(1) : T(2);
                 const T cs = (s == 2) ? dt : hdt;
                 const CS SC = (CS)q.slot;
-                T ec[6];
+                [[maybe_unused]] T ec[6];
+                [[maybe_unused]] T fk[FK_N];
+                if constexpr (FOLD) {
+                    const CK FC = (CK)q.blocked + blk_fold_offset(LS);
 #pragma unroll
-                for (int i = 0; i < 6; ++i) ec[i] = SC->elem.c[i];
+                    for (int i = 0; i < FK_N; ++i) fk[i] = FC[i];
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) ec[i] = SC->elem.c[i];
+                }
                 const T drag_all = SC->drag;   // (loaded whatever the flag: a load under a branch costs a wait of its own)
                 const T dragc = (q.flags & 1u) ? drag_all : T(0);
                 // -- positions of the next stage: the last node's ride on this stage's q exchange
@@ -418,7 +444,11 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                 T f2[NP], cW[NP];   // (REGROUP: the axial pair as f2 and W, crb_math.h)
 #pragma unroll
                 for (int k = 0; k < NP; ++k) {
-                    if constexpr (REGROUP) {
+                    if constexpr (FOLD) {
+                        const ElemForceRegrouped<T> e = elem_force_nonlinear_folded<T, const T*>(fk, k ? sq[k - 1] : qL, sq[k]);
+                        f2[k] = e.f2; cW[k] = e.W;   // (W carries cA1)
+                        fl[k][1] = e.f3; fr[k][1] = -e.f3; fl[k][2] = e.m_left; fr[k][2] = e.m_right;
+                    } else if constexpr (REGROUP) {
                         const ElemForceRegrouped<T> e = CHORD ? elem_force_nonlinear_chord<T>(ec, k ? sq[k - 1] : qL, sq[k])
                                                               : elem_force_nonlinear_regrouped<T>(ec, k ? sq[k - 1] : qL, sq[k]);
                         f2[k] = e.f2; cW[k] = ec[1] * e.W;
@@ -442,7 +472,7 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                 //    written as an opaque block per node because a C++ branch here splits the stage's straight-line code, which
                 //    the scheduler then no longer interleaves with the solve (measured: 50 spilled VGPRs).  No lane shift inside.
                 //    After a compiler upgrade re-check with `make resource-usage`: this kernel at 0 SGPR spills, <= 256 VGPRs
-                //    (250 with the chord forces and the RK4 positions on the accelerations, 90 SGPRs), no scratch.  The block can go back to the C++ form of the host branch below once that no longer splits the
+                //    (256 with the folded forces and the RK4 positions on the accelerations, 100 SGPRs: the ceiling of two waves per SIMD, with no register of headroom left -- a compiler that needs one more spills), no scratch.  The block can go back to the C++ form of the host branch below once that no longer splits the
                 //    schedule (same resource figures, same step time).
                 {
                     const int kon = imp_on ? kimp : -1, dof = q.imp_dof;

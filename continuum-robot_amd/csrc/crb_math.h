@@ -296,6 +296,113 @@ CRB_HD ElemForceRegrouped<T> elem_force_nonlinear_chord(const T* c, const T ql[3
     return o;
 }
 
+// The chord form with every prefactor multiplied into the polynomial coefficients, for a caller whose elements all share
+// ONE pack (the blocked stepper: 256 equal elements), so that a = phi L, U = L du, g = 3 e and the products with cA1, cA3,
+// cD3, cA4, cD4 are one number per plan.  In du, dw, sigma = phi1 + phi2, delta = phi1 - phi2 and
+// eps = sigma - (2/L) dw  (e = L eps, d = L delta):
+//   f2      = k dw^2 + k du + k delta^2 + k eps^2
+//   cA1 LT  = k0 + k eps + k dw                                        (W = u2 times that: it carries cA1)
+//   f3      = eps (k0 + k du + k delta^2 + k dw^2 + k eps^2) + dw (k delta^2 + k du + k dw^2 + k eps^2)
+//   X       = eps (k0 + k delta^2 + k du + k dw^2 + k eps^2) + dw (k delta^2 + k eps^2)
+//   Rf      = k0 + k delta^2 + k du + k eps^2 + dw (k dw + k eps)
+//   m_left  = X + delta Rf,   m_right = X - delta Rf
+// identically equal to elem_force_nonlinear_chord's in rational arithmetic (tests/test_folded_forces_cpu.py checks the
+// identities, the constants, and bounds the rounding against exact values next to the symmetric form's).  41 fp64
+// instructions per element with contraction against 48 + 1 (cA1 W) + 1.25 (phi L per node).
+enum : int {
+    FK_EPS = 0,                                                   // eps = sigma - k dw
+    FK_F2_DW2, FK_F2_DU, FK_F2_D2, FK_F2_E2,                      // f2
+    FK_LT_0, FK_LT_E, FK_LT_DW,                                   // cA1 LT
+    FK_F3E_0, FK_F3E_DU, FK_F3E_D2, FK_F3E_DW2, FK_F3E_E2,        // f3, the factor of eps
+    FK_F3W_D2, FK_F3W_DU, FK_F3W_DW2, FK_F3W_E2,                  // f3, the factor of dw
+    FK_XE_0, FK_XE_D2, FK_XE_DU, FK_XE_DW2, FK_XE_E2,             // X, the factor of eps
+    FK_XW_D2, FK_XW_E2,                                           // X, the factor of dw
+    FK_R_0, FK_R_D2, FK_R_DU, FK_R_E2, FK_R_DW, FK_R_E,           // Rf
+    FK_N                                                          // 30
+};
+// The constants of a nonlinear pack, each formed in long double from the pack's values and rounded once.
+#if defined(__HIPCC__)
+__host__
+#endif
+inline void elem_fold_build(const ElemCoef<double>& e, double k[FK_N]) {
+    const long double L = e.c[0], cA1 = e.c[1], cA3 = e.c[2], cD3 = e.c[3], cA4 = e.c[4], cD4 = e.c[5];
+    const long double L2 = L * L, L3 = L2 * L;
+    k[FK_EPS] = double(2.0L / L);                          // 2 / L
+    k[FK_F2_DW2] = double(cA1 / 2.0L);                     // cA1 / 2
+    k[FK_F2_DU] = double(-(cA1 * L));                      // -cA1 L
+    k[FK_F2_D2] = double(cA1 * L2 / 24.0L);                // cA1 L^2 / 24
+    k[FK_F2_E2] = double(cA1 * L2 / 40.0L);                // cA1 L^2 / 40
+    k[FK_LT_0] = double(cA1 * L);                          // cA1 L
+    k[FK_LT_E] = double(cA1 * L / 20.0L);                  // cA1 L / 20
+    k[FK_LT_DW] = double(-(cA1 / 2.0L));                   // -cA1 / 2
+    k[FK_F3E_0] = double(-(3.0L * cD3 * L));               // -3 cD3 L
+    k[FK_F3E_DU] = double(cA3 * L2);                       // cA3 L^2
+    k[FK_F3E_D2] = double(3.0L * cA3 * L3 / 56.0L);        // 3/56 cA3 L^3
+    k[FK_F3E_DW2] = double(-(3.0L * cA3 * L / 2.0L));      // -3/2 cA3 L
+    k[FK_F3E_E2] = double(-(cA3 * L3 / 56.0L));            // -cA3 L^3 / 56
+    k[FK_F3W_D2] = double(3.0L * cA3 * L2 / 4.0L);         // 3/4 cA3 L^2
+    k[FK_F3W_DU] = double(-(10.0L * cA3 * L));             // -10 cA3 L
+    k[FK_F3W_DW2] = double(5.0L * cA3);                    // 5 cA3
+    k[FK_F3W_E2] = double(15.0L * cA3 * L2 / 28.0L);       // 15/28 cA3 L^2
+    k[FK_XE_0] = double(3.0L * cD4 * L);                   // 3 cD4 L
+    k[FK_XE_D2] = double(11.0L * cA4 * L3 / 560.0L);       // 11/560 cA4 L^3
+    k[FK_XE_DU] = double(-(cA4 * L2 / 10.0L));             // -cA4 L^2 / 10
+    k[FK_XE_DW2] = double(3.0L * cA4 * L / 20.0L);         // 3/20 cA4 L
+    k[FK_XE_E2] = double(3.0L * cA4 * L3 / 560.0L);        // 3/560 cA4 L^3
+    k[FK_XW_D2] = double(cA4 * L2 / 20.0L);                // cA4 L^2 / 20
+    k[FK_XW_E2] = double(3.0L * cA4 * L2 / 140.0L);        // 3/140 cA4 L^2
+    k[FK_R_0] = double(cD4 * L);                           // cD4 L
+    k[FK_R_D2] = double(cA4 * L3 / 80.0L);                 // cA4 L^3 / 80
+    k[FK_R_DU] = double(-(cA4 * L2 / 6.0L));               // -cA4 L^2 / 6
+    k[FK_R_E2] = double(11.0L * cA4 * L3 / 560.0L);        // 11/560 cA4 L^3
+    k[FK_R_DW] = double(cA4 * L / 4.0L);                   // cA4 L / 4
+    k[FK_R_E] = double(cA4 * L2 / 10.0L);                  // cA4 L^2 / 10
+}
+// (K: a plain or a constant-address-space pointer to the FK_N constants, or an array of them)
+template <typename T, typename K = const T*>
+CRB_HD ElemForceRegrouped<T> elem_force_nonlinear_folded(K k, const T ql[3], const T qr[3]) {
+    const T u2 = qr[0];
+    const T du = ql[0] - u2, dw = ql[1] - qr[1];
+    const T sg = ql[2] + qr[2], dl = ql[2] - qr[2];
+    const T eps = sg - k[FK_EPS] * dw;
+    const T e2 = eps * eps, d2 = dl * dl, dw2 = dw * dw;
+
+    T f2 = k[FK_F2_DW2] * dw2;
+    f2 = f2 + k[FK_F2_DU] * du;
+    f2 = f2 + k[FK_F2_D2] * d2;
+    f2 = f2 + k[FK_F2_E2] * e2;
+    T LT = k[FK_LT_0] + k[FK_LT_E] * eps;
+    LT = LT + k[FK_LT_DW] * dw;
+
+    T F3e = k[FK_F3E_0] + k[FK_F3E_DU] * du;
+    F3e = F3e + k[FK_F3E_D2] * d2;
+    F3e = F3e + k[FK_F3E_DW2] * dw2;
+    F3e = F3e + k[FK_F3E_E2] * e2;
+    T F3w = k[FK_F3W_D2] * d2;
+    F3w = F3w + k[FK_F3W_DU] * du;
+    F3w = F3w + k[FK_F3W_DW2] * dw2;
+    F3w = F3w + k[FK_F3W_E2] * e2;
+    T Xe = k[FK_XE_0] + k[FK_XE_D2] * d2;
+    Xe = Xe + k[FK_XE_DU] * du;
+    Xe = Xe + k[FK_XE_DW2] * dw2;
+    Xe = Xe + k[FK_XE_E2] * e2;
+    const T Xw = k[FK_XW_D2] * d2 + k[FK_XW_E2] * e2;
+    const T X = eps * Xe + dw * Xw;
+    T Rf = k[FK_R_0] + k[FK_R_D2] * d2;
+    Rf = Rf + k[FK_R_DU] * du;
+    Rf = Rf + k[FK_R_E2] * e2;
+    Rf = Rf + dw * (k[FK_R_DW] * dw + k[FK_R_E] * eps);
+    const T Y = dl * Rf;
+
+    ElemForceRegrouped<T> o;
+    o.f2 = f2;
+    o.W = u2 * LT;
+    o.f3 = eps * F3e + dw * F3w;
+    o.m_left = X + Y;
+    o.m_right = X - Y;
+    return o;
+}
+
 // Classical RK4 of a second-order system q' = v, v' = a(q, v), per component, with the position side carried on the
 // accelerations alone: with a_i the acceleration of stage i (evaluated at q_i and the stage velocity v_i),
 //   q_2 = q + dt/2 v     q_3 = q_2 + dt^2/4 a_1     q_4 = (q + dt v) + dt^2/2 a_2

@@ -37,6 +37,8 @@ __host__ __device__ constexpr int blk_sep_vals(int levels) { return levels * PCR
 // plans of nonlinear elements: the folded force constants (crb_math.h: elem_fold_build, FK_N values) follow the separator
 // tables of the plan's `levels` in the blocked table buffer
 __host__ __device__ constexpr int blk_fold_offset(int levels) { return BU_N + blk_sep_vals(levels) * BLK_LANES; }
+// ... and behind them the constants of the form that shares the membrane combinations (elem_share_build, SK_N values)
+__host__ __device__ constexpr int blk_share_offset(int levels) { return blk_fold_offset(levels) + FK_N; }
 
 // The wave-uniform table as the kernel holds it: BLK_TAB_REGS fp64 registers per lane, constant k in lane k % BLK_TAB_ROW of
 // EVERY 16-lane row of register k / BLK_TAB_ROW (a DPP row broadcast reads inside the reader's own row, so each of the four

@@ -264,6 +264,25 @@ __device__ __forceinline__ void lean_rhs(const ElemCoef<T>& ec, T dragc, bool co
 // the compiler no longer holds the chord form's rationals in SGPR pairs across the loop.  Outputs agree with the parent's to
 // rounding (DESIGN.md §4 has the timings of this build, of its parent and of the tuning build with CRB_BLK_FOLD=0, the chord
 // form, and the counters).  The linear instance is untouched.
+// The folded polynomials now share the membrane strain's two combinations (crb_math.h: elem_force_nonlinear_shared): the du
+// and dw^2 coefficients of f2, of both factors of f3, of X's eps factor and of Rf are pairwise proportional, so A1 = dw^2 - 2 L du
+// and A2 = dw^2 - (2 L / 3) du are formed once per element (one multiply-add each) and the five sums lose a term each: 38
+// fp64 instructions per element against 41, 27 plan constants (elem_share_build, behind the folded ones: crb_blocked.h,
+// blk_share_offset) against 30; 1386 -> 1338 fp64 instructions per step, VALU 1928 -> 1880.  u2 LT is contracted into the
+// axial right-hand side's subtractions (no bare multiply is left of it).  The five sums of two products are explicit fused
+// multiply-adds, so that their roundings do not depend on the code around the call.
+// The constants are requested ONE STAGE AHEAD (CRB_BLK_CONST_AHEAD): once before the step loop, then after each stage's
+// right-hand side for the next stage (stage 3: for the next step's stage 0), where the last instruction that reads them is
+// behind and the whole mass solve and the RK4 ends, which need no scalar register, lie ahead; they land under the solve's
+// first LDS wait instead of being waited for at the stage's top.  With that, what else a stage read at its top -- the
+// impulse window's end and component, the drag factor, the constants' address -- is read once per beam and held over the
+// step loop (CRB_BLK_HOLD_PARAMS): seven scalar registers, live in the force block either way, which is where the scalar
+// file is fullest.  A stage's top has no scalar load and no wait: per step 87 -> 71 s_load (20 of them the four requests),
+// 108 -> 95 s_waitcnt, 256 VGPRs, 97 SGPRs, no spill, no scratch, two waves per SIMD.  The values are the same numbers, so
+// the outputs are bitwise those of a build with both switches off (checked with bench.py --dump-outputs).  DESIGN.md §4
+// has the timings of the four variants, of this build and of its parent, and the counters.  CRB_BLK_SHARE /
+// CRB_BLK_CONST_AHEAD / CRB_BLK_HOLD_PARAMS (=0 in the tuning build) switch each off; with all three off the unit's
+// code is the parent's line for line.
 // The next beam's state is not prefetched as in the one-node-per-lane
 // form: four nodes' records are 48 more registers than the budget of two waves per SIMD holds.
 #ifndef CRB_BLK_CHORD
@@ -271,6 +290,15 @@ __device__ __forceinline__ void lean_rhs(const ElemCoef<T>& ec, T dragc, bool co
 #endif
 #ifndef CRB_BLK_FOLD
 #define CRB_BLK_FOLD 1
+#endif
+#ifndef CRB_BLK_SHARE
+#define CRB_BLK_SHARE 1
+#endif
+#ifndef CRB_BLK_CONST_AHEAD
+#define CRB_BLK_CONST_AHEAD 1
+#endif
+#ifndef CRB_BLK_HOLD_PARAMS
+#define CRB_BLK_HOLD_PARAMS 1
 #endif
 #ifndef CRB_BLK_RK4_POS
 #define CRB_BLK_RK4_POS 1
@@ -296,6 +324,19 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
     // the element polynomials with the pack's prefactors folded into their coefficients (crb_math.h: elem_force_nonlinear_folded;
     // the plan's FK_N constants behind the blocked tables, crb_blocked.h: blk_fold_offset) instead of the chord form
     constexpr bool FOLD = REGROUP && CRB_BLK_FOLD;
+    // the folded form with the membrane combinations A1, A2 formed once (crb_math.h: elem_force_nonlinear_shared; the plan's
+    // SK_N constants behind the folded ones, crb_blocked.h: blk_share_offset) instead of the folded form; without
+    // CRB_BLK_FOLD the switch does nothing
+    constexpr bool SHARE = FOLD && CRB_BLK_SHARE;
+    constexpr int NK = SHARE ? int(SK_N) : int(FK_N);
+    // the polynomial constants requested one stage ahead, after the previous stage's right-hand side, instead of at the
+    // stage's top (the same loads of the same values: outputs are bitwise those of the build without)
+    constexpr bool AHEAD = FOLD && CRB_BLK_CONST_AHEAD;
+    // ... and what else a stage reads by scalar loads (the impulse window's end and component, the drag factor, the constants'
+    // address) read once per beam and held over the step loop, so that a stage's top has no scalar load and no wait at all:
+    // with the constants arriving under the solve these seven registers no longer push anything out of the scalar file
+    // (needs CRB_BLK_CONST_AHEAD)
+    constexpr bool HOLD = AHEAD && CRB_BLK_HOLD_PARAMS;
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef const __attribute__((address_space(4))) SlotConst<T>* CS;
     typedef const __attribute__((address_space(4))) T* CK;
@@ -377,6 +418,24 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
         [[maybe_unused]] T accq[NP][3], accv[NP][3];
         T sq[NP][3], sv[NP][3];
         [[maybe_unused]] Rk4Pos<T> rk[NP][3];
+        // AHEAD: the polynomial constants, requested here for the first stage and after each stage's right-hand side for the next
+        [[maybe_unused]] T fk_ahead[NK];
+        [[maybe_unused]] CK FC_held = nullptr;
+        [[maybe_unused]] double dur_held = 0.0;
+        [[maybe_unused]] int dof_held = 0;
+        [[maybe_unused]] T dragc_held = T(0);
+        if constexpr (AHEAD) {
+            const CK FC = (CK)p.blocked + (SHARE ? blk_share_offset(LS) : blk_fold_offset(LS));
+#pragma unroll
+            for (int i = 0; i < NK; ++i) fk_ahead[i] = FC[i];
+            if constexpr (HOLD) {
+                FC_held = FC;
+                dur_held = p.duration;
+                dof_held = p.imp_dof;
+                const T drag_all = ((CS)p.slot)->drag;
+                dragc_held = (p.flags & 1u) ? drag_all : T(0);
+            }
+        }
         for (int step = 0; step < p.n_steps; ++step) {
             double t_half, t_full;
             {
@@ -392,28 +451,33 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                 for (int c = 0; c < 3; ++c) { sq[k][c] = xq[k][c]; sv[k][c] = xv[k][c]; }
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
-                // (what a stage needs of the launch parameters is re-read through the laundered kernarg pointer: held across
-                //  the loop, it would push the polynomial constants out of the scalar file)
+                // (without HOLD, what a stage needs of the launch parameters is re-read through the laundered kernarg pointer:
+                //  held across the loop next to constants loaded at the stage's top, it pushed them out of the scalar file)
                 KPT ks = kp;
                 CRB_BFRESH(ks);
                 const KParams<T>& q = *(const KParams<T>*)(ks);
                 const double ts = (s == 0) ? tc : ((s == 3) ? t_full : t_half);
-                const bool imp_on = ts < q.duration;
+                const bool imp_on = ts < (HOLD ? dur_held : q.duration);
                 const T w = (s == 0 || s == 3) ? T(1) : T(2);
                 const T cs = (s == 2) ? dt : hdt;
                 const CS SC = (CS)q.slot;
                 [[maybe_unused]] T ec[6];
-                [[maybe_unused]] T fk[FK_N];
+                [[maybe_unused]] T fk_stage[NK];
+                [[maybe_unused]] T* const fk = AHEAD ? fk_ahead : fk_stage;
+                [[maybe_unused]] CK FCn = nullptr;   // (AHEAD: where the request after the right-hand side reads)
                 if constexpr (FOLD) {
-                    const CK FC = (CK)q.blocked + blk_fold_offset(LS);
+                    const CK FC = (CK)q.blocked + (SHARE ? blk_share_offset(LS) : blk_fold_offset(LS));
+                    if constexpr (AHEAD) FCn = HOLD ? FC_held : FC;
+                    else {
 #pragma unroll
-                    for (int i = 0; i < FK_N; ++i) fk[i] = FC[i];
+                        for (int i = 0; i < NK; ++i) fk[i] = FC[i];
+                    }
                 } else {
 #pragma unroll
                     for (int i = 0; i < 6; ++i) ec[i] = SC->elem.c[i];
                 }
                 const T drag_all = SC->drag;   // (loaded whatever the flag: a load under a branch costs a wait of its own)
-                const T dragc = (q.flags & 1u) ? drag_all : T(0);
+                const T dragc = HOLD ? dragc_held : ((q.flags & 1u) ? drag_all : T(0));
                 // -- positions of the next stage: the last node's ride on this stage's q exchange
                 [[maybe_unused]] T qn3[3];
                 T qLn[3];
@@ -445,7 +509,9 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
 #pragma unroll
                 for (int k = 0; k < NP; ++k) {
                     if constexpr (FOLD) {
-                        const ElemForceRegrouped<T> e = elem_force_nonlinear_folded<T, const T*>(fk, k ? sq[k - 1] : qL, sq[k]);
+                        ElemForceRegrouped<T> e;
+                        if constexpr (SHARE) e = elem_force_nonlinear_shared<T, const T*>(fk, k ? sq[k - 1] : qL, sq[k]);
+                        else e = elem_force_nonlinear_folded<T, const T*>(fk, k ? sq[k - 1] : qL, sq[k]);
                         f2[k] = e.f2; cW[k] = e.W;   // (W carries cA1)
                         fl[k][1] = e.f3; fr[k][1] = -e.f3; fl[k][2] = e.m_left; fr[k][2] = e.m_right;
                     } else if constexpr (REGROUP) {
@@ -472,10 +538,10 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                 //    written as an opaque block per node because a C++ branch here splits the stage's straight-line code, which
                 //    the scheduler then no longer interleaves with the solve (measured: 50 spilled VGPRs).  No lane shift inside.
                 //    After a compiler upgrade re-check with `make resource-usage`: this kernel at 0 SGPR spills, <= 256 VGPRs
-                //    (256 with the folded forces and the RK4 positions on the accelerations, 100 SGPRs: the ceiling of two waves per SIMD, with no register of headroom left -- a compiler that needs one more spills), no scratch.  The block can go back to the C++ form of the host branch below once that no longer splits the
+                //    (256 with the folded forces and the RK4 positions on the accelerations, 97 SGPRs with the constants a stage ahead: the ceiling of two waves per SIMD, with no register of headroom left -- a compiler that needs one more spills), no scratch.  The block can go back to the C++ form of the host branch below once that no longer splits the
                 //    schedule (same resource figures, same step time).
                 {
-                    const int kon = imp_on ? kimp : -1, dof = q.imp_dof;
+                    const int kon = imp_on ? kimp : -1, dof = HOLD ? dof_held : q.imp_dof;
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
                     for (int k = 0; k < NP; ++k)
@@ -518,6 +584,18 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                         if (c == 1) h += drag_force<T>(dragc, sv[k][1]);
                         r[k][c] = h - ((k + 1 < NP) ? fl[k + 1][c] : flR);
                     }
+                }
+                // -- AHEAD: the polynomial constants of the NEXT stage (stage 3: of the next step's stage 0), requested where this
+                //    stage's last use of them is behind: the request is tied to the finished right-hand side, the solve and the
+                //    RK4 ends below need no scalar register, and the values land under them
+                if constexpr (AHEAD) {
+#if defined(__HIP_DEVICE_COMPILE__)
+                    asm volatile("" : "+s"(FCn)
+                                 : "v"(r[0][0]), "v"(r[0][1]), "v"(r[0][2]), "v"(r[1][0]), "v"(r[1][1]), "v"(r[1][2]),
+                                   "v"(r[2][0]), "v"(r[2][1]), "v"(r[2][2]), "v"(r[3][0]), "v"(r[3][1]), "v"(r[3][2]));
+#endif
+#pragma unroll
+                    for (int i = 0; i < NK; ++i) fk_ahead[i] = FCn[i];
                 }
                 // -- mass solve: interior, separator right-hand side, separator levels, back substitution.  Every wave-uniform
                 //    constant is a row broadcast of `tab` inside a multiply-add (66 per stage), or one of the nine copies; each

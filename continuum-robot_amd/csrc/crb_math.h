@@ -403,6 +403,116 @@ CRB_HD ElemForceRegrouped<T> elem_force_nonlinear_folded(K k, const T ql[3], con
     return o;
 }
 
+// The folded form with the membrane strain's two combinations formed once.  In the folded constants the du and dw^2
+// coefficients of five sub-forms are pairwise proportional: with
+//   A1 = dw^2 - 2 L du          A2 = dw^2 - (2 L / 3) du
+// f2 and the dw factor of f3 take du and dw^2 only through A1, the eps factors of f3 and X and Rf only through A2:
+//   f2      = k A1 + k delta^2 + k eps^2
+//   cA1 LT  = k0 + k eps + k dw                                        (as folded)
+//   f3      = eps (k0 + k A2 + k delta^2 + k eps^2) + dw (k A1 + k delta^2 + k eps^2)
+//   X       = eps (k0 + k A2 + k delta^2 + k eps^2) + dw (k delta^2 + k eps^2)
+//   Rf      = k0 + k A2 + k delta^2 + k eps^2 + k (dw eps)
+// identically the folded form's polynomials in rational arithmetic (tests/test_shared_forces_cpu.py checks the identities,
+// the constants, and bounds the rounding against exact values next to the symmetric form's).  A1 and A2 cost one
+// multiply-add each, the four sums lose one each and Rf one: 38 fp64 instructions per element against 41, 27 constants
+// against 30.  A1 is rounded where it cancels (du ~ dw^2 / (2 L), the inextensible bend: the membrane strain itself), which
+// the folded form's f2 was not: an error of 2^-53 dw^2 times the factor, the size of f2's own dw^2 monomial's rounding.
+// The five sums of TWO products (the heads of f2 and of f3's dw factor, X's dw factor, X and f3) are written as one product
+// and an explicit fused multiply-add: left to contraction the compiler fuses either product, and which one it picks changes
+// with the code around the call (seen between two builds of the blocked stepper that differ only in where the constants
+// are loaded), so the roundings would not be a property of this function.
+template <typename T>
+CRB_HD T fused_madd(T a, T b, T c);   // a b + c, rounded once
+template <>
+CRB_HD double fused_madd<double>(double a, double b, double c) { return __builtin_fma(a, b, c); }
+template <>
+CRB_HD float fused_madd<float>(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+enum : int {
+    SK_EPS = 0, SK_A1, SK_A2,                                     // eps = sigma - k dw, A1 = dw^2 + k du, A2 = dw^2 + k du
+    SK_F2_A, SK_F2_D2, SK_F2_E2,                                  // f2
+    SK_LT_0, SK_LT_E, SK_LT_DW,                                   // cA1 LT
+    SK_F3E_0, SK_F3E_A, SK_F3E_D2, SK_F3E_E2,                     // f3, the factor of eps
+    SK_F3W_A, SK_F3W_D2, SK_F3W_E2,                               // f3, the factor of dw
+    SK_XE_0, SK_XE_A, SK_XE_D2, SK_XE_E2,                         // X, the factor of eps
+    SK_XW_D2, SK_XW_E2,                                           // X, the factor of dw
+    SK_R_0, SK_R_A, SK_R_D2, SK_R_E2, SK_R_DWE,                   // Rf
+    SK_N                                                          // 27
+};
+// The constants of a nonlinear pack, each formed in long double from the pack's values and rounded once.
+#if defined(__HIPCC__)
+__host__
+#endif
+inline void elem_share_build(const ElemCoef<double>& e, double k[SK_N]) {
+    const long double L = e.c[0], cA1 = e.c[1], cA3 = e.c[2], cD3 = e.c[3], cA4 = e.c[4], cD4 = e.c[5];
+    const long double L2 = L * L, L3 = L2 * L;
+    k[SK_EPS] = double(2.0L / L);                          // 2 / L
+    k[SK_A1] = double(-(2.0L * L));                        // -2 L
+    k[SK_A2] = double(-(2.0L * L / 3.0L));                 // -2 L / 3
+    k[SK_F2_A] = double(cA1 / 2.0L);                       // cA1 / 2
+    k[SK_F2_D2] = double(cA1 * L2 / 24.0L);                // cA1 L^2 / 24
+    k[SK_F2_E2] = double(cA1 * L2 / 40.0L);                // cA1 L^2 / 40
+    k[SK_LT_0] = double(cA1 * L);                          // cA1 L
+    k[SK_LT_E] = double(cA1 * L / 20.0L);                  // cA1 L / 20
+    k[SK_LT_DW] = double(-(cA1 / 2.0L));                   // -cA1 / 2
+    k[SK_F3E_0] = double(-(3.0L * cD3 * L));               // -3 cD3 L
+    k[SK_F3E_A] = double(-(3.0L * cA3 * L / 2.0L));        // -3/2 cA3 L
+    k[SK_F3E_D2] = double(3.0L * cA3 * L3 / 56.0L);        // 3/56 cA3 L^3
+    k[SK_F3E_E2] = double(-(cA3 * L3 / 56.0L));            // -cA3 L^3 / 56
+    k[SK_F3W_A] = double(5.0L * cA3);                      // 5 cA3
+    k[SK_F3W_D2] = double(3.0L * cA3 * L2 / 4.0L);         // 3/4 cA3 L^2
+    k[SK_F3W_E2] = double(15.0L * cA3 * L2 / 28.0L);       // 15/28 cA3 L^2
+    k[SK_XE_0] = double(3.0L * cD4 * L);                   // 3 cD4 L
+    k[SK_XE_A] = double(3.0L * cA4 * L / 20.0L);           // 3/20 cA4 L
+    k[SK_XE_D2] = double(11.0L * cA4 * L3 / 560.0L);       // 11/560 cA4 L^3
+    k[SK_XE_E2] = double(3.0L * cA4 * L3 / 560.0L);        // 3/560 cA4 L^3
+    k[SK_XW_D2] = double(cA4 * L2 / 20.0L);                // cA4 L^2 / 20
+    k[SK_XW_E2] = double(3.0L * cA4 * L2 / 140.0L);        // 3/140 cA4 L^2
+    k[SK_R_0] = double(cD4 * L);                           // cD4 L
+    k[SK_R_A] = double(cA4 * L / 4.0L);                    // cA4 L / 4
+    k[SK_R_D2] = double(cA4 * L3 / 80.0L);                 // cA4 L^3 / 80
+    k[SK_R_E2] = double(11.0L * cA4 * L3 / 560.0L);        // 11/560 cA4 L^3
+    k[SK_R_DWE] = double(cA4 * L2 / 10.0L);                // cA4 L^2 / 10
+}
+// (K: a plain or a constant-address-space pointer to the SK_N constants, or an array of them)
+template <typename T, typename K = const T*>
+CRB_HD ElemForceRegrouped<T> elem_force_nonlinear_shared(K k, const T ql[3], const T qr[3]) {
+    const T u2 = qr[0];
+    const T du = ql[0] - u2, dw = ql[1] - qr[1];
+    const T sg = ql[2] + qr[2], dl = ql[2] - qr[2];
+    const T eps = sg - k[SK_EPS] * dw;
+    const T e2 = eps * eps, d2 = dl * dl, dw2 = dw * dw;
+    const T A1 = dw2 + k[SK_A1] * du, A2 = dw2 + k[SK_A2] * du;
+
+    T f2 = fused_madd<T>(k[SK_F2_D2], d2, k[SK_F2_A] * A1);
+    f2 = f2 + k[SK_F2_E2] * e2;
+    T LT = k[SK_LT_0] + k[SK_LT_E] * eps;
+    LT = LT + k[SK_LT_DW] * dw;
+
+    T F3e = k[SK_F3E_0] + k[SK_F3E_A] * A2;
+    F3e = F3e + k[SK_F3E_D2] * d2;
+    F3e = F3e + k[SK_F3E_E2] * e2;
+    T F3w = fused_madd<T>(k[SK_F3W_D2], d2, k[SK_F3W_A] * A1);
+    F3w = F3w + k[SK_F3W_E2] * e2;
+    T Xe = k[SK_XE_0] + k[SK_XE_A] * A2;
+    Xe = Xe + k[SK_XE_D2] * d2;
+    Xe = Xe + k[SK_XE_E2] * e2;
+    const T Xw = fused_madd<T>(k[SK_XW_E2], e2, k[SK_XW_D2] * d2);
+    const T X = fused_madd<T>(dw, Xw, eps * Xe);
+    T Rf = k[SK_R_0] + k[SK_R_A] * A2;
+    Rf = Rf + k[SK_R_D2] * d2;
+    Rf = Rf + k[SK_R_E2] * e2;
+    Rf = Rf + k[SK_R_DWE] * (dw * eps);
+    const T Y = dl * Rf;
+
+    ElemForceRegrouped<T> o;
+    o.f2 = f2;
+    o.W = u2 * LT;
+    o.f3 = fused_madd<T>(dw, F3w, eps * F3e);
+    o.m_left = X + Y;
+    o.m_right = X - Y;
+    return o;
+}
+
 // Classical RK4 of a second-order system q' = v, v' = a(q, v), per component, with the position side carried on the
 // accelerations alone: with a_i the acceleration of stage i (evaluated at q_i and the stage velocity v_i),
 //   q_2 = q + dt/2 v     q_3 = q_2 + dt^2/4 a_1     q_4 = (q + dt v) + dt^2/2 a_2

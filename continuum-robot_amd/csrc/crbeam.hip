@@ -362,17 +362,19 @@ int device_assemble(crb_plan* p, const crb_beam_desc* descs, int nd, const std::
                       std::memcmp(&hs[j].drag, &hs[0].drag, sizeof(T)) == 0 && hs[j].mask[0] == T(1) && hs[j].mask[1] == T(1) &&
                       hs[j].mask[2] == T(1);
         if (uniform) {
-            std::vector<double> tab(size_t(blk_fold_offset(BLK_MAX_LV)) + FK_N);
+            std::vector<double> tab(size_t(blk_share_offset(BLK_MAX_LV)) + SK_N);
             double norms[BLK_MAX_LV];
             const int lv = blocked_factor(blk.data(), d->length[0], tab.data(), tab.data() + BU_N, norms);
             if (lv >= 1) {
-                // nonlinear elements: the force polynomials' folded constants behind the tables (crb_math.h: elem_fold_build)
+                // nonlinear elements: the force polynomials' folded constants behind the tables (crb_math.h: elem_fold_build),
+                // and behind those the constants of the form that shares the membrane combinations (elem_share_build)
                 const bool fold = hs[0].elem.kind == KIND_NONLINEAR;
-                const size_t n = size_t(blk_fold_offset(lv)) + (fold ? FK_N : 0);
+                const size_t n = fold ? size_t(blk_share_offset(lv)) + SK_N : size_t(blk_fold_offset(lv));
                 if (fold) {
                     ElemCoef<double> ecd;
                     for (int i = 0; i < 6; ++i) ecd.c[i] = double(hs[0].elem.c[i]);
                     elem_fold_build(ecd, tab.data() + blk_fold_offset(lv));
+                    elem_share_build(ecd, tab.data() + blk_share_offset(lv));
                 }
                 HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p->d_blocked), n * sizeof(double)));
                 HIP_TRY(hipMemcpy(p->d_blocked, tab.data(), n * sizeof(double), hipMemcpyHostToDevice));

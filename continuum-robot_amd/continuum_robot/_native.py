@@ -172,6 +172,8 @@ def load():
     L.crb_plan_set_status.argtypes = [vp, vp, C.c_longlong]
     L.crb_tangent_stiffness.argtypes = [vp, vp, vp, vp]
     L.crb_solve_static.argtypes = [vp, vp, C.POINTER(InputDesc), i32, i32, C.c_double, C.c_double, vp, vp, vp]
+    L.crb_static_jvp.argtypes = [vp, vp, vp, i32, vp, vp, vp]
+    L.crb_static_vjp.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     L.crb_feedback_work_bytes.restype = C.c_size_t
     L.crb_rhs_jvp.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp]
     L.crb_step_rk4_tangent.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, i32, C.POINTER(InputDesc),

@@ -197,6 +197,7 @@ class BeamEnsemble:
                                 else np.full(n_beams, self.n_elem))
         self.state = torch.zeros((n_beams, 2, self.n_node, 4), dtype=dtype, device=self.device)
         self.time = 0.0
+        self.static_status = None   # int32 [B] of the last static_jvp / static_vjp: 0, or -2 (non-finite sensitivity)
         self._lib = nat.load()
         # functional composition (step_composed): the built-in forces appear in the registry as markers, user forces
         # are torch callables; plans with a built-in force switched off are created on demand
@@ -518,6 +519,68 @@ class BeamEnsemble:
         self._keep = keep
         q = self.unpack_state(x)[:, :self.n]
         return StaticSolution(q, iters >= 0, iters, resid)
+
+    # ------------------------------------------------------------------ sensitivities of the equilibrium (crb_static.h)
+    def _static_sens(self, v_red, q_red, transpose: bool, params: bool, who: str):
+        """one crb_static_jvp / crb_static_vjp launch: (solution [D, B, n], param_bar or None, status [B], single)"""
+        v, single = self._dirs(v_red, self.n, f"{who}: {'qbar_red' if transpose else 'du_red'}")
+        D = v.shape[0]
+        x = self.state if q_red is None else self._positions(q_red)
+        vd = self._pack_dirs(v, False)
+        out = torch.empty_like(vd)
+        status = torch.empty((self.n_beams,), dtype=torch.int32, device=self.device)
+        param_bar = None
+        with self._on_device():
+            if transpose:
+                if params:
+                    param_bar = torch.zeros((D, self.n_beams, self.n_node, 8), dtype=self.dtype, device=self.device)
+                nat.check(self._lib.crb_static_vjp(self.plan.h, self._ptr(x), self._ptr(vd), int(D), self._ptr(out),
+                                                   self._ptr(param_bar), self._ptr(status), self._stream()))
+            else:
+                nat.check(self._lib.crb_static_jvp(self.plan.h, self._ptr(x), self._ptr(vd), int(D), self._ptr(out),
+                                                   self._ptr(status), self._stream()))
+        self._keep = [x, vd]
+        self.static_status = status
+        return self._unpack_force_dirs(out), param_bar, status, single
+
+    def static_jvp(self, du_red, q_red=None):
+        """Forward sensitivity of the static equilibrium (crb_static_jvp): dq = J^-1 du, the change of the rest shape of
+        ``solve_static`` with the held force -- its compliance -- with J = dk/dq - dg/dq the exact tangent at the reduced
+        positions ``q_red`` [B, n] (None: the resident state's positions, as in ``tangent_stiffness``).  ``du_red`` [B, n] or
+        D directions [D, B, n] in one launch; returns the same shape.  ``static_status`` [B] holds 0, or -2 for a beam
+        whose result is not finite (a singular tangent: the equilibrium is a limit point).  Entries past a beam's own DOFs
+        (mixed-topology ensembles) are zero.  fp64 ensembles only; refused for a PINNED root under gravity, whose tangent
+        is not block tridiagonal."""
+        out, _, _, single = self._static_sens(du_red, q_red, False, False, "static_jvp")
+        return out[0] if single else out
+
+    def static_vjp(self, qbar_red, q_red=None, params: bool = False):
+        """Reverse sensitivity of the static equilibrium (crb_static_vjp): for a cotangent ``qbar_red`` = dL/dq of the rest
+        shape ([B, n], or D cotangents [D, B, n] in one launch) returns f_bar = dL/d held_force = J^-T qbar in the same
+        shape, J as in ``static_jvp`` -- unsymmetric for nonlinear elements, so this is a solve of its own.  ``q_red``
+        [B, n]: the equilibrium (None: the resident state's positions).  With ``params=True`` also the dict of
+        ``step_adjoint_params`` (EA_scale, EI_scale, elastic_modulus, moment_inertia, gravity, ...: dL/d of the rod's own
+        parameters, mu . d(u - k + g)/d theta with mu = f_bar), its drag entries zero: nothing moves at rest.
+        ``static_status`` as in ``static_jvp``."""
+        out, param_bar, _, single = self._static_sens(qbar_red, q_red, True, params, "static_vjp")
+        fb = out[0] if single else out
+        if not params:
+            return fb
+        pd = self._param_dict(param_bar)
+        return fb, ({k: v[0] for k, v in pd.items()} if single else pd)
+
+    def equilibrium(self, held_force=None, q0=None, load_steps: int = 8, max_iter: int = 20, rtol: float = STATIC_RTOL,
+                    atol: float = 0.0):
+        """A differentiable ``solve_static``: (q [B, n], converged [B]) as a torch.autograd.Function whose backward is one
+        ``static_vjp`` launch at q -- ``loss.backward()`` reaches ``held_force`` [B, n] when it requires grad.  Rows of
+        beams that did not converge, or whose sensitivity status is -2 (singular tangent), get a ZERO gradient: their q
+        is not an equilibrium, so there is nothing the implicit function theorem could differentiate.  The rod's
+        parameters are not autograd inputs (the forward would need parameter overrides, as for ``rollout``); use
+        ``static_vjp(..., params=True)``.  Leaves ``state``, ``time`` and ``status`` alone.  fp64 ensembles only; once
+        differentiable."""
+        held = None if held_force is None else torch.as_tensor(held_force, dtype=self.dtype, device=self.device)
+        opts = dict(q0=q0, load_steps=int(load_steps), max_iter=int(max_iter), rtol=float(rtol), atol=float(atol))
+        return _Equilibrium.apply(self, opts, held)
 
     def rhs_device(self, x: torch.Tensor, u: Optional[torch.Tensor] = None) -> torch.Tensor:
         """xdot in device layout for a state (and optional force) in device layout."""
@@ -1699,3 +1762,28 @@ class _FeedbackRollout(torch.autograd.Function):
         ggain = gain_bar[0] if ctx.needs_input_grad[3] else None
         gref = ref_bar[0] if (ctx.has_ref and ctx.needs_input_grad[4]) else None
         return None, None, gx0, ggain, gref
+
+
+class _Equilibrium(torch.autograd.Function):
+    """BeamEnsemble.equilibrium: forward = crb_solve_static, backward = one crb_static_vjp at the solution"""
+
+    @staticmethod
+    def forward(ctx, ens, opts, held):
+        sol = ens.solve_static(None if held is None else held.detach(), opts["q0"], opts["load_steps"], opts["max_iter"],
+                               opts["rtol"], opts["atol"])
+        ctx.ens, ctx.has_held = ens, held is not None
+        ctx.save_for_backward(sol.q, sol.converged)
+        ctx.mark_non_differentiable(sol.converged)
+        return sol.q, sol.converged
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_q, g_conv):
+        ens = ctx.ens
+        q, converged = ctx.saved_tensors
+        if not (ctx.has_held and ctx.needs_input_grad[2]):
+            return None, None, None
+        g_q = torch.zeros_like(q) if g_q is None else g_q
+        fb, _, status, _ = ens._static_sens(g_q.to(ens.dtype).contiguous(), q, True, False, "equilibrium")
+        ok = (converged & (status == 0)).view(-1, 1)
+        return None, None, torch.where(ok, fb[0], torch.zeros_like(fb[0]))

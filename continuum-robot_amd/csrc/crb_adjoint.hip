@@ -30,4 +30,10 @@ hipError_t launch_param_grad(const KParams<double>& k, const AdjParams<double>& 
     hipLaunchKernelGGL((crb_param_grad_kernel<double>), dim3(groups, n_cot), dim3(threads), adjoint_lds_bytes<double>(threads), st, k, q);
     return hipGetLastError();
 }
+hipError_t launch_static_param(const KParams<double>& k, const AdjParams<double>& q, int groups, int n_cot, int threads,
+                               hipStream_t st) {
+    if (threads > ADJ_MAX_NT || n_cot < 1 || n_cot > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((crb_static_param_kernel<double>), dim3(groups, n_cot), dim3(threads), adjoint_lds_bytes<double>(threads), st, k, q);
+    return hipGetLastError();
+}
 }  // namespace crb

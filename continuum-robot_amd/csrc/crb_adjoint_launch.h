@@ -16,4 +16,7 @@ hipError_t launch_adj_backward_store(const KParams<double>& k, const AdjParams<d
                                      hipStream_t st);
 // crb_param_grad_kernel<double> (crb_paramgrad.h): the parameter sums of one segment of k.n_steps steps over q.work and q.rbar
 hipError_t launch_param_grad(const KParams<double>& k, const AdjParams<double>& q, int groups, int n_cot, int threads, hipStream_t st);
+// crb_static_param_kernel<double> (crb_paramgrad.h): crb_static_vjp's parameter records from q.work (the state) and q.rbar (mu)
+hipError_t launch_static_param(const KParams<double>& k, const AdjParams<double>& q, int groups, int n_cot, int threads,
+                               hipStream_t st);
 }  // namespace crb

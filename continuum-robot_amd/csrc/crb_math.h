@@ -925,32 +925,52 @@ struct Row3 {
     double A[9], B[9], C[9], r[3];
 };
 // Block-Jacobi normalisation of a row: B_i -> I (A, C, r multiplied by inv(B_i)).  What a level of the reduction reads
-// from the rows i - s and i + s is their normalised A, C and r.
+// from the rows i - s and i + s is their normalised A, C and r.  In two parts, so that one matrix pass can serve several
+// right-hand sides (crb_static_sens_kernel): the matrix part returns inv(B_i) for the right-hand sides.
+CRB_HD void row3_normalise_matrix(double A[9], double B[9], double C[9], double Bi[9]) {
+    double t[9];
+    inv3<double>(B, Bi);
+    mul3<double>(Bi, A, t);
+    for (int k = 0; k < 9; ++k) A[k] = t[k];
+    mul3<double>(Bi, C, t);
+    for (int k = 0; k < 9; ++k) C[k] = t[k];
+    for (int k = 0; k < 3; ++k) { B[k * 3 + 0] = k == 0; B[k * 3 + 1] = k == 1; B[k * 3 + 2] = k == 2; }
+}
+CRB_HD void row3_normalise_rhs(const double Bi[9], double r[3]) {
+    double v[3];
+    mulv3<double>(Bi, r, v);
+    for (int k = 0; k < 3; ++k) r[k] = v[k];
+}
 CRB_HD void row3_normalise(Row3& w) {
-    double Bi[9], t[9], v[3];
-    inv3<double>(w.B, Bi);
-    mul3<double>(Bi, w.A, t);
-    for (int k = 0; k < 9; ++k) w.A[k] = t[k];
-    mul3<double>(Bi, w.C, t);
-    for (int k = 0; k < 9; ++k) w.C[k] = t[k];
-    mulv3<double>(Bi, w.r, v);
-    for (int k = 0; k < 3; ++k) { w.r[k] = v[k]; w.B[k * 3 + 0] = k == 0; w.B[k * 3 + 1] = k == 1; w.B[k * 3 + 2] = k == 2; }
+    double Bi[9];
+    row3_normalise_matrix(w.A, w.B, w.C, Bi);
+    row3_normalise_rhs(Bi, w.r);
 }
 // One level of block cyclic reduction, factorisation and right-hand side together: with the normalised rows `me`, `lo` = row
 // i - s, `hi` = row i + s (zero blocks outside the beam) the couplings to i -+ s are eliminated:
 //   B' = I - A lo.C - C hi.A,   A' = -A lo.A,   C' = -C hi.C,   r' = r - A lo.r - C hi.r
+// The right-hand-side part reads the row's A and C from BEFORE the level.
+CRB_HD void row3_level_matrix(const double meA[9], const double meC[9], const double loA[9], const double loC[9],
+                              const double hiA[9], const double hiC[9], double outA[9], double outB[9], double outC[9]) {
+    double t[9], u[9];
+    mul3<double>(meA, loC, t);
+    mul3<double>(meC, hiA, u);
+    for (int k = 0; k < 9; ++k) outB[k] = ((k % 4) == 0 ? 1.0 : 0.0) - t[k] - u[k];
+    mul3<double>(meA, loA, t);
+    mul3<double>(meC, hiC, u);
+    for (int k = 0; k < 9; ++k) { outA[k] = -t[k]; outC[k] = -u[k]; }
+}
+CRB_HD void row3_level_rhs(const double meA[9], const double meC[9], const double mer[3], const double lor[3],
+                           const double hir[3], double outr[3]) {
+    double v[3], w[3];
+    mulv3<double>(meA, lor, v);
+    mulv3<double>(meC, hir, w);
+    for (int k = 0; k < 3; ++k) outr[k] = mer[k] - v[k] - w[k];
+}
 CRB_HD void row3_level(const Row3& me, const double loA[9], const double loC[9], const double lor[3], const double hiA[9],
                        const double hiC[9], const double hir[3], Row3& out) {
-    double t[9], u[9], v[3], w[3];
-    mul3<double>(me.A, loC, t);
-    mul3<double>(me.C, hiA, u);
-    for (int k = 0; k < 9; ++k) out.B[k] = ((k % 4) == 0 ? 1.0 : 0.0) - t[k] - u[k];
-    mul3<double>(me.A, loA, t);
-    mul3<double>(me.C, hiC, u);
-    for (int k = 0; k < 9; ++k) { out.A[k] = -t[k]; out.C[k] = -u[k]; }
-    mulv3<double>(me.A, lor, v);
-    mulv3<double>(me.C, hir, w);
-    for (int k = 0; k < 3; ++k) out.r[k] = me.r[k] - v[k] - w[k];
+    row3_level_matrix(me.A, me.C, loA, loC, hiA, hiC, out.A, out.B, out.C);
+    row3_level_rhs(me.A, me.C, me.r, lor, hir, out.r);
 }
 
 }  // namespace crb

@@ -42,6 +42,87 @@ __device__ __forceinline__ ElemCoef<T> stiffness_part(const ElemCoef<T>& e, bool
     return o;
 }
 
+// One stage point of the sums above: the state record `w` (positions at w[c], velocities a `plane` further) and the masked
+// rbar record `r` of this thread's node, both null-safe only through `valid`; the left neighbour's records lie one node
+// (4 values) before.  Adds into acc = (sA, sI, sD, gx, gy) in the order the rollout kernel has always used.  Whole workgroup
+// when grav_on (two barriers); drag_on false leaves sD alone (a static equilibrium has v = 0).
+template <typename T>
+__device__ __forceinline__ void param_stage_point(const AdjLds<T>& L, const Topo& tp, const SlotConst<T>& sc, const T (&ml)[3],
+                                                  const ElemCoef<T>& eA, const ElemCoef<T>& eI, const AdjIdx<T>& ix, bool valid,
+                                                  bool has_l, const T* w, const T* r, size_t plane, bool drag_on, bool grav_on,
+                                                  bool corrected, T (&acc)[5]) {
+    const int NT = L.NT;
+    T q[3] = {T(0), T(0), T(0)}, ql[3] = {T(0), T(0), T(0)}, rb[3] = {T(0), T(0), T(0)}, rl[3] = {T(0), T(0), T(0)};
+    T vw = T(0);
+    if (valid) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { q[c] = w[c] * sc.mask[c]; rb[c] = r[c]; }
+        if (drag_on) vw = w[plane + 1] * sc.mask[1];
+        if (has_l)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { ql[c] = w[c - 4] * ml[c]; rl[c] = r[c - 4]; }
+    }
+    T fl[3], fr[3];
+    elem_force<T>(eA, ql, q, corrected, fl, fr);
+    acc[0] = acc[0] - (rl[0] * fl[0] + rl[1] * fl[1] + rl[2] * fl[2] + rb[0] * fr[0] + rb[1] * fr[1] + rb[2] * fr[2]);
+    elem_force<T>(eI, ql, q, corrected, fl, fr);
+    acc[1] = acc[1] - (rl[0] * fl[0] + rl[1] * fl[1] + rl[2] * fl[2] + rb[0] * fr[0] + rb[1] * fr[1] + rb[2] * fr[2]);
+    if (drag_on) acc[2] = acc[2] + rb[1] * drag_force<T>(sc.drag, vw);
+    if (grav_on) {   // (workgroup-uniform)
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { L.q[c * NT + tp.t] = q[c]; L.rb[c * NT + tp.t] = rb[c]; }
+        __syncthreads();
+        T gb[2];
+#pragma unroll
+        for (int m = 0; m < 2; ++m) gb[m] = L.base[ix.sg[m][0]] + L.base[ix.sg[m][1]];
+        const T phi = ix.phim * (L.base[ix.fq[0]] + L.base[ix.fq[1]]);
+        T sn, cs;
+        crb_sincos(phi, &sn, &cs);
+        acc[3] = acc[3] + sc.half_mass * (cs * gb[0] - sn * gb[1]);
+        acc[4] = acc[4] + sc.half_mass * (sn * gb[0] + cs * gb[1]);
+    }
+}
+
+// crb_static_vjp's parameter records: one "stage point", the equilibrium itself.  aq.work = the state whose plane 0 holds q,
+// aq.rbar = mu [n_cot][B][n_node][4] (masked, as crb_static_sens_kernel stores it), aq.param_bar written, not accumulated.  No
+// drag term: the velocities of an equilibrium are zero whatever the state's second plane holds.  Grid and LDS as below.
+template <typename T>
+__global__ void __launch_bounds__(ADJ_MAX_NT) crb_static_param_kernel(const KParams<T> p, const AdjParams<T> aq) {
+    static_assert(sizeof(T) == 8, "the adjoint kernels are fp64");
+    const AdjLds<T> L = carve_adjoint_lds<T>(blockDim.x);
+    const int NT = L.NT;
+    int g;
+    const Topo tp = make_topo<T>(p, g);
+    const bool valid = tp.valid;
+    const size_t d = blockIdx.y;
+    const bool grav_on = (p.flags & 2u) != 0, corrected = (p.flags & 4u) != 0;
+    const SlotConst<T>* const slots = p.slot + size_t(tp.beam) * p.slot_stride;
+    const SlotConst<T> sc = valid ? slots[tp.j] : padding_slot<T>();
+    const bool has_l = valid && tp.j >= 1;
+    T ml[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) ml[c] = has_l ? slots[tp.j - 1].mask[c] : T(0);
+    const ElemCoef<T> eA = stiffness_part<T>(sc.elem, true), eI = stiffness_part<T>(sc.elem, false);
+    AdjIdx<T> ix;
+    adj_index<T>(p, aq, tp, sc, NT, ix);
+    if (threadIdx.x == 0) L.base[ADJ_LDS_ZERO * NT] = T(0);
+    const size_t plane = size_t(p.n_node) * 4, node = size_t(tp.j + p.off);
+    const size_t xoff = size_t(tp.beam) * 2 * plane + node * 4, uoff = size_t(tp.beam) * plane + node * 4;
+    T acc[5] = {T(0), T(0), T(0), T(0), T(0)};
+    param_stage_point<T>(L, tp, sc, ml, eA, eI, ix, valid, has_l, aq.work + xoff, aq.rbar + d * size_t(p.B) * plane + uoff, plane,
+                         false, grav_on, corrected, acc);
+    if (!valid) return;
+    T* const out = aq.param_bar + ((d * size_t(p.B) + tp.beam) * size_t(p.n_node) + node) * 8;
+#pragma unroll
+    for (int c = 0; c < 5; ++c) out[c] = acc[c];
+#pragma unroll
+    for (int c = 5; c < 8; ++c) out[c] = T(0);
+    if (p.off == 1 && tp.j == 0)
+#pragma unroll
+        for (int c = 0; c < 8; ++c) out[c - 8] = T(0);
+}
+
 // p: the plan's tables and shape, p.n_steps = steps of the segment.  aq: gadj / gadj_beam, work (stage points), rbar,
 // param_bar.  Grid groups x n_cot, blockDim = the plan's NT, adjoint_lds_bytes<T>(NT) of LDS.
 template <typename T>
@@ -84,38 +165,8 @@ __global__ void __launch_bounds__(ADJ_MAX_NT) crb_param_grad_kernel(const KParam
 #pragma unroll 1
         for (int s = 3; s >= 0; --s) {
             const size_t st = size_t(i) * 4 + size_t(s);
-            T q[3] = {T(0), T(0), T(0)}, ql[3] = {T(0), T(0), T(0)}, rb[3] = {T(0), T(0), T(0)}, rl[3] = {T(0), T(0), T(0)};
-            T vw = T(0);
-            if (valid) {
-                const T* const w = aq.work + st * state_sz + xoff;
-                const T* const r = aq.rbar + st * rb_sz + d * size_t(p.B) * plane + uoff;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) { q[c] = w[c] * sc.mask[c]; rb[c] = r[c]; }
-                vw = w[plane + 1] * sc.mask[1];
-                if (has_l)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) { ql[c] = w[c - 4] * ml[c]; rl[c] = r[c - 4]; }
-            }
-            T fl[3], fr[3];
-            elem_force<T>(eA, ql, q, corrected, fl, fr);
-            acc[0] = acc[0] - (rl[0] * fl[0] + rl[1] * fl[1] + rl[2] * fl[2] + rb[0] * fr[0] + rb[1] * fr[1] + rb[2] * fr[2]);
-            elem_force<T>(eI, ql, q, corrected, fl, fr);
-            acc[1] = acc[1] - (rl[0] * fl[0] + rl[1] * fl[1] + rl[2] * fl[2] + rb[0] * fr[0] + rb[1] * fr[1] + rb[2] * fr[2]);
-            if (drag_on) acc[2] = acc[2] + rb[1] * drag_force<T>(sc.drag, vw);
-            if (grav_on) {   // (workgroup-uniform)
-                __syncthreads();
-#pragma unroll
-                for (int c = 0; c < 3; ++c) { L.q[c * NT + tp.t] = q[c]; L.rb[c * NT + tp.t] = rb[c]; }
-                __syncthreads();
-                T gb[2];
-#pragma unroll
-                for (int m = 0; m < 2; ++m) gb[m] = L.base[ix.sg[m][0]] + L.base[ix.sg[m][1]];
-                const T phi = ix.phim * (L.base[ix.fq[0]] + L.base[ix.fq[1]]);
-                T sn, cs;
-                crb_sincos(phi, &sn, &cs);
-                acc[3] = acc[3] + sc.half_mass * (cs * gb[0] - sn * gb[1]);
-                acc[4] = acc[4] + sc.half_mass * (sn * gb[0] + cs * gb[1]);
-            }
+            param_stage_point<T>(L, tp, sc, ml, eA, eI, ix, valid, has_l, aq.work + st * state_sz + xoff,
+                                 aq.rbar + st * rb_sz + d * size_t(p.B) * plane + uoff, plane, drag_on, grav_on, corrected, acc);
         }
     }
     if (!valid) return;

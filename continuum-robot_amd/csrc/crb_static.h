@@ -1,5 +1,5 @@
 // crb_static.h -- static equilibrium and tangent stiffness of every beam of an ensemble (crb_solve_static,
-// crb_tangent_stiffness).
+// crb_tangent_stiffness), and the sensitivities of that equilibrium (crb_static_jvp, crb_static_vjp: the end of this file).
 //
 // Residual.  r(q) = k(q) - g(q) - u with the velocities zero (drag vanishes): the force balance whose zero is a rest shape,
 // i.e. the q at which crb_rhs returns zero acceleration.  k and g are evaluated per node exactly as the RHS kernels do
@@ -11,10 +11,12 @@
 // is assembled like the mass matrix (mass_add_as_left_elem / mass_add_as_right_elem): a node's own element contributes
 // K22 to B and K21 to A, the element on its right (its right neighbour's) K11 to B and K12 to C.  Gravity adds -dg/dq:
 // segment s's force depends on the rotation(s) its table entry phiA / phiB names.  For a FIXED root (the plain cantilever)
-// and for interior FIXED / PINNED nodes those lie on slots s and s + 1, inside the +-1 band of every node the segment
-// loads.  A PINNED root shifts the reduced indexing by two, and the phi row of node i then depends on the rotation source
-// of slot i + 2: such terms fall outside the band and are left out of the ITERATION matrix only (the residual keeps them;
-// Newton converges linearly instead of quadratically there -- they are O(rho A L g), against the element stiffness).
+// those lie on slots s and s + 1, inside the +-1 band of every node the segment loads.  A PINNED root (and any other
+// constraint that removes a number of DOFs that is no multiple of three ahead of a segment) shifts the reduced indexing, and
+// the row of node i then depends on a source two or more slots away: such terms fall outside the band and are left out of
+// the ITERATION matrix only (the residual keeps them; Newton converges linearly instead of quadratically there -- they are
+// O(rho A L g), against the element stiffness).  The plan builder records whether a plan has such terms
+// (gravity_out_of_band): the sensitivities at the end of this file, for which the tangent must be exact, refuse it.
 // Constrained DOFs get identity rows and columns.
 //
 // Newton homotopy from the initial guess q0:  H(q, lam) = r(q) - (1 - lam) r(q0),  lam = 0 -> 1 in load_steps equal
@@ -68,19 +70,20 @@ struct StaticLds {
     unsigned long long* red;
     int NT;
 };
+// (xcols: columns of the exchange buffer; crb_static_sens_kernel carries 18 + 3 NR per level)
 template <typename T>
-__host__ __device__ constexpr size_t static_lds_bytes(int NT) {
-    return size_t(26) * size_t(NT) * sizeof(T) + size_t(STATIC_RED_SLOTS) * 4 * sizeof(unsigned long long);
+__host__ __device__ constexpr size_t static_lds_bytes(int NT, int xcols = 21) {
+    return size_t(5 + xcols) * size_t(NT) * sizeof(T) + size_t(STATIC_RED_SLOTS) * 4 * sizeof(unsigned long long);
 }
 template <typename T>
-__device__ __forceinline__ StaticLds<T> carve_static_lds(int NT) {
+__device__ __forceinline__ StaticLds<T> carve_static_lds(int NT, int xcols = 21) {
     extern __shared__ __attribute__((aligned(16))) unsigned char crb_smem[];
     StaticLds<T> l;
     l.NT = NT;
     l.q = reinterpret_cast<T*>(crb_smem);
     l.x = l.q + 3 * NT;
-    l.g = l.x + 21 * NT;
-    l.red = reinterpret_cast<unsigned long long*>(crb_smem + size_t(26) * NT * sizeof(T));
+    l.g = l.x + xcols * NT;
+    l.red = reinterpret_cast<unsigned long long*>(crb_smem + size_t(5 + xcols) * NT * sizeof(T));
     return l;
 }
 
@@ -439,6 +442,224 @@ __global__ void __launch_bounds__(STATIC_MAX_NT, 1) crb_static_kernel(const KPar
         sp.iters[tp.beam] = state == 1 ? total : state;
         if (sp.residual) sp.residual[tp.beam] = resid;
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Sensitivities of the equilibrium (crb_static_jvp, crb_static_vjp).  With R(q; u, theta) = k(q) - g(q) - u = 0 the implicit
+// function theorem gives dq = J^-1 du and, for a cotangent qbar = dL/dq, mu = J^-T qbar = dL/du; dL/dtheta = mu . dr/dtheta
+// with r = u - k + g is crb_paramgrad.h's stage sum at the one point q (crb_static_param_kernel).  J is static_eval's exact
+// tangent (the plan builder refuses the plans whose gravity couplings fall outside its band); it does not depend on u.
+//
+// crb_static_sens_kernel<T, TRANSPOSE, NR>: grid groups x ceil(n_dir / NR), crb_static_kernel's mapping and tables.  One
+// tangent evaluation and, per pass, one Jacobi scaling and the matrix part of every reduction level serve NR right-hand
+// sides; the exchange carries 18 + 3 NR columns per level.  Two passes: the solve and one refinement step on b - J x.  TRANSPOSE turns the node row (A_j, B_j, C_j) of J into that of J^T,
+// ((C_{j-1})^T, B_j^T, (A_{j+1})^T), by one exchange of A and C.  Right-hand sides past n_dir (the tail chunk) are zero and
+// store nothing.  Everything that crosses lanes is a select on `inside the beam`, never a 0 / 1 factor: a beam whose q is not
+// finite leaves the beams that share its wave bitwise alone.
+template <typename T>
+struct StaticSensParams {
+    const T* rhs;       // [n_dir][B][n_node][4]: du, or qbar
+    T* sol;             // [n_dir][B][n_node][4]: dq = J^-1 du, or mu = J^-T qbar (component 3, constrained DOFs: 0)
+    int n_dir;
+    int32_t* status;    // [B] zeroed before the launch: -2 where a component of a direction is not finite; or null
+};
+__host__ __device__ constexpr int static_sens_xcols(int NR) { return 18 + 3 * NR > 21 ? 18 + 3 * NR : 21; }
+
+// static_solve for NR right-hand sides: r[k] in, x[k] out; A, B, C are consumed.  Whole workgroup; X = [18 + 3 NR][NT].
+template <int NR>
+__device__ __forceinline__ void static_solve_multi(const Topo& tp, double* X, int NT, int levels, double (&A)[9], double (&B)[9],
+                                                   double (&C)[9], double (&r)[NR][3], double (&x)[NR][3]) {
+    double d[3], dl[3], dh[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double a = fabs(B[4 * c]);
+        d[c] = (a > 0.0 && a < INFINITY) ? 1.0 / sqrt(a) : 1.0;
+        X[c * NT + tp.t] = d[c];
+    }
+    __syncthreads();
+    {
+        const bool hl = tp.j >= 1, hh = tp.j + 1 < tp.S;
+        const int tl = hl ? tp.thread_of(tp.j - 1) : tp.t, th = hh ? tp.thread_of(tp.j + 1) : tp.t;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { dl[c] = hl ? X[c * NT + tl] : 1.0; dh[c] = hh ? X[c * NT + th] : 1.0; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int k = 0; k < NR; ++k) r[k][i] *= d[i];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { A[3 * i + c] *= d[i] * dl[c]; B[3 * i + c] *= d[i] * d[c]; C[3 * i + c] *= d[i] * dh[c]; }
+    }
+    for (int l = 0; l < levels; ++l) {
+        const int s = 1 << l;
+        double Bi[9];
+        row3_normalise_matrix(A, B, C, Bi);
+#pragma unroll
+        for (int k = 0; k < NR; ++k) row3_normalise_rhs(Bi, r[k]);
+#pragma unroll
+        for (int e = 0; e < 9; ++e) { X[e * NT + tp.t] = A[e]; X[(9 + e) * NT + tp.t] = C[e]; }
+#pragma unroll
+        for (int k = 0; k < NR; ++k)
+#pragma unroll
+            for (int e = 0; e < 3; ++e) X[(18 + 3 * k + e) * NT + tp.t] = r[k][e];
+        __syncthreads();
+        const bool lo = tp.j - s >= 0, hi = tp.j + s < tp.S;
+        const int tl = lo ? tp.thread_of(tp.j - s) : tp.t, th = hi ? tp.thread_of(tp.j + s) : tp.t;
+#pragma unroll
+        for (int k = 0; k < NR; ++k) {   // (the right-hand sides first: they read the row's A and C of before the level)
+            double lor[3], hir[3], o[3];
+#pragma unroll
+            for (int e = 0; e < 3; ++e) {
+                lor[e] = lo ? X[(18 + 3 * k + e) * NT + tl] : 0.0;
+                hir[e] = hi ? X[(18 + 3 * k + e) * NT + th] : 0.0;
+            }
+            row3_level_rhs(A, C, r[k], lor, hir, o);
+#pragma unroll
+            for (int e = 0; e < 3; ++e) r[k][e] = o[e];
+        }
+        double loA[9], loC[9], hiA[9], hiC[9], oA[9], oC[9];
+#pragma unroll
+        for (int e = 0; e < 9; ++e) {
+            loA[e] = lo ? X[e * NT + tl] : 0.0;
+            loC[e] = lo ? X[(9 + e) * NT + tl] : 0.0;
+            hiA[e] = hi ? X[e * NT + th] : 0.0;
+            hiC[e] = hi ? X[(9 + e) * NT + th] : 0.0;
+        }
+        __syncthreads();
+        row3_level_matrix(A, C, loA, loC, hiA, hiC, oA, B, oC);
+#pragma unroll
+        for (int e = 0; e < 9; ++e) { A[e] = oA[e]; C[e] = oC[e]; }
+    }
+    double Bi[9];
+    inv3<double>(B, Bi);
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+        mulv3<double>(Bi, r[k], x[k]);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) x[k][c] *= d[c];
+    }
+}
+
+template <typename T, bool TRANSPOSE, int NR>
+__global__ void __launch_bounds__(STATIC_MAX_NT) crb_static_sens_kernel(const KParams<T> p, const StaticSensParams<T> sp) {
+    static_assert(sizeof(T) == 8, "the static sensitivities are fp64 (the reduction's rows are fp64)");
+    const int NT = blockDim.x;
+    const StaticLds<T> L = carve_static_lds<T>(NT, static_sens_xcols(NR));
+    int g;
+    const Topo tp = make_topo<T>(p, g);
+    const bool valid = tp.valid;
+    StaticConst<T> k;
+    static_load_const<T>(p, tp, k);
+    unsigned long long* const red = L.red + 4 * g;
+    for (int i = tp.t; i < STATIC_RED_SLOTS * 4; i += NT) L.red[i] = 0ull;   // (static_eval's barriers come before its use)
+    const size_t plane = size_t(p.n_node) * 4, node = size_t(tp.j + p.off);
+    const size_t voff = size_t(tp.beam) * plane + node * 4;
+    const int d0 = int(blockIdx.y) * NR;
+    bool fr[3];
+    T q[3] = {0.0, 0.0, 0.0};
+    double r[NR][3], x[NR][3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        fr[c] = valid && k.sc.mask[c] != T(0);
+        if (fr[c]) q[c] = p.x[size_t(tp.beam) * 2 * plane + node * 4 + c];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            r[i][c] = 0.0;
+            if (fr[c] && d0 + i < sp.n_dir) r[i][c] = sp.rhs[size_t(d0 + i) * size_t(p.B) * plane + voff + c];
+        }
+    }
+    double A[9], B[9], C[9];
+    {
+        T kq[3], gq[3];
+        static_eval<T, true>(p, L, tp, k, q, kq, gq, A, B, C);
+    }
+    if (TRANSPOSE) {
+        double* const X = L.x;
+#pragma unroll
+        for (int e = 0; e < 9; ++e) { X[e * NT + tp.t] = A[e]; X[(9 + e) * NT + tp.t] = C[e]; }
+        __syncthreads();
+        const bool hl = tp.j >= 1, hh = tp.j + 1 < tp.S;
+        const int tl = hl ? tp.thread_of(tp.j - 1) : tp.t, th = hh ? tp.thread_of(tp.j + 1) : tp.t;
+        double own[9];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                A[3 * i + c] = hl ? X[(9 + 3 * c + i) * NT + tl] : 0.0;   // (C_{j-1})^T
+                C[3 * i + c] = hh ? X[(3 * c + i) * NT + th] : 0.0;       // (A_{j+1})^T
+                own[3 * i + c] = B[3 * c + i];
+            }
+#pragma unroll
+        for (int e = 0; e < 9; ++e) B[e] = own[e];
+        __syncthreads();
+    }
+    // The solve, then ONE step of iterative refinement with the unscaled row: block cyclic reduction takes no pivots across
+    // blocks, and on tangents of condition 1e8 .. 1e10 its error reached twice LAPACK's own; the residual b - J x in fp64 and a
+    // second pass bring it to LAPACK's level.
+    double A0[9], B0[9], C0[9], r0[NR][3];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) { A0[e] = A[e]; B0[e] = B[e]; C0[e] = C[e]; }
+#pragma unroll
+    for (int i = 0; i < NR; ++i)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) r0[i][c] = r[i][c];
+    static_solve_multi<NR>(tp, L.x, NT, p.levels, A, B, C, r, x);
+    {
+        double* const X = L.x;
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < NR; ++i)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) X[(3 * i + c) * NT + tp.t] = x[i][c];
+        __syncthreads();
+        const bool hl = tp.j >= 1, hh = tp.j + 1 < tp.S;
+        const int tl = hl ? tp.thread_of(tp.j - 1) : tp.t, th = hh ? tp.thread_of(tp.j + 1) : tp.t;
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            double xl[3], xh[3], a[3], b[3], c3[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                xl[c] = hl ? X[(3 * i + c) * NT + tl] : 0.0;
+                xh[c] = hh ? X[(3 * i + c) * NT + th] : 0.0;
+            }
+            mulv3<double>(A0, xl, a);
+            mulv3<double>(B0, x[i], b);
+            mulv3<double>(C0, xh, c3);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) r[i][c] = r0[i][c] - a[c] - b[c] - c3[c];
+        }
+        __syncthreads();
+    }
+    {
+        double dx[NR][3];
+        static_solve_multi<NR>(tp, L.x, NT, p.levels, A0, B0, C0, r, dx);
+#pragma unroll
+        for (int i = 0; i < NR; ++i)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) x[i][c] += dx[i][c];
+    }
+    bool bad = false;
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        const bool on = valid && d0 + i < sp.n_dir;
+        T* const o = sp.sol + size_t(d0 + i) * size_t(p.B) * plane + voff;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double v = fr[c] ? x[i][c] : 0.0;
+            bad = bad || (on && !isfinite(v));
+            if (on) o[c] = v;
+        }
+        if (on) {
+            o[3] = 0.0;
+            if (p.off == 1 && tp.j == 0)   // node 0 (FIXED in every beam, no slot): zero
+#pragma unroll
+                for (int c = 0; c < 4; ++c) o[c - 4] = 0.0;
+        }
+    }
+    atomicMax(red, bad ? 1ull : 0ull);
+    __syncthreads();
+    if (valid && tp.j == 0 && sp.status && red[0] != 0ull) sp.status[tp.beam] = -2;
 }
 
 }  // namespace crb

@@ -66,6 +66,8 @@ struct crb_plan {
     int levels = 0, levels_full = 0, lognw = 0;
     size_t slot_stride = 0, lv_stride = 0, fin_stride = 0;  // per-beam coefficient tables (0 = shared)
     bool canonical_gravity = false;  // gravity index table is the nearest-neighbour pattern of the plain cantilever
+    bool gravity_out_of_band = false;  // a gravity rotation source lies more than one slot from a node its segment loads
+                                       // (a PINNED root): dg/dq leaves the block-tridiagonal tangent (crb_static.h)
     uint32_t flags = 0;
     int elem_mode = 0;           // EM_* (crb_generic.h)
     double gx = 0, gy = 0;
@@ -547,6 +549,14 @@ static int plan_create_impl(crb_plan** out, int device, int dtype, int n_beams, 
     for (int b = 0; b < nd; ++b) topo[b] = &topos[topo_of[b]];
     const BeamTopo& t0 = *topo[0];
     for (const BeamTopo& t : topos) p->h_grav_topo.push_back(t.grav);
+    for (const BeamTopo& t : topos)   // (tables of gravity-free topologies are empty of entries)
+        for (int j = 0; j < S; ++j)
+            for (int c = 0; c < 3; ++c)
+                for (const int sg : {int(t.grav[j].segA[c]), int(t.grav[j].segB[c])}) {
+                    if (sg < 0 || sg >= S) continue;
+                    for (const int src : {int(t.grav[sg].phiA), int(t.grav[sg].phiB)})
+                        if (src >= 0 && std::abs((src >> 2) - j) > 1) p->gravity_out_of_band = true;
+                }
     if (topos.size() > 1) p->grav_topo_of = topo_of;
     p->free_index = t0.free_index;
     p->full2red = t0.full2red;
@@ -2745,6 +2755,76 @@ extern "C" int crb_step_rk4_adjoint_params_sched(const crb_plan* p, const void* 
                                                  void* sched_bar, void* work, void* stream) {
     return adjoint_rollout(sched ? "crb_step_rk4_adjoint_params_sched" : "crb_step_rk4_adjoint_params", p, ckpt, lam, n_cot, t0,
                            dt, n_steps, every, in, rec_bar, grad, true, pgrad, sched, sched_bar, work, stream);
+}
+
+// ---- sensitivities of the equilibrium (crb_static.h: crb_static_sens_kernel; crb_paramgrad.h: crb_static_param_kernel)
+namespace {
+// every refusal before the device is touched, so that they hold for host-only plans too
+int static_sens_checks(const crb_plan* p, int n, const std::string& who, const char* count) {
+    if (n < 1 || n > 65535) return fail(CRB_EINVAL, who + ": " + count + " must be in [1, 65535]");
+    return CRB_OK;
+}
+int static_sens_plan_checks(const crb_plan* p, const std::string& who) {
+    if (p->dtype != CRB_F64) return fail(CRB_EUNSUPPORTED, who + ": the static sensitivities need an fp64 plan");
+    if (p->NT > STATIC_MAX_NT)
+        return fail(CRB_EUNSUPPORTED, who + ": beams of more than 256 thread-carried nodes are not supported");
+    if ((p->flags & CRB_FORCE_GRAVITY) && p->gravity_out_of_band)
+        return fail(CRB_EUNSUPPORTED, who + ": the gravity index table couples a node to a rotation more than one slot away (a "
+                                            "PINNED root under gravity); such terms lie outside the block-tridiagonal tangent, "
+                                            "and a sensitivity without them would be wrong");
+    return need_device(p, who.c_str());
+}
+}  // namespace
+
+extern "C" int crb_static_jvp(const crb_plan* p, const void* x, const void* du, int n_dir, void* dq, int32_t* status, void* stream) {
+    const std::string who = "crb_static_jvp";
+    if (!p) return fail(CRB_EINVAL, who + ": null plan");
+    if (!x || !du || !dq) return fail(CRB_EINVAL, who + ": null pointer");
+    if (int rc = static_sens_checks(p, n_dir, who, "n_dir")) return rc;
+    if (dq == x || dq == du || (status && (static_cast<const void*>(status) == x || static_cast<const void*>(status) == du ||
+                                           static_cast<const void*>(status) == dq)))
+        return fail(CRB_EINVAL, who + ": outputs must not alias inputs or each other");
+    if (int rc = static_sens_plan_checks(p, who)) return rc;
+    StaticSensParams<double> q{};
+    q.rhs = static_cast<const double*>(du);
+    q.sol = static_cast<double*>(dq);
+    q.n_dir = n_dir;
+    q.status = status;
+    HIP_TRY(crb::launch_static_sens(static_params<double>(p, x), q, false, (p->B + p->G - 1) / p->G, p->NT,
+                                    static_cast<hipStream_t>(stream)));
+    return CRB_OK;
+}
+
+extern "C" int crb_static_vjp(const crb_plan* p, const void* x, const void* q_bar, int n_cot, void* f_held_bar, void* param_bar,
+                              int32_t* status, void* stream) {
+    const std::string who = "crb_static_vjp";
+    if (!p) return fail(CRB_EINVAL, who + ": null plan");
+    if (!x || !q_bar || !f_held_bar) return fail(CRB_EINVAL, who + ": null pointer");
+    if (int rc = static_sens_checks(p, n_cot, who, "n_cot")) return rc;
+    const void* const st_v = status;
+    if (f_held_bar == x || f_held_bar == q_bar || (param_bar && (param_bar == x || param_bar == q_bar || param_bar == f_held_bar)) ||
+        (status && (st_v == x || st_v == q_bar || st_v == f_held_bar || st_v == param_bar)))
+        return fail(CRB_EINVAL, who + ": outputs must not alias inputs or each other");
+    if (int rc = static_sens_plan_checks(p, who)) return rc;
+    if (param_bar)
+        if (int rc = ensure_gadj(p, who.c_str())) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int groups = (p->B + p->G - 1) / p->G;
+    const KParams<double> k = static_params<double>(p, x);
+    StaticSensParams<double> q{};
+    q.rhs = static_cast<const double*>(q_bar);
+    q.sol = static_cast<double*>(f_held_bar);
+    q.n_dir = n_cot;
+    q.status = status;
+    HIP_TRY(crb::launch_static_sens(k, q, true, groups, p->NT, st));
+    if (param_bar) {
+        AdjParams<double> a = adj_params(p);
+        a.work = static_cast<const double*>(x);
+        a.rbar = static_cast<double*>(f_held_bar);
+        a.param_bar = static_cast<double*>(param_bar);
+        HIP_TRY(crb::launch_static_param(k, a, groups, n_cot, p->NT, st));
+    }
+    return CRB_OK;
 }
 
 // ------------------------------------------------------------------ adjoint of the closed loop (crb_feedback_adjoint.h)

@@ -320,6 +320,28 @@ int crb_step_rk4_adjoint_params(const crb_plan* plan, const void* ckpt, void* la
                                 int every, const crb_input_desc* input, const crb_record_desc* rec_bar,
                                 const crb_input_cotangent* grad, const crb_param_cotangent* pgrad, void* work, void* stream);
 
+/* Sensitivities of the static equilibrium of crb_solve_static.  With R(q; u, theta) = k(q) - g(q) - u = 0 and the exact
+ * tangent J = dk/dq - dg/dq at the positions of plane 0 of x [B][2][n_node][4], the implicit function theorem gives both
+ * directions -- what central differences over crb_solve_static would otherwise give, one Newton solve per parameter and no
+ * better than the equilibrium's residual floor.  J does not depend on the held force, so neither call takes an input.
+ *   du, dq, q_bar, f_held_bar   device [n][B][n_node][4], fp64; component 3, constrained DOFs, padding nodes and node 0 of
+ *                               plans without its slot come out zero
+ *   status                      device int32 [B] or NULL: 0, or -2 where a component of a direction is not finite (a singular
+ *                               tangent: the equilibrium is a limit point; or a non-finite q).  Other beams are unaffected.
+ * One launch solves 4 right-hand sides per workgroup (1 for n < 4) by the block cyclic reduction of crb_solve_static;
+ * n directions in one call are bitwise n calls of one.  Outputs must not alias inputs or each other.
+ * CRB_EINVAL: NULL plan or pointers, n outside 1 .. 65535, aliasing.  CRB_EUNSUPPORTED: fp32 plans; more than 256
+ * thread-carried nodes; plans with gravity whose index table couples a node to a rotation more than one slot away (a PINNED
+ * root under gravity: such terms lie outside the block-tridiagonal tangent -- crb_solve_static only iterates with it, a
+ * sensitivity would be wrong).  Then host-only plans: CRB_ENODEV. */
+/* dq = J^-1 du at the positions of plane 0 of x: the sensitivity of the static equilibrium to the held force. */
+int crb_static_jvp(const crb_plan* plan, const void* x, const void* du, int n_dir, void* dq, int32_t* status, void* stream);
+/* mu = J^-T q_bar (= dL/d held force) into f_held_bar; param_bar: NULL, or device [n_cot][B][n_node][8] crb_param_cotangent
+ * records (sA, sI, 0, gx, gy, 0, 0, 0) WRITTEN (not accumulated) from mu and q by the formulas of crb_step_rk4_adjoint_params
+ * with rbar := mu at the one point q and no drag (v = 0). */
+int crb_static_vjp(const crb_plan* plan, const void* x, const void* q_bar, int n_cot, void* f_held_bar, void* param_bar,
+                   int32_t* status, void* stream);
+
 /* Inverse lists of the gravity index table of beam `beam` (crb_plan_get_slot_tables' grav, reversed), host-only plans too:
  *   seg [n_slots][2][2]: per segment and force component (0 axial / 1 transverse), slot*4+dof of the node DOFs it adds to
  *   phi [n_slots][3][2]: per DOF of a slot, (segment << 1) | half of the segments whose rotation reads it (half: the segment

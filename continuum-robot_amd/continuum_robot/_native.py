@@ -211,6 +211,12 @@ def load():
                                                 C.POINTER(RecordDesc), C.POINTER(FeedbackCotangent), vp, vp]
     L.crb_step_rk4_feedback.argtypes = [vp, vp, C.c_double, C.c_double, i32, vp, vp, C.POINTER(InputDesc), vp,
                                         C.POINTER(C.c_double), vp]
+    L.crb_implicit_adjoint_work_bytes.restype = C.c_size_t
+    L.crb_implicit_adjoint_work_bytes.argtypes = [vp, i32, i32, i32]
+    L.crb_step_implicit_checkpoint.argtypes = [vp, vp, C.c_double, C.c_double, i32, i32, i32, C.POINTER(InputDesc),
+                                               C.POINTER(RecordDesc), vp, _dp, vp]
+    L.crb_step_implicit_adjoint.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, i32, i32, i32, C.POINTER(InputDesc),
+                                            C.POINTER(RecordDesc), C.POINTER(InputCotangent), vp, vp]
     _lib = L
     return L
 

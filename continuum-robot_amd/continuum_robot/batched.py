@@ -14,7 +14,7 @@ Reference interfaces mirrored (file:line under /root/reference/src/continuum_rob
 """
 import ctypes as C
 import pathlib
-from typing import NamedTuple, Optional, Sequence, Union
+from typing import NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import pandas as pd
@@ -813,18 +813,24 @@ class BeamEnsemble:
         return (xb[0], ub[0]) if single else (xb, ub)
 
     def checkpoint_interval(self, n_steps: int, checkpoint_every: Optional[int] = None,
-                            param_cotangents: Optional[int] = None, feedback_cotangents: Optional[int] = None) -> int:
+                            param_cotangents: Optional[int] = None, feedback_cotangents: Optional[int] = None,
+                            implicit: Optional[Tuple[int, int]] = None) -> int:
         """Steps per checkpoint segment of an adjoint rollout: ``checkpoint_every``, or ceil(sqrt(n_steps)) lowered until the
         work buffer of crb_step_rk4_adjoint (crb_rk4_adjoint_work_bytes) fits ADJOINT_WORK_BUDGET.  ``param_cotangents``: the
         number of cotangents of a ``step_adjoint_params`` call, whose work buffer
         (crb_rk4_adjoint_params_work_bytes) is sized instead; ``feedback_cotangents``: that of a ``step_feedback_adjoint`` call
-        (crb_rk4_feedback_adjoint_work_bytes)."""
+        (crb_rk4_feedback_adjoint_work_bytes); ``implicit`` = (n_iter, n_cot): that of a ``step_implicit_adjoint`` call
+        (crb_implicit_adjoint_work_bytes)."""
         if checkpoint_every is not None:
             if int(checkpoint_every) < 1:
                 raise ValueError("checkpoint_every must be >= 1")
             return int(checkpoint_every)
         every = max(1, int(np.ceil(np.sqrt(max(int(n_steps), 1)))))
-        if feedback_cotangents is not None:
+        if implicit is not None:
+            if param_cotangents is not None or feedback_cotangents is not None:
+                raise ValueError("checkpoint_interval: implicit and param_cotangents / feedback_cotangents are given together")
+            work_bytes = lambda e: self._lib.crb_implicit_adjoint_work_bytes(self.plan.h, e, int(implicit[0]), int(implicit[1]))  # noqa: E731
+        elif feedback_cotangents is not None:
             if param_cotangents is not None:
                 raise ValueError("checkpoint_interval: param_cotangents and feedback_cotangents are given together")
             work_bytes = lambda e: self._lib.crb_rk4_feedback_adjoint_work_bytes(self.plan.h, e, int(feedback_cotangents))  # noqa: E731
@@ -1032,6 +1038,87 @@ class BeamEnsemble:
                     index=int(impulse_index), record=record, record_every=int(record_every),
                     every=self.checkpoint_interval(n_steps, checkpoint_every), hold=hold)
         xT, samples = _Rollout.apply(self, opts, x0, amp, held, ctrl)
+        return (xT, samples) if record is not None else xT
+
+    # ------------------------------------------------------------------ adjoint of the implicit stepper (crb_implicit_adjoint.h)
+    def _implicit_checkpoint(self, x, n_steps, h, n_iter, t0, desc, every, rec):
+        """crb_step_implicit_checkpoint on the device state ``x`` (advanced in place): returns the checkpoint buffer
+        [n_seg, B, 3, n_node, 4] (q, v and the starting iterate of each segment's first step)"""
+        nseg = max(1, -(-int(n_steps) // every))
+        ckpt = torch.empty((nseg, self.n_beams, 3, self.n_node, 4), dtype=self.dtype, device=self.device)
+        t_end = C.c_double(0.0)
+        with self._on_device():
+            nat.check(self._lib.crb_step_implicit_checkpoint(self.plan.h, self._ptr(x), float(t0), float(h), int(n_steps),
+                                                             int(n_iter), int(every), C.byref(desc), self._ref(rec),
+                                                             self._ptr(ckpt), C.byref(t_end), self._stream()))
+        return ckpt
+
+    def _implicit_adjoint(self, ckpt, lamd, n_steps, h, n_iter, t0, desc, every, rec_bar, want_amp):
+        """crb_step_implicit_adjoint: lamd [D, B, 2, n_node, 4] in place; returns (amp_bar [D, B] or None,
+        f_bar [D, B, n_node, 4])"""
+        D = lamd.shape[0]
+        grad = nat.InputCotangent()
+        amp_bar = torch.zeros((D, self.n_beams), dtype=self.dtype, device=self.device) if want_amp else None
+        f_bar = torch.zeros((D, self.n_beams, self.n_node, 4), dtype=self.dtype, device=self.device)
+        grad.amp_bar = amp_bar.data_ptr() if amp_bar is not None else None
+        grad.f_held_bar = f_bar.data_ptr()
+        nbytes = int(self._lib.crb_implicit_adjoint_work_bytes(self.plan.h, int(every), int(n_iter), int(D)))
+        work = torch.empty((max(1, nbytes) + 7) // 8, dtype=torch.float64, device=self.device)
+        with self._on_device():
+            nat.check(self._lib.crb_step_implicit_adjoint(self.plan.h, self._ptr(ckpt), self._ptr(lamd), int(D), float(t0),
+                                                          float(h), int(n_steps), int(n_iter), int(every), C.byref(desc),
+                                                          self._ref(rec_bar), C.byref(grad), self._ptr(work), self._stream()))
+        self._keep = [work, ckpt, lamd, amp_bar, f_bar]
+        return amp_bar, f_bar
+
+    def step_implicit_adjoint(self, n_steps: int, h: float, lam_red, n_iter: int = 2, x0_red=None, impulse_amp=None,
+                              impulse_duration: float = 0.01, impulse_index: int = -2, held_force=None,
+                              t0: Optional[float] = None, record=None, record_every: int = 1, lam_record=None,
+                              checkpoint_every: Optional[int] = None):
+        """Gradient of a scalar loss through a rollout of ``step_implicit()`` (crb_step_implicit_checkpoint +
+        crb_step_implicit_adjoint) -- the stepper that takes h = 1e-4 ... 1e-3 s -- in ONE backward sweep: the arguments and
+        returns of ``step_adjoint``, (xbar0, amp_bar, f_held_bar) = (dL/dx(0) [B, 2n], dL/d impulse_amp [B] or None without
+        an impulse, dL/d held_force [B, n]), with a leading D axis when ``lam_red`` has one.  The derivative is the exact
+        transpose of the discrete map step_implicit computes -- ``n_iter`` (1 ... 16) modified-Newton iterations per step,
+        each step's iteration starting from the previous step's iterate -- not of the converged midpoint rule.  ``state``,
+        ``time`` and ``status`` are left alone; the result does not depend on ``checkpoint_every``, bitwise.  fp64 ensembles
+        only.  Not available: the damped variant (``rho_inf`` < 1), control schedules, the closed loop, and gradients with
+        respect to the rod's own parameters (E and I enter the iteration matrix)."""
+        lam, single = self._dirs(lam_red, 2 * self.n, "step_implicit_adjoint: lam_red")
+        D = lam.shape[0]
+        if isinstance(held_force, ControlSchedule):
+            raise NotImplementedError("step_implicit_adjoint: control schedules are not available in the implicit stepper's adjoint")
+        t0 = self.time if t0 is None else float(t0)
+        every = self.checkpoint_interval(n_steps, checkpoint_every, implicit=(n_iter, D))
+        desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index, held_force)
+        x = self.state.clone() if x0_red is None else self.pack_state(x0_red)
+        ckpt = self._implicit_checkpoint(x, n_steps, h, n_iter, t0, desc, every, None)
+        rec_bar, cot = self._record_cotangent(record, n_steps, record_every, lam_record, D)
+        lamd = self._pack_dirs(lam, True)
+        amp_bar, f_bar = self._implicit_adjoint(ckpt, lamd, n_steps, h, n_iter, t0, desc, every, rec_bar, impulse_amp is not None)
+        self._keep += keep + [x, cot]
+        xb, fb = self._unpack_dirs(lamd), self._unpack_force_dirs(f_bar)
+        return (xb[0], (amp_bar[0] if amp_bar is not None else None), fb[0]) if single else (xb, amp_bar, fb)
+
+    def rollout_implicit(self, x0_red, n_steps: int, h: float, n_iter: int = 2, impulse_amp=None, held_force=None,
+                         impulse_duration: float = 0.01, impulse_index: int = -2, t0: float = 0.0, record=None,
+                         record_every: int = 1, checkpoint_every: Optional[int] = None):
+        """A differentiable rollout of the implicit stepper: x(T) reduced [B, 2n] from ``x0_red`` after ``n_steps`` steps of
+        ``step_implicit()``'s map (and the ``record`` samples as step_implicit() returns them), as a torch.autograd.Function
+        whose backward is crb_step_implicit_adjoint -- ``loss.backward()`` reaches whichever of ``x0_red``, ``impulse_amp``
+        [B] and ``held_force`` [B, n] require grad, over the 0.1 ... 1 s horizons the examples simulate
+        (examples/reach_tip_implicit.py).  The forward is the checkpoint pass (it agrees with step_implicit to rounding),
+        whose checkpoints backward reuses.  Leaves ``state``, ``time`` and ``status`` alone.  fp64 ensembles only; once
+        differentiable; no control schedules, no damped variant."""
+        if isinstance(held_force, ControlSchedule):
+            raise NotImplementedError("rollout_implicit: control schedules are not available in the implicit stepper's adjoint")
+        x0 = torch.as_tensor(x0_red, dtype=self.dtype, device=self.device)
+        amp = None if impulse_amp is None else torch.as_tensor(impulse_amp, dtype=self.dtype, device=self.device)
+        held = None if held_force is None else torch.as_tensor(held_force, dtype=self.dtype, device=self.device)
+        opts = dict(n_steps=int(n_steps), h=float(h), n_iter=int(n_iter), t0=float(t0), duration=float(impulse_duration),
+                    index=int(impulse_index), record=record, record_every=int(record_every),
+                    every=self.checkpoint_interval(n_steps, checkpoint_every, implicit=(n_iter, 1)))
+        xT, samples = _ImplicitRollout.apply(self, opts, x0, amp, held)
         return (xT, samples) if record is not None else xT
 
     # ------------------------------------------------------------------ adjoint of the closed loop (crb_feedback_adjoint.h)
@@ -1722,6 +1809,46 @@ class _Rollout(torch.autograd.Function):
         gheld = ens._unpack_force_dirs(f_bar)[0] if (ctx.has_held and ctx.needs_input_grad[4]) else None
         gctrl = ens._unpack_sched_dirs(f_bar)[0] if (ctx.has_ctrl and ctx.needs_input_grad[5]) else None
         return None, None, gx0, gamp, gheld, gctrl
+
+
+class _ImplicitRollout(torch.autograd.Function):
+    """BeamEnsemble.rollout_implicit: forward = crb_step_implicit_checkpoint, backward = crb_step_implicit_adjoint on the saved
+    checkpoints"""
+
+    @staticmethod
+    def forward(ctx, ens, opts, x0, amp, held):
+        desc, keep = ens._input_desc(None if amp is None else amp.detach(), opts["duration"], opts["index"],
+                                     None if held is None else held.detach())
+        x = ens.pack_state(x0.detach())
+        rec, samples = ens._record_desc(opts["record"], opts["n_steps"], opts["record_every"])
+        ckpt = ens._implicit_checkpoint(x, opts["n_steps"], opts["h"], opts["n_iter"], opts["t0"], desc, opts["every"], rec)
+        ens._keep = keep + [x, samples]
+        ctx.ens, ctx.opts = ens, opts
+        ctx.has_amp, ctx.has_held = amp is not None, held is not None
+        ctx.save_for_backward(ckpt, None if amp is None else amp.detach(), None if held is None else held.detach())
+        if samples is None:
+            samples = torch.zeros(0, dtype=ens.dtype, device=ens.device)
+        if opts["record"] is None:
+            ctx.mark_non_differentiable(samples)
+        return ens.unpack_state(x), samples
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_x, g_samples):
+        ens, o = ctx.ens, ctx.opts
+        ckpt, amp, held = ctx.saved_tensors
+        desc, keep = ens._input_desc(amp, o["duration"], o["index"], held)
+        g_x = torch.zeros((ens.n_beams, 2 * ens.n), dtype=ens.dtype, device=ens.device) if g_x is None else g_x
+        lamd = ens._pack_dirs(g_x.to(ens.dtype).reshape(1, ens.n_beams, 2 * ens.n).contiguous(), True)
+        rec_bar, cot = ens._record_cotangent(o["record"], o["n_steps"], o["record_every"],
+                                             g_samples if o["record"] is not None else None, 1)
+        amp_bar, f_bar = ens._implicit_adjoint(ckpt, lamd, o["n_steps"], o["h"], o["n_iter"], o["t0"], desc, o["every"],
+                                               rec_bar, ctx.has_amp)
+        ens._keep += keep + [cot]
+        gx0 = ens._unpack_dirs(lamd)[0] if ctx.needs_input_grad[2] else None
+        gamp = amp_bar[0] if (ctx.has_amp and ctx.needs_input_grad[3]) else None
+        gheld = ens._unpack_force_dirs(f_bar)[0] if (ctx.has_held and ctx.needs_input_grad[4]) else None
+        return None, None, gx0, gamp, gheld
 
 
 class _FeedbackRollout(torch.autograd.Function):

@@ -1,0 +1,28 @@
+// crb_implicit_adjoint.hip -- the implicit stepper's adjoint kernels (crb_implicit_adjoint.h), one translation unit of their own.
+#include "crb_implicit_adjoint_launch.h"
+
+namespace crb {
+namespace {
+template <int MODE>
+hipError_t imp_adj_impl(const KParams<double>& k, const AdjParams<double>& q, const ImpAdjParams<double>& iq, int groups, int n_cot,
+                        int threads, hipStream_t st) {
+    if (threads > ADJ_MAX_NT || n_cot < 1 || n_cot > 65535 || iq.n_iter < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((crb_imp_adj_kernel<double, MODE>), dim3(groups, n_cot), dim3(threads), adjoint_lds_bytes<double>(threads), st,
+                       k, q, iq);
+    return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_imp_adj_checkpoint(const KParams<double>& k, const AdjParams<double>& q, const ImpAdjParams<double>& iq, int groups,
+                                     int threads, hipStream_t st) {
+    return imp_adj_impl<IADJ_CKPT>(k, q, iq, groups, 1, threads, st);
+}
+hipError_t launch_imp_adj_segment(const KParams<double>& k, const AdjParams<double>& q, const ImpAdjParams<double>& iq, int groups,
+                                  int threads, hipStream_t st) {
+    return imp_adj_impl<IADJ_SEG>(k, q, iq, groups, 1, threads, st);
+}
+hipError_t launch_imp_adj_backward(const KParams<double>& k, const AdjParams<double>& q, const ImpAdjParams<double>& iq, int groups,
+                                   int n_cot, int threads, hipStream_t st) {
+    return imp_adj_impl<IADJ_BWD>(k, q, iq, groups, n_cot, threads, st);
+}
+}  // namespace crb

@@ -19,6 +19,7 @@
 #include "crb_static_launch.h"
 #include "crb_tangent_launch.h"
 #include "crb_adjoint_launch.h"
+#include "crb_implicit_adjoint_launch.h"
 #include "crb_feedback_adjoint_launch.h"
 #include "crb_host.h"
 #include "crb_blocked.h"
@@ -2755,6 +2756,155 @@ extern "C" int crb_step_rk4_adjoint_params_sched(const crb_plan* p, const void* 
                                                  void* sched_bar, void* work, void* stream) {
     return adjoint_rollout(sched ? "crb_step_rk4_adjoint_params_sched" : "crb_step_rk4_adjoint_params", p, ckpt, lam, n_cot, t0,
                            dt, n_steps, every, in, rec_bar, grad, true, pgrad, sched, sched_bar, work, stream);
+}
+
+// ---- adjoint of the implicit stepper (crb_implicit_adjoint.h)
+namespace {
+constexpr int IMP_ADJ_MAX_ITER = 16;
+// the argument checks the two implicit-adjoint entry points share, in the documented order: CRB_EINVAL first (the caller adds
+// its own pointer and aliasing checks before this), then imp_adjoint_plan_checks
+int imp_adjoint_arg_checks(const std::string& who, int n_cot, int n_steps, int every, int n_iter, double h) {
+    if (n_cot < 1 || n_cot > 65535) return fail(CRB_EINVAL, who + ": n_cot must be in [1, 65535]");
+    if (n_steps < 0) return fail(CRB_EINVAL, who + ": n_steps must be >= 0");
+    if (every < 1) return fail(CRB_EINVAL, who + ": every must be >= 1");
+    if (n_iter < 1 || n_iter > IMP_ADJ_MAX_ITER) return fail(CRB_EINVAL, who + ": n_iter must be in [1, 16]");
+    if (!(h > 0)) return fail(CRB_EINVAL, who + ": h must be positive");
+    return CRB_OK;
+}
+int imp_adjoint_plan_checks(const crb_plan* p, const std::string& who) {
+    if (p->dtype != CRB_F64) return fail(CRB_EUNSUPPORTED, who + ": the adjoint of the implicit stepper needs an fp64 plan");
+    if (p->NT > ADJ_MAX_NT) return fail(CRB_EUNSUPPORTED, who + ": beams of more than 256 thread-carried nodes are not supported");
+    return CRB_OK;
+}
+// the launch parameters of the implicit adjoint kernels: A's tables (stiff_tables, for alpha = h^2 / 4) where M's are
+int imp_adjoint_params(const crb_plan* p, double h, hipStream_t st, KParams<double>* k) {
+    if (int rc = stiff_tables<double>(p, 0.25 * h * h, st)) return rc;
+    *k = base_params<double>(p);
+    const bool per_beam = p->asm_in->nd > 1;
+    k->pcr_levels = static_cast<const double*>(p->d_alevels);
+    k->pcr_final = static_cast<const double*>(p->d_afinal);
+    k->lv_stride = per_beam ? size_t(p->levels_full) * p->S * PCR_LEVEL_VALS : 0;
+    k->fin_stride = per_beam ? size_t(p->S) * PCR_FINAL_VALS : 0;
+    k->levels = p->stiff_levels;
+    k->dt = h;
+    return CRB_OK;
+}
+size_t force_doubles(const crb_plan* p) { return size_t(p->B) * size_t(p->n_node) * 4; }
+}  // namespace
+
+extern "C" size_t crb_implicit_adjoint_work_bytes(const crb_plan* p, int every, int n_iter, int n_cot) {
+    if (!p || every < 1 || n_iter < 1 || n_iter > IMP_ADJ_MAX_ITER || n_cot < 1 || n_cot > 65535) return 0;
+    return (size_t(every) * ((2 + size_t(n_iter)) * force_doubles(p) + 1) + size_t(n_cot) * force_doubles(p)) * sizeof(double);
+}
+
+extern "C" int crb_step_implicit_checkpoint(const crb_plan* p, void* x, double t0, double h, int n_steps, int n_iter, int every,
+                                            const crb_input_desc* in, const crb_record_desc* rec, void* ckpt, double* t_end,
+                                            void* stream) {
+    const std::string who("crb_step_implicit_checkpoint");
+    if (!p) return fail(CRB_EINVAL, who + ": null plan");
+    if (!x || !ckpt) return fail(CRB_EINVAL, who + ": null state or checkpoint buffer");
+    if (x == ckpt) return fail(CRB_EINVAL, who + ": the checkpoint buffer must not alias the state");
+    if (int rc = imp_adjoint_arg_checks(who, 1, n_steps, every, n_iter, h)) return rc;
+    Recording r;
+    if (int rc = decode_record(p, rec, n_steps, true, who.c_str(), &r)) return rc;
+    Forcing f;
+    if (int rc = decode_input(p, in, who.c_str(), &f)) return rc;
+    if (r.out && (r.out == x || r.out == ckpt)) return fail(CRB_EINVAL, who + ": the record must not alias the state or the checkpoints");
+    if (int rc = imp_adjoint_plan_checks(p, who)) return rc;
+    if (int rc = need_device(p, who.c_str())) return rc;
+    if (t_end) *t_end = clock_after(t0, h, n_steps);
+    if (n_steps == 0) return CRB_OK;
+    if (int rc = ensure_gadj(p, who.c_str())) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    KParams<double> k;
+    if (int rc = imp_adjoint_params(p, h, st, &k)) return rc;
+    k.x = static_cast<double*>(x);
+    set_io(k, f, &r);
+    k.t0 = t0; k.n_steps = n_steps;
+    AdjParams<double> q = adj_params(p);
+    q.states = static_cast<double*>(ckpt);
+    q.store_every = every;
+    q.write_back = 1;
+    ImpAdjParams<double> iq;
+    std::memset(&iq, 0, sizeof(iq));
+    iq.n_iter = n_iter;
+    HIP_TRY(crb::launch_imp_adj_checkpoint(k, q, iq, (p->B + p->G - 1) / p->G, p->NT, st));
+    return CRB_OK;
+}
+
+extern "C" int crb_step_implicit_adjoint(const crb_plan* p, const void* ckpt, void* lam, int n_cot, double t0, double h, int n_steps,
+                                         int n_iter, int every, const crb_input_desc* in, const crb_record_desc* rec_bar,
+                                         const crb_input_cotangent* grad, void* work, void* stream) {
+    const std::string who("crb_step_implicit_adjoint");
+    if (!p) return fail(CRB_EINVAL, who + ": null plan");
+    if (!ckpt || !lam) return fail(CRB_EINVAL, who + ": null checkpoint buffer or cotangent");
+    if (!work) return fail(CRB_EINVAL, who + ": null work buffer (crb_implicit_adjoint_work_bytes)");
+    void* const amp_bar = grad ? grad->amp_bar : nullptr;
+    void* const f_bar = grad ? grad->f_held_bar : nullptr;
+    const void* const rec_out = rec_bar ? rec_bar->out : nullptr;
+    const void* const held = in ? in->f_held : nullptr;
+    const void* bufs[6] = {ckpt, work, amp_bar, f_bar, rec_out, held};
+    for (const void* b : bufs)
+        if (b && b == lam) return fail(CRB_EINVAL, who + ": lam must not alias another buffer of the call");
+    if (work == ckpt || (amp_bar && (amp_bar == work || amp_bar == ckpt || amp_bar == f_bar)) ||
+        (f_bar && (f_bar == work || f_bar == ckpt)))
+        return fail(CRB_EINVAL, who + ": the output and work buffers must not alias each other or the checkpoints");
+    if (int rc = imp_adjoint_arg_checks(who, n_cot, n_steps, every, n_iter, h)) return rc;
+    Recording r;
+    if (int rc = decode_record(p, rec_bar, n_steps, true, who.c_str(), &r)) return rc;
+    Forcing f;
+    if (int rc = decode_input(p, in, who.c_str(), &f)) return rc;
+    if (amp_bar && !f.impulse)
+        return fail(CRB_EINVAL, who + ": amp_bar needs an impulse input (its amplitude is what it differentiates)");
+    if (int rc = imp_adjoint_plan_checks(p, who)) return rc;
+    if (int rc = need_device(p, who.c_str())) return rc;
+    if (n_steps == 0) return CRB_OK;
+    if (int rc = ensure_gadj(p, who.c_str())) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    KParams<double> base;
+    if (int rc = imp_adjoint_params(p, h, st, &base)) return rc;
+    set_io(base, f);
+    const int groups = (p->B + p->G - 1) / p->G;
+    const size_t sd = state_doubles(p), fd = force_doubles(p);
+    // (crb_implicit_adjoint_work_bytes: start states, iterates, clocks, carry)
+    double* const wstates = static_cast<double*>(work);
+    double* const witers = wstates + size_t(every) * sd;
+    double* const wclock = witers + size_t(every) * size_t(n_iter) * fd;
+    double* const wcarry = wclock + size_t(every);
+    const int nseg = (n_steps + every - 1) / every;
+    for (int g = nseg - 1; g >= 0; --g) {
+        const int k0 = g * every, n = (n_steps - k0) < every ? (n_steps - k0) : every;
+        KParams<double> k = base;
+        k.t0 = clock_after(t0, h, k0);   // (the checkpoint pass's clock at the segment start: the same additions)
+        k.n_steps = n;
+        // 1. the segment's step data from its checkpoint
+        AdjParams<double> q = adj_params(p);
+        q.states = wstates;
+        q.clocks = wclock;
+        ImpAdjParams<double> iq;
+        std::memset(&iq, 0, sizeof(iq));
+        iq.n_iter = n_iter;
+        iq.start = static_cast<const double*>(ckpt) + size_t(g) * 3 * fd;
+        iq.iters_out = witers;
+        HIP_TRY(crb::launch_imp_adj_segment(k, q, iq, groups, p->NT, st));
+        // 2. the sweep back over it, every cotangent
+        k.rec_out = static_cast<double*>(r.out); k.rec_slot = r.slot; k.rec_comp = r.comp; k.rec_every = r.every; k.rec_n = r.count;
+        AdjParams<double> b = adj_params(p);
+        b.work = wstates;
+        b.work_clock = wclock;
+        b.lam = static_cast<double*>(lam);
+        b.amp_bar = static_cast<double*>(amp_bar);
+        b.f_bar = static_cast<double*>(f_bar);
+        b.step0 = k0;
+        ImpAdjParams<double> ib;
+        std::memset(&ib, 0, sizeof(ib));
+        ib.n_iter = n_iter;
+        ib.iters = witers;
+        ib.carry = wcarry;
+        ib.carry_in = g < nseg - 1 ? 1 : 0;
+        HIP_TRY(crb::launch_imp_adj_backward(k, b, ib, groups, n_cot, p->NT, st));
+    }
+    return CRB_OK;
 }
 
 // ---- sensitivities of the equilibrium (crb_static.h: crb_static_sens_kernel; crb_paramgrad.h: crb_static_param_kernel)

@@ -618,6 +618,46 @@ int crb_step_rk4_adjoint_params_sched(const crb_plan* plan, const void* ckpt, vo
                                       const crb_input_cotangent* grad, const crb_param_cotangent* pgrad,
                                       const crb_input_schedule* sched, void* sched_bar, void* work, void* stream);
 
+/* ---- Adjoint of the implicit stepper: gradients through stiff rollouts (csrc/crb_implicit_adjoint.h).
+ * The exact discrete adjoint of the map crb_step_implicit computes (the implicit midpoint rule with n_iter modified-Newton
+ * iterations on A = M + h^2/4 K0, each step's iteration starting from the previous step's final iterate, 0 at the first step
+ * of a call) -- not of the converged rule.  The three calls below follow crb_rk4_adjoint_work_bytes,
+ * crb_step_rk4_checkpoint and crb_step_rk4_adjoint; lam, rec_bar and grad keep their layouts and accumulate semantics.
+ *
+ * crb_implicit_adjoint_work_bytes: device bytes of the work buffer of crb_step_implicit_adjoint,
+ *     (every * ((2 + n_iter) * B * n_node * 4 + 1) + n_cot * B * n_node * 4) * sizeof(double)
+ * -- per step of one segment its start state (q0, v0) [B][2][n_node][4], then the iterates a^0 .. a^{n_iter-1}
+ * [n_iter][B][n_node][4] of every step, then the steps' clocks, then per cotangent the carry [n_cot][B][n_node][4] (the
+ * cotangent of a segment's starting iterate, handed to the segment before it).  0 for a NULL plan, every < 1, n_iter outside
+ * 1 ... 16 or n_cot outside 1 ... 65535.
+ *
+ * crb_step_implicit_checkpoint: crb_step_implicit (same clock, same input, midpoint sampling; x advances in place, *t_end as
+ * there) in the adjoint's own arithmetic, writing the state and the starting iterate of steps 0, every, 2 every, ... to
+ * ckpt [ceil(n_steps / every)][B][3][n_node][4] (device; planes q, v, a).  rec: as crb_step_rk4_rec (may be NULL).  x agrees
+ * with crb_step_implicit to rounding, not bitwise.  Per-beam status is not written.
+ *
+ * crb_step_implicit_adjoint: the gradient of a scalar loss L(x(T), samples) of the rollout crb_step_implicit_checkpoint ran
+ * from t0 (the same h, n_steps, n_iter, every and input) with respect to x(0), amp and f_held, for n_cot cotangents:
+ *   lam      device [n_cot][B][2][n_node][4], in place: dL/dx(T) on entry, dL/dx(0) on exit
+ *   rec_bar  the record of the forward pass with out = the cotangent of its samples (as crb_step_rk4_adjoint), or NULL
+ *   grad     amp_bar / f_held_bar += dL/d amp, dL/d f_held (may be NULL)
+ *   work     crb_implicit_adjoint_work_bytes(plan, every, n_iter, n_cot) device bytes
+ * Per segment, last to first: one launch recomputes the segment's step data from its checkpoint, one sweeps it back for all
+ * cotangents.  The result is bitwise independent of `every`, and D cotangents in one call are bitwise D calls of one.
+ *
+ * Refusals, all before the device is touched, crb_last_error() naming the entry point, in this order: CRB_EINVAL for a NULL
+ * plan or buffer, aliasing buffers, n_cot outside 1 ... 65535, n_steps < 0, every < 1, n_iter outside 1 ... 16, h <= 0, a bad
+ * input or record description, amp_bar without an impulse input; CRB_EUNSUPPORTED for fp32 plans and beams of more than 256
+ * thread-carried nodes; CRB_ENODEV for host-only plans.  *t_end is written only by a call that is not refused.
+ * Not covered: the damped variant (rho_inf < 1), control schedules, the closed loop, and parameter gradients (E and I enter A
+ * and K0, so with a fixed iteration count the dependence is not the linear sum crb_step_rk4_adjoint_params computes). */
+size_t crb_implicit_adjoint_work_bytes(const crb_plan* plan, int every, int n_iter, int n_cot);
+int crb_step_implicit_checkpoint(const crb_plan* plan, void* x, double t0, double h, int n_steps, int n_iter, int every,
+                                 const crb_input_desc* input, const crb_record_desc* rec, void* ckpt, double* t_end, void* stream);
+int crb_step_implicit_adjoint(const crb_plan* plan, const void* ckpt, void* lam, int n_cot, double t0, double h, int n_steps,
+                              int n_iter, int every, const crb_input_desc* input, const crb_record_desc* rec_bar,
+                              const crb_input_cotangent* grad, void* work, void* stream);
+
 /* out[b] = x[b][plane][node][dof]  (e.g. tip displacement = plane 0, node n_elem, dof 1;
  * lqr_control.py:168) */
 int crb_gather_dof(const crb_plan* plan, const void* x, int plane, int node, int dof, void* out, void* stream);

@@ -399,6 +399,16 @@ class BeamEnsemble:
             keep.append(held)
         return desc, keep
 
+    def _sample_address(self, samples):
+        """The address of a record buffer for a crb_record_desc.  A call that takes no sample (record_every > n_steps) has an
+        empty buffer, which has no address, and the library refuses a NULL ``out`` before it counts the samples: such a
+        call gets the address of a one-element placeholder, which nothing reads or writes."""
+        if samples.numel() > 0:
+            return samples.data_ptr()
+        if getattr(self, "_no_samples", None) is None:
+            self._no_samples = torch.zeros(1, dtype=self.dtype, device=self.device)
+        return self._no_samples.data_ptr()
+
     def _record_desc(self, record, n: int, every: int = 1):
         """The crb_record_desc of a call and its zeroed buffer of n_samples = n // every samples (n steps, a sample every
         ``every``-th; or the n points of a t_eval grid): record="all" = whole-state snapshots (every DOF of the reference's
@@ -409,11 +419,12 @@ class BeamEnsemble:
         n_samples = int(n) // int(every)
         if isinstance(record, str) and record == "all":
             samples = torch.zeros((n_samples,) + tuple(self.state.shape), dtype=self.dtype, device=self.device)
-            return nat.RecordDesc(0, -1, 0, int(every), samples.data_ptr()), samples
+            return nat.RecordDesc(0, -1, 0, int(every), self._sample_address(samples)), samples
         node, param = record
         vel = param.startswith("d") and param.endswith("_dt")
         samples = torch.zeros((self.n_beams, n_samples), dtype=self.dtype, device=self.device)
-        return nat.RecordDesc(int(vel), int(node), _PARAM[param[1:-3] if vel else param], int(every), samples.data_ptr()), samples
+        return nat.RecordDesc(int(vel), int(node), _PARAM[param[1:-3] if vel else param], int(every),
+                              self._sample_address(samples)), samples
 
     def _control(self, held_force, control, control_hold, n_steps, who):
         """The held force or the control schedule of a call of the RK4 rollout family: (held_force, None) or
@@ -953,7 +964,7 @@ class BeamEnsemble:
             if tuple(cot.shape[1:]) != tuple(samples.shape) or cot.shape[0] not in (1, D):
                 raise ValueError(f"lam_record: expected shape {tuple(samples.shape)} or [D, ...] of it, got {tuple(cot.shape)}")
             cot = cot.expand(shape).contiguous()
-        rec.out = cot.data_ptr()
+        rec.out = self._sample_address(cot)
         return rec, cot
 
     def step_adjoint(self, n_steps: int, dt: float, lam_red, x0_red=None, impulse_amp=None, impulse_duration: float = 0.01,

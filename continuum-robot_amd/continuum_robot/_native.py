@@ -217,6 +217,12 @@ def load():
                                                C.POINTER(RecordDesc), vp, _dp, vp]
     L.crb_step_implicit_adjoint.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, i32, i32, i32, C.POINTER(InputDesc),
                                             C.POINTER(RecordDesc), C.POINTER(InputCotangent), vp, vp]
+    L.crb_step_implicit_sched.argtypes = [vp, vp, C.c_double, C.c_double, i32, i32, C.POINTER(InputDesc), sched,
+                                          C.POINTER(RecordDesc), _dp, vp]
+    L.crb_step_implicit_checkpoint_sched.argtypes = [vp, vp, C.c_double, C.c_double, i32, i32, i32, C.POINTER(InputDesc), sched,
+                                                     C.POINTER(RecordDesc), vp, _dp, vp]
+    L.crb_step_implicit_adjoint_sched.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, i32, i32, i32, C.POINTER(InputDesc),
+                                                  C.POINTER(RecordDesc), C.POINTER(InputCotangent), sched, vp, vp, vp]
     _lib = L
     return L
 

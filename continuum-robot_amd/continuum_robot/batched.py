@@ -37,7 +37,9 @@ class ControlSchedule(NamedTuple):
     """A piecewise-constant control sequence for the RK4 rollout family (crb_input_schedule): ``control`` reduced [K, B, n],
     vector k held for RK4 steps k * hold .. (k + 1) * hold - 1 of the call.  ``step``, ``step_adjoint_params`` and ``rollout``
     take it as ``control=`` / ``control_hold=``; every method of the family -- ``step_tangent`` and ``step_adjoint`` this way
-    only -- takes it in place of a held force, ``held_force=ControlSchedule(U, hold)``."""
+    only -- takes it in place of a held force, ``held_force=ControlSchedule(U, hold)``.  The implicit family takes it too
+    (``step_implicit`` and ``rollout_implicit`` both ways, ``step_implicit_adjoint`` in place of a held force); ``hold`` then
+    counts implicit steps."""
     control: object
     hold: int
 
@@ -426,10 +428,10 @@ class BeamEnsemble:
         return nat.RecordDesc(int(vel), int(node), _PARAM[param[1:-3] if vel else param], int(every),
                               self._sample_address(samples)), samples
 
-    def _control(self, held_force, control, control_hold, n_steps, who):
-        """The held force or the control schedule of a call of the RK4 rollout family: (held_force, None) or
+    def _control(self, held_force, control, control_hold, n_steps, who, unit="RK4 steps"):
+        """The held force or the control schedule of a call of a rollout family: (held_force, None) or
         (None, (control [K, B, n] on the device, hold)).  A schedule comes as ``control`` / ``control_hold`` or as
-        ``held_force=ControlSchedule(control, hold)``."""
+        ``held_force=ControlSchedule(control, hold)``.  ``unit``: what ``hold`` counts, for the error text."""
         if isinstance(held_force, ControlSchedule):
             if control is not None or control_hold is not None:
                 raise ValueError(f"{who}: a ControlSchedule as held_force and control= are given together")
@@ -441,7 +443,7 @@ class BeamEnsemble:
         if held_force is not None:
             raise ValueError(f"{who}: control and held_force are given together (a schedule takes the held force's place)")
         if control_hold is None or int(control_hold) != control_hold or int(control_hold) < 1:
-            raise ValueError(f"{who}: control_hold must be an integer >= 1 (RK4 steps per interval)")
+            raise ValueError(f"{who}: control_hold must be an integer >= 1 ({unit} per interval)")
         U = torch.as_tensor(control, dtype=self.dtype, device=self.device)
         if U.dim() != 3 or tuple(U.shape[1:]) != (self.n_beams, self.n) or U.shape[0] < 1:
             raise ValueError(f"{who}: control must be [K >= 1, {self.n_beams}, {self.n}], got {tuple(U.shape)}")
@@ -1052,33 +1054,39 @@ class BeamEnsemble:
         return (xT, samples) if record is not None else xT
 
     # ------------------------------------------------------------------ adjoint of the implicit stepper (crb_implicit_adjoint.h)
-    def _implicit_checkpoint(self, x, n_steps, h, n_iter, t0, desc, every, rec):
-        """crb_step_implicit_checkpoint on the device state ``x`` (advanced in place): returns the checkpoint buffer
-        [n_seg, B, 3, n_node, 4] (q, v and the starting iterate of each segment's first step)"""
+    def _implicit_checkpoint(self, x, n_steps, h, n_iter, t0, desc, every, rec, sd=None):
+        """crb_step_implicit_checkpoint (with the crb_input_schedule ``sd``: crb_step_implicit_checkpoint_sched) on the device
+        state ``x`` (advanced in place): returns the checkpoint buffer [n_seg, B, 3, n_node, 4] (q, v and the starting iterate
+        of each segment's first step)"""
         nseg = max(1, -(-int(n_steps) // every))
         ckpt = torch.empty((nseg, self.n_beams, 3, self.n_node, 4), dtype=self.dtype, device=self.device)
         t_end = C.c_double(0.0)
         with self._on_device():
-            nat.check(self._lib.crb_step_implicit_checkpoint(self.plan.h, self._ptr(x), float(t0), float(h), int(n_steps),
-                                                             int(n_iter), int(every), C.byref(desc), self._ref(rec),
-                                                             self._ptr(ckpt), C.byref(t_end), self._stream()))
+            nat.check(self._lib.crb_step_implicit_checkpoint_sched(self.plan.h, self._ptr(x), float(t0), float(h), int(n_steps),
+                                                                   int(n_iter), int(every), C.byref(desc), self._ref(sd),
+                                                                   self._ref(rec), self._ptr(ckpt), C.byref(t_end),
+                                                                   self._stream()))
         return ckpt
 
-    def _implicit_adjoint(self, ckpt, lamd, n_steps, h, n_iter, t0, desc, every, rec_bar, want_amp):
+    def _implicit_adjoint(self, ckpt, lamd, n_steps, h, n_iter, t0, desc, every, rec_bar, want_amp, sd=None):
         """crb_step_implicit_adjoint: lamd [D, B, 2, n_node, 4] in place; returns (amp_bar [D, B] or None,
-        f_bar [D, B, n_node, 4])"""
+        f_bar [D, B, n_node, 4]).  ``sd``: the crb_input_schedule of the forward pass -- crb_step_implicit_adjoint_sched, and
+        f_bar is the schedule's cotangent [D, K, B, n_node, 4]."""
         D = lamd.shape[0]
         grad = nat.InputCotangent()
         amp_bar = torch.zeros((D, self.n_beams), dtype=self.dtype, device=self.device) if want_amp else None
-        f_bar = torch.zeros((D, self.n_beams, self.n_node, 4), dtype=self.dtype, device=self.device)
+        f_bar = torch.zeros((D,) + (() if sd is None else (int(sd.n_intervals),)) + (self.n_beams, self.n_node, 4),
+                            dtype=self.dtype, device=self.device)
         grad.amp_bar = amp_bar.data_ptr() if amp_bar is not None else None
-        grad.f_held_bar = f_bar.data_ptr()
+        grad.f_held_bar = f_bar.data_ptr() if sd is None else None
         nbytes = int(self._lib.crb_implicit_adjoint_work_bytes(self.plan.h, int(every), int(n_iter), int(D)))
         work = torch.empty((max(1, nbytes) + 7) // 8, dtype=torch.float64, device=self.device)
-        with self._on_device():
-            nat.check(self._lib.crb_step_implicit_adjoint(self.plan.h, self._ptr(ckpt), self._ptr(lamd), int(D), float(t0),
-                                                          float(h), int(n_steps), int(n_iter), int(every), C.byref(desc),
-                                                          self._ref(rec_bar), C.byref(grad), self._ptr(work), self._stream()))
+        with self._on_device():   # (f_bar is grad.f_held_bar without a schedule, sched_bar with one)
+            nat.check(self._lib.crb_step_implicit_adjoint_sched(self.plan.h, self._ptr(ckpt), self._ptr(lamd), int(D), float(t0),
+                                                                float(h), int(n_steps), int(n_iter), int(every), C.byref(desc),
+                                                                self._ref(rec_bar), C.byref(grad), self._ref(sd),
+                                                                self._ptr(f_bar if sd is not None else None), self._ptr(work),
+                                                                self._stream()))
         self._keep = [work, ckpt, lamd, amp_bar, f_bar]
         return amp_bar, f_bar
 
@@ -1093,43 +1101,52 @@ class BeamEnsemble:
         transpose of the discrete map step_implicit computes -- ``n_iter`` (1 ... 16) modified-Newton iterations per step,
         each step's iteration starting from the previous step's iterate -- not of the converged midpoint rule.  ``state``,
         ``time`` and ``status`` are left alone; the result does not depend on ``checkpoint_every``, bitwise.  fp64 ensembles
-        only.  Not available: the damped variant (``rho_inf`` < 1), control schedules, the closed loop, and gradients with
-        respect to the rod's own parameters (E and I enter the iteration matrix)."""
+        only.
+        ``held_force=ControlSchedule(U, hold)`` differentiates the rollout of step_implicit(control=U, control_hold=hold)
+        (crb_step_implicit_checkpoint_sched + crb_step_implicit_adjoint_sched): the third return is then dL/d control, [K, B, n]
+        ([D, K, B, n]); intervals the rollout does not reach, and entries past a beam's own DOF count in mixed-topology
+        ensembles, are exact zeros.  The scheduled rollout is the chain of one call per interval, so every interval's first step
+        starts its iteration from 0 and the cotangent carried through the starting iterate is dropped there.
+        Not available: the damped variant (``rho_inf`` < 1), the closed loop, and gradients with respect to the rod's own
+        parameters (E and I enter the iteration matrix)."""
         lam, single = self._dirs(lam_red, 2 * self.n, "step_implicit_adjoint: lam_red")
         D = lam.shape[0]
-        if isinstance(held_force, ControlSchedule):
-            raise NotImplementedError("step_implicit_adjoint: control schedules are not available in the implicit stepper's adjoint")
+        held_force, sch = self._control(held_force, None, None, n_steps, "step_implicit_adjoint", "implicit steps")
         t0 = self.time if t0 is None else float(t0)
         every = self.checkpoint_interval(n_steps, checkpoint_every, implicit=(n_iter, D))
         desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index, held_force)
+        sd, packed = self._sched_desc(sch)
         x = self.state.clone() if x0_red is None else self.pack_state(x0_red)
-        ckpt = self._implicit_checkpoint(x, n_steps, h, n_iter, t0, desc, every, None)
+        ckpt = self._implicit_checkpoint(x, n_steps, h, n_iter, t0, desc, every, None, sd)
         rec_bar, cot = self._record_cotangent(record, n_steps, record_every, lam_record, D)
         lamd = self._pack_dirs(lam, True)
-        amp_bar, f_bar = self._implicit_adjoint(ckpt, lamd, n_steps, h, n_iter, t0, desc, every, rec_bar, impulse_amp is not None)
-        self._keep += keep + [x, cot]
-        xb, fb = self._unpack_dirs(lamd), self._unpack_force_dirs(f_bar)
+        amp_bar, f_bar = self._implicit_adjoint(ckpt, lamd, n_steps, h, n_iter, t0, desc, every, rec_bar, impulse_amp is not None,
+                                                sd)
+        self._keep += keep + [x, cot, packed]
+        xb, fb = self._unpack_dirs(lamd), (self._unpack_force_dirs(f_bar) if sd is None else self._unpack_sched_dirs(f_bar))
         return (xb[0], (amp_bar[0] if amp_bar is not None else None), fb[0]) if single else (xb, amp_bar, fb)
 
     def rollout_implicit(self, x0_red, n_steps: int, h: float, n_iter: int = 2, impulse_amp=None, held_force=None,
                          impulse_duration: float = 0.01, impulse_index: int = -2, t0: float = 0.0, record=None,
-                         record_every: int = 1, checkpoint_every: Optional[int] = None):
+                         record_every: int = 1, checkpoint_every: Optional[int] = None, control=None,
+                         control_hold: Optional[int] = None):
         """A differentiable rollout of the implicit stepper: x(T) reduced [B, 2n] from ``x0_red`` after ``n_steps`` steps of
         ``step_implicit()``'s map (and the ``record`` samples as step_implicit() returns them), as a torch.autograd.Function
         whose backward is crb_step_implicit_adjoint -- ``loss.backward()`` reaches whichever of ``x0_red``, ``impulse_amp``
-        [B] and ``held_force`` [B, n] require grad, over the 0.1 ... 1 s horizons the examples simulate
-        (examples/reach_tip_implicit.py).  The forward is the checkpoint pass (it agrees with step_implicit to rounding),
-        whose checkpoints backward reuses.  Leaves ``state``, ``time`` and ``status`` alone.  fp64 ensembles only; once
-        differentiable; no control schedules, no damped variant."""
-        if isinstance(held_force, ControlSchedule):
-            raise NotImplementedError("rollout_implicit: control schedules are not available in the implicit stepper's adjoint")
+        [B], ``held_force`` [B, n] and ``control`` [K, B, n] (held ``control_hold`` implicit steps each, as in
+        step_implicit()) require grad, over the 0.1 ... 1 s horizons the examples simulate
+        (examples/reach_tip_implicit.py, examples/steer_tip_implicit.py): the whole control sequence in one backward sweep.
+        The forward is the checkpoint pass (it agrees with step_implicit to rounding), whose checkpoints backward reuses.
+        Leaves ``state``, ``time`` and ``status`` alone.  fp64 ensembles only; once differentiable; no damped variant."""
         x0 = torch.as_tensor(x0_red, dtype=self.dtype, device=self.device)
         amp = None if impulse_amp is None else torch.as_tensor(impulse_amp, dtype=self.dtype, device=self.device)
+        held_force, sch = self._control(held_force, control, control_hold, n_steps, "rollout_implicit", "implicit steps")
         held = None if held_force is None else torch.as_tensor(held_force, dtype=self.dtype, device=self.device)
+        ctrl, hold = (None, None) if sch is None else sch
         opts = dict(n_steps=int(n_steps), h=float(h), n_iter=int(n_iter), t0=float(t0), duration=float(impulse_duration),
                     index=int(impulse_index), record=record, record_every=int(record_every),
-                    every=self.checkpoint_interval(n_steps, checkpoint_every, implicit=(n_iter, 1)))
-        xT, samples = _ImplicitRollout.apply(self, opts, x0, amp, held)
+                    every=self.checkpoint_interval(n_steps, checkpoint_every, implicit=(n_iter, 1)), hold=hold)
+        xT, samples = _ImplicitRollout.apply(self, opts, x0, amp, held, ctrl)
         return (xT, samples) if record is not None else xT
 
     # ------------------------------------------------------------------ adjoint of the closed loop (crb_feedback_adjoint.h)
@@ -1237,7 +1254,7 @@ class BeamEnsemble:
 
     def step_implicit(self, n_steps: int, h: float, n_iter: int = 2, impulse_amp=None, impulse_duration: float = 0.01,
                       impulse_index: int = -2, held_force=None, t0: Optional[float] = None, record=None,
-                      record_every: int = 1, rho_inf: float = 1.0):
+                      record_every: int = 1, rho_inf: float = 1.0, control=None, control_hold: Optional[int] = None):
         """Advance the resident state by ``n_steps`` steps of size ``h`` of the implicit midpoint rule in one launch
         (crb_step_implicit): the stiff end of the reference's call sites -- the examples integrate 1 s with
         ``solve_ivp(method="LSODA")`` (example_utilities.py:153-159) because explicit steppers are limited to
@@ -1246,13 +1263,32 @@ class BeamEnsemble:
         Displacements converge at second order in h; velocity components of modes with |lambda| h >> 1 are not
         resolved (amplitude kept, phase not).  ``rho_inf`` < 1: the numerically damped member of the family
         (generalised-alpha, crb_step_implicit_damped) -- those modes lose the factor ``rho_inf`` per step instead, as
-        they do under LSODA's BDF formulas; 0 removes them within a step or two, 1 is the midpoint rule."""
+        they do under LSODA's BDF formulas; 0 removes them within a step or two, 1 is the midpoint rule.
+        ``control`` [K, B, n] / ``control_hold`` (or ``held_force=ControlSchedule(control, hold)``): a piecewise-constant control
+        sequence as in ``step``, vector k held for ``control_hold`` implicit steps, switched inside the kernel
+        (crb_step_implicit_sched) -- bitwise the chain of one call per interval with ``held_force=control[k]``.  Every call
+        starts its first step's iteration from 0, so every interval's first step does: a sequence of K equal vectors is the
+        chain of K calls, not bitwise the one held-force call (they differ by the iteration's convergence error).  Not
+        together with ``held_force`` [B, n]; not with ``rho_inf`` < 1 (NotImplementedError)."""
+        held_force, sch = self._control(held_force, control, control_hold, n_steps, "step_implicit", "implicit steps")
+        if sch is not None and float(rho_inf) < 1.0:
+            raise NotImplementedError("step_implicit: the damped variant (rho_inf < 1) has no scheduled form")
         if t0 is not None:
             self.time = float(t0)
         desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index, held_force)
         rec, samples = self._record_desc(record, n_steps, record_every)
         keep.append(samples)
         t_end = C.c_double(0.0)
+        if sch is not None:
+            sd, packed = self._sched_desc(sch)
+            keep.append(packed)
+            with self._on_device():
+                nat.check(self._lib.crb_step_implicit_sched(self.plan.h, self._ptr(self.state), self.time, float(h), int(n_steps),
+                                                            int(n_iter), C.byref(desc), C.byref(sd), self._ref(rec),
+                                                            C.byref(t_end), self._stream()))
+            self._keep = keep
+            self.time = t_end.value
+            return (self.time, samples) if record is not None else self.time
         with self._on_device():
             nat.check(self._lib.crb_step_implicit_damped(self.plan.h, self._ptr(self.state), self.time, float(h), int(n_steps),
                                                          int(n_iter), float(rho_inf), C.byref(desc),
@@ -1823,20 +1859,21 @@ class _Rollout(torch.autograd.Function):
 
 
 class _ImplicitRollout(torch.autograd.Function):
-    """BeamEnsemble.rollout_implicit: forward = crb_step_implicit_checkpoint, backward = crb_step_implicit_adjoint on the saved
-    checkpoints"""
+    """BeamEnsemble.rollout_implicit: forward = crb_step_implicit_checkpoint(_sched), backward =
+    crb_step_implicit_adjoint(_sched) on the saved checkpoints"""
 
     @staticmethod
-    def forward(ctx, ens, opts, x0, amp, held):
+    def forward(ctx, ens, opts, x0, amp, held, ctrl):
         desc, keep = ens._input_desc(None if amp is None else amp.detach(), opts["duration"], opts["index"],
                                      None if held is None else held.detach())
+        sd, packed = ens._sched_desc(None if ctrl is None else (ctrl.detach(), opts["hold"]))
         x = ens.pack_state(x0.detach())
         rec, samples = ens._record_desc(opts["record"], opts["n_steps"], opts["record_every"])
-        ckpt = ens._implicit_checkpoint(x, opts["n_steps"], opts["h"], opts["n_iter"], opts["t0"], desc, opts["every"], rec)
-        ens._keep = keep + [x, samples]
+        ckpt = ens._implicit_checkpoint(x, opts["n_steps"], opts["h"], opts["n_iter"], opts["t0"], desc, opts["every"], rec, sd)
+        ens._keep = keep + [x, samples, packed]
         ctx.ens, ctx.opts = ens, opts
-        ctx.has_amp, ctx.has_held = amp is not None, held is not None
-        ctx.save_for_backward(ckpt, None if amp is None else amp.detach(), None if held is None else held.detach())
+        ctx.has_amp, ctx.has_held, ctx.has_ctrl = amp is not None, held is not None, ctrl is not None
+        ctx.save_for_backward(ckpt, None if amp is None else amp.detach(), None if held is None else held.detach(), packed)
         if samples is None:
             samples = torch.zeros(0, dtype=ens.dtype, device=ens.device)
         if opts["record"] is None:
@@ -1847,19 +1884,21 @@ class _ImplicitRollout(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g_x, g_samples):
         ens, o = ctx.ens, ctx.opts
-        ckpt, amp, held = ctx.saved_tensors
+        ckpt, amp, held, packed = ctx.saved_tensors
         desc, keep = ens._input_desc(amp, o["duration"], o["index"], held)
+        sd = nat.InputSchedule(packed.data_ptr(), int(packed.shape[0]), int(o["hold"])) if ctx.has_ctrl else None
         g_x = torch.zeros((ens.n_beams, 2 * ens.n), dtype=ens.dtype, device=ens.device) if g_x is None else g_x
         lamd = ens._pack_dirs(g_x.to(ens.dtype).reshape(1, ens.n_beams, 2 * ens.n).contiguous(), True)
         rec_bar, cot = ens._record_cotangent(o["record"], o["n_steps"], o["record_every"],
                                              g_samples if o["record"] is not None else None, 1)
         amp_bar, f_bar = ens._implicit_adjoint(ckpt, lamd, o["n_steps"], o["h"], o["n_iter"], o["t0"], desc, o["every"],
-                                               rec_bar, ctx.has_amp)
-        ens._keep += keep + [cot]
+                                               rec_bar, ctx.has_amp, sd)
+        ens._keep += keep + [cot, packed]
         gx0 = ens._unpack_dirs(lamd)[0] if ctx.needs_input_grad[2] else None
         gamp = amp_bar[0] if (ctx.has_amp and ctx.needs_input_grad[3]) else None
         gheld = ens._unpack_force_dirs(f_bar)[0] if (ctx.has_held and ctx.needs_input_grad[4]) else None
-        return None, None, gx0, gamp, gheld
+        gctrl = ens._unpack_sched_dirs(f_bar)[0] if (ctx.has_ctrl and ctx.needs_input_grad[5]) else None
+        return None, None, gx0, gamp, gheld, gctrl
 
 
 class _FeedbackRollout(torch.autograd.Function):

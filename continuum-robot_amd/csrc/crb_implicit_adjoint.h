@@ -98,7 +98,12 @@ __device__ __forceinline__ void imp_k0t(const AdjLds<T>& L, const Topo& tp, cons
     for (int c = 0; c < 3; ++c) out[c] = orr[c] + (has_r ? L.r[(3 + c) * NT + tr] : T(0));
 }
 
-template <typename T, int MODE>
+// SCHED: a control schedule (crb_input_schedule; KParams sched_*, AdjParams fbar_cot_stride as in crb_adj_kernel) -- a
+// compile-time axis, so that the unscheduled instances stay the code they were.  A scheduled call is the chain of one call per
+// interval: at an interval's first step the forward modes reload uh and reset the starting iterate to 0 BEFORE that step's
+// checkpoint / start-state store, and the sweep drops cbar there, stores the interval's force cotangent and takes up the
+// record of the interval below.
+template <typename T, int MODE, bool SCHED = false>
 __global__ void __launch_bounds__(ADJ_MAX_NT) crb_imp_adj_kernel(const KParams<T> p, const AdjParams<T> aq, const ImpAdjParams<T> iq) {
     static_assert(sizeof(T) == 8, "the adjoint kernels are fp64");
     const AdjLds<T> L = carve_adjoint_lds<T>(blockDim.x);
@@ -120,6 +125,7 @@ __global__ void __launch_bounds__(ADJ_MAX_NT) crb_imp_adj_kernel(const KParams<T
     const size_t state_sz = size_t(p.B) * 2 * plane, force_sz = size_t(p.B) * plane;
     const size_t uoff = size_t(tp.beam) * plane + node * 4;
     const size_t loff = d * state_sz + xoff, luoff = d * force_sz + uoff;
+    const size_t fboff = SCHED ? d * aq.fbar_cot_stride + uoff : luoff;   // f_bar ([n_cot][n_intervals][B][n_node][4] with a schedule)
     const bool zero_node0 = p.off == 1 && tp.j == 0;
     T uh[3] = {T(0), T(0), T(0)};
     T amp = T(0);
@@ -151,7 +157,23 @@ __global__ void __launch_bounds__(ADJ_MAX_NT) crb_imp_adj_kernel(const KParams<T
             }
         }
         double tc = p.t0;
+        // SCHED: steps until the next interval's force takes uh's place (the host hands every launch the interval and the phase
+        // it starts in), and this node's record of the current interval
+        int sched_left = SCHED ? p.sched_first : -1;
+        const T* sched_u = p.u_held + uoff;
         for (int step = 0; step < p.n_steps; ++step) {
+            if constexpr (SCHED) {
+                if (sched_left == 0) {   // (wave-uniform)
+                    sched_left = p.sched_hold;
+                    sched_u += p.sched_stride;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        if (valid) uh[c] = sched_u[c];
+                        am[c] = T(0);   // the interval starts as a call does: a^0 = 0 (what is stored below)
+                    }
+                }
+                --sched_left;
+            }
             if (MODE == IADJ_SEG) {   // the step's start state and clock
                 if (valid) {
                     T* const so = aq.states + size_t(step) * state_sz + xoff;
@@ -232,14 +254,14 @@ __global__ void __launch_bounds__(ADJ_MAX_NT) crb_imp_adj_kernel(const KParams<T
         for (int c = 0; c < 3; ++c) {
             lam[c] = aq.lam[loff + c] * sc.mask[c];
             lam[3 + c] = aq.lam[loff + plane + c] * sc.mask[c];
-            if (aq.f_bar) fb[c] = aq.f_bar[luoff + c];
+            if (aq.f_bar) fb[c] = aq.f_bar[fboff + c];
             if (iq.carry_in) cb[c] = iq.carry[luoff + c] * sc.mask[c];
         }
         if (aq.amp_bar && imp_here) ab = aq.amp_bar[d * size_t(p.B) + tp.beam];
     }
     // this lane's addresses of the sweep's buffers, formed once and held in vector registers (crb_adj_kernel)
     T* lam_p = aq.lam + loff;
-    T* fb_p = (aq.f_bar && valid) ? aq.f_bar + luoff : nullptr;
+    T* fb_p = (aq.f_bar && valid) ? aq.f_bar + fboff : nullptr;
     T* ab_p = (aq.amp_bar && imp_here) ? aq.amp_bar + d * size_t(p.B) + tp.beam : nullptr;
     T* cb_p = iq.carry + luoff;
     const T* it_p = iq.iters + uoff;
@@ -318,12 +340,30 @@ __global__ void __launch_bounds__(ADJ_MAX_NT) crb_imp_adj_kernel(const KParams<T
                 ab = ab + ui;
             }
         }
+        bool first = kstep == 0;   // (step 0 of the call starts from the constant a^0 = 0 ...
+        if constexpr (SCHED) {     //  ... and so does the first step of every interval)
+            int hold = p.sched_hold;
+            asm volatile("" : "+s"(hold));
+            first = kstep % hold == 0;
+        }
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            cb[c] = kstep == 0 ? T(0) : abar[c];   // (step 0 of the call starts from the constant a^0 = 0)
+            cb[c] = first ? T(0) : abar[c];
             const T lq = lam[c];
             lam[c] = lq + qpb[c];
             lam[3 + c] = (h * lq + lam[3 + c]) + (hh * qpb[c] + vpb[c]);
+        }
+        // SCHED: the step just swept was its interval's first, and the launch goes on below it -- this interval's sum is
+        // complete: store it, move the lane address down one interval and take up the record there (accumulated: a later
+        // segment may have left a partial sum), as crb_adj_kernel does
+        if constexpr (SCHED) {
+            if (i > 0 && first && fb_p) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) fb_p[c] = fb[c];
+                fb_p -= p.sched_stride;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) fb[c] = fb_p[c];
+            }
         }
     }
     if (!valid) return;

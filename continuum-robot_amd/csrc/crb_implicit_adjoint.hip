@@ -7,8 +7,11 @@ template <int MODE>
 hipError_t imp_adj_impl(const KParams<double>& k, const AdjParams<double>& q, const ImpAdjParams<double>& iq, int groups, int n_cot,
                         int threads, hipStream_t st) {
     if (threads > ADJ_MAX_NT || n_cot < 1 || n_cot > 65535 || iq.n_iter < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((crb_imp_adj_kernel<double, MODE>), dim3(groups, n_cot), dim3(threads), adjoint_lds_bytes<double>(threads), st,
-                       k, q, iq);
+    const dim3 grid(groups, n_cot), block(threads);
+    const size_t smem = adjoint_lds_bytes<double>(threads);
+    // a control schedule (k.sched_*) runs the SCHED instances; calls without one run the instances they always did
+    if (k.sched_stride) hipLaunchKernelGGL((crb_imp_adj_kernel<double, MODE, true>), grid, block, smem, st, k, q, iq);
+    else hipLaunchKernelGGL((crb_imp_adj_kernel<double, MODE, false>), grid, block, smem, st, k, q, iq);
     return hipGetLastError();
 }
 }  // namespace

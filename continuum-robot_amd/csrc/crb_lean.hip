@@ -180,9 +180,9 @@ hipError_t launch_lean(const KParams<T>& k, int n_beams, int levels, int lognw, 
 
 #if (CRB_LEAN_PART == 0 || CRB_LEAN_PART == 3) && !defined(CRB_FAST_BUILD)
 namespace {
-template <int LV, int LOGNW, bool GRAV, int EM, bool PACK>
+template <int LV, int LOGNW, bool GRAV, int EM, bool PACK, bool SCHED>
 hipError_t one_implicit(const KParams<T>& k, const StiffParams<T>& q, int groups, hipStream_t st) {
-    constexpr auto kernel = crb_implicit_lean_kernel<T, LV, LOGNW, GRAV, EM, PACK>;
+    constexpr auto kernel = crb_implicit_lean_kernel<T, LV, LOGNW, GRAV, EM, PACK, SCHED>;
     const size_t smem = implicit_lean_lds_bytes<T>(64 << LOGNW, LOGNW);
     if (hipError_t e = lds_opt_in(kernel, smem)) return e;
     hipLaunchKernelGGL(kernel, dim3(groups), dim3(64 << LOGNW), smem, st, k, q);
@@ -194,7 +194,11 @@ hipError_t launch_implicit_lean(const KParams<T>& k, const StiffParams<T>& q, in
     return with_int<0, MAX_LV>(levels, [&](auto lv) { return with_int<0, 3>(lognw, [&](auto nw) { return with_bool(k.G > 1, [&](auto pack) {
         if constexpr (pack ? nw == 0 && lean_implicit_pack_built(F64, lv) : lean_implicit_built(F64, lv, nw))
             return with_bool(grav, [&](auto g) { return with_elem_mode(elem_mode, [&](auto e) {
-                return one_implicit<lv, nw, g, e, pack>(k, q, groups, st); }); });
+                if (!k.sched_stride) return one_implicit<lv, nw, g, e, pack, false>(k, q, groups, st);
+                // a control schedule (k.sched_*): its own instantiation, for the shapes lean_implicit_sched_built names
+                if constexpr (pack ? lean_implicit_pack_sched_built(F64, lv) : lean_implicit_sched_built(F64, lv, nw))
+                    return one_implicit<lv, nw, g, e, pack, true>(k, q, groups, st);
+                else return hipErrorInvalidValue; }); });
         else return hipErrorInvalidValue;
     }); }); });
 }

@@ -31,6 +31,12 @@ constexpr bool lean_rk45_built(bool f64, int levels, int lognw) { return lognw >
 // .. the full count of that width (33 .. 64 / 65 .. 128 / 129 .. 256 slots); several beams per wave at 3 .. 5 levels
 constexpr bool lean_implicit_built(bool f64, int levels, int lognw) { return f64 && lognw >= 0 && lognw <= 2 && levels >= 5 && levels <= 6 + lognw; }
 constexpr bool lean_implicit_pack_built(bool f64, int levels) { return f64 && levels >= 3 && levels <= 5; }
+// ... and with a control schedule (KParams sched_*): the SCHED instantiation of every shape the family builds and of no
+// other -- a scheduled call must run the arithmetic of the chain of held-force calls it stands for, so it runs the lean
+// kernel exactly where they do.  (Shapes whose SCHED instance would spill at two waves per SIMD are built at one:
+// implicit_lean_sched_minw in crb_stiff.h.)
+constexpr bool lean_implicit_sched_built(bool f64, int levels, int lognw) { return lean_implicit_built(f64, levels, lognw); }
+constexpr bool lean_implicit_pack_sched_built(bool f64, int levels) { return lean_implicit_pack_built(f64, levels); }
 
 // ---- The launchers: hipErrorInvalidValue for a shape that is not built.
 // launches crb_step_lean_kernel<T, levels, lognw, grav, elem_mode> on `n_beams` workgroups (lean_step_built)

@@ -41,8 +41,11 @@ struct StiffParams {
     double kappa, cv, c_qv, c_qa, c_va, tf_frac, alpha_m, inv1m, c_q0, c_q1, c_v0, c_v1;
 };
 
-template <typename T, int LV, int MAXT, int MINW, bool DAMPED = false>
+// SCHED: a control schedule (crb_input_schedule, KParams sched_*) -- at the top of a step that is an interval's first, uh is
+// reloaded from that interval's record and the starting iterate is reset to 0: the call is the chain of one call per interval.
+template <typename T, int LV, int MAXT, int MINW, bool DAMPED = false, bool SCHED = false>
 __global__ void __launch_bounds__(MAXT, MINW) crb_implicit_kernel(const KParams<T> p, const StiffParams<T> q) {
+    static_assert(!(DAMPED && SCHED), "the damped variant has no scheduled form");
     const int NT = blockDim.x;
     const Lds<T> lds = carve_lds<T>(NT);
     Topo tp;
@@ -119,7 +122,22 @@ __global__ void __launch_bounds__(MAXT, MINW) crb_implicit_kernel(const KParams<
 
     const T h = T(q.h), hh = DAMPED ? T(q.cv) : T(0.5 * q.h), alpha = DAMPED ? T(q.kappa) : T(0.25 * q.h * q.h), alpha2 = T(0.5 * q.h * q.h);
     double tc = p.t0;
+    // SCHED: steps until the next interval's force takes uh's place, and this node's record of the current interval
+    int sched_left = SCHED ? p.sched_first : -1;
+    const T* sched_u = p.u_held + aoff;
     for (int step = 0; step < p.n_steps; ++step) {
+        if constexpr (SCHED) {
+            if (sched_left == 0) {   // (wave-uniform; three loads per lane at an interval's first step)
+                sched_left = p.sched_hold;
+                sched_u += p.sched_stride;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    if (valid) uh[c] = sched_u[c];
+                    am[c] = T(0);   // the interval starts as a call does: a^0 = 0
+                }
+            }
+            --sched_left;
+        }
         const double tm = __dadd_rn(tc, (DAMPED ? q.tf_frac : 0.5) * q.h), t1 = __dadd_rn(tc, q.h);
         const T av = (tm < p.duration) ? amp : T(0);
         T uadd[3], qp[3], vp[3];
@@ -194,6 +212,15 @@ __global__ void __launch_bounds__(MAXT, MINW) crb_implicit_kernel(const KParams<
 // 7 / 8 levels of long beams take the register file whole
 __host__ __device__ constexpr int implicit_lean_minw(int lv, bool grav, int lognw = 1) {
     return ((lv <= 5 || (lv == 6 && !grav)) && lean_minw_f64(lv, lognw, grav) == 2) ? 2 : 1;
+}
+// ... and with a control schedule (SCHED).  The SCHED instance of a shape takes the registers and the scratch of its
+// unscheduled instance (make resource-usage), and some two-wave shapes of the family spill (12 .. 100 bytes of scratch per
+// lane).  No SCHED instance is built with scratch: those shapes run theirs at one wave per SIMD; the arithmetic of a step
+// is the same.
+__host__ __device__ constexpr int implicit_lean_sched_minw(int lv, bool grav, int lognw, bool pack) {
+    const bool spills = pack ? ((lv == 4 && grav) || (lv == 5 && !grav))
+                             : ((lv == 6 && !grav) || (lognw >= 1 && lv == 5 && grav));
+    return spills ? 1 : implicit_lean_minw(lv, grav, lognw);
 }
 template <typename T>
 __host__ __device__ constexpr size_t implicit_lean_lds_bytes(int NT, int lognw) {
@@ -288,8 +315,12 @@ __device__ __forceinline__ void lean_implicit_iterate(const ElemCoef<T>& ec, con
 // PACK (one-wave form only): beams of fewer than 64 slots, G = 64 / S of them per wave (lane = g S + j), as in the packed
 // explicit stepper: every exchange stays a lane shift, and what a shift drags across a beam boundary is replaced by 0
 // with a select (a diverged wave-mate's Inf / NaN must not reach its neighbours through a 0 * NaN).
-template <typename T, int LV, int LOGNW, bool GRAV, int EM, bool PACK = false>
-__global__ void __launch_bounds__(64 << LOGNW, implicit_lean_minw(LV, GRAV, LOGNW)) crb_implicit_lean_kernel(const KParams<T> p, const StiffParams<T> q) {
+// SCHED: a control schedule (KParams sched_*), as in crb_implicit_kernel.  Only the countdown and the interval index stay
+// live across a step: what the reload needs of the launch parameters is re-read through a laundered kernarg pointer inside
+// the (wave-uniform) branch, as crb_step_lean_kernel<..., HELD> does.
+template <typename T, int LV, int LOGNW, bool GRAV, int EM, bool PACK = false, bool SCHED = false>
+__global__ void __launch_bounds__(64 << LOGNW, SCHED ? implicit_lean_sched_minw(LV, GRAV, LOGNW, PACK) : implicit_lean_minw(LV, GRAV, LOGNW))
+crb_implicit_lean_kernel(const KParams<T> p, const StiffParams<T> q) {
     static_assert(LV >= 1, "needs at least one reduction level");
     static_assert(!PACK || LOGNW == 0, "packed beams live inside one wave");
     constexpr int NW = 1 << LOGNW, NT = 64 << LOGNW, NULLT = NT;
@@ -373,7 +404,34 @@ __global__ void __launch_bounds__(64 << LOGNW, implicit_lean_minw(LV, GRAV, LOGN
             if (GRAV && p.gvec) { gx = p.gvec[2 * size_t(beam)]; gy = p.gvec[2 * size_t(beam) + 1]; }
         }
         double tc = p.t0;
+        int sched_left = SCHED ? p.sched_first : -1, sched_k = 0;
         for (int step = 0; step < p.n_steps; ++step) {
+            if constexpr (SCHED) {
+                if (sched_left == 0) {   // (wave-uniform)
+#if defined(__HIP_DEVICE_COMPILE__)
+                    typedef const __attribute__((address_space(4))) KParams<T>* KP;
+                    KP kq = (KP)__builtin_amdgcn_kernarg_segment_ptr();   // (the explicit arguments start at offset 0: p)
+                    asm volatile("" : "+s"(kq));
+                    const KParams<T>& f = *(const KParams<T>*)(kq);
+#else
+                    const KParams<T>& f = p;
+#endif
+                    sched_left = f.sched_hold;
+                    ++sched_k;
+                    if (valid) {   // the record of the beam this lane carries now (its node from j: nothing more stays live)
+                        const T* const u = f.u_held + size_t(sched_k) * f.sched_stride + (size_t(beam) * size_t(f.n_node) + size_t(j + f.off)) * 4;
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) uh[c] = u[c];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) asm volatile("" : "+v"(uh[c]));
+#endif
+                    }
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) am[c] = T(0);   // the interval starts as a call does: a^0 = 0
+                }
+                --sched_left;
+            }
             const double tm = __dadd_rn(tc, 0.5 * q.h), t1 = __dadd_rn(tc, q.h);
             const T av = (tm < p.duration) ? amp : T(0);
             T uadd[3], qp[3];

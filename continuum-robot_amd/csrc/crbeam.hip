@@ -1090,6 +1090,13 @@ bool lean_implicit_ok(const crb_plan* p) {
                                                : implicit_pack_shape(p) && lean_implicit_pack_built(f64(p), p->stiff_levels);
     return built && lean_grav_ok(p) && lean_implicit_enabled();
 }
+// ... with a control schedule: the SCHED instances (lean_implicit_sched_built / lean_implicit_pack_sched_built: the same
+// shapes, so that a scheduled call runs the kernel family of the chain of held-force calls it stands for)
+bool lean_implicit_sched_ok(const crb_plan* p) {
+    if (!lean_implicit_ok(p)) return false;
+    return implicit_group_shape(p) ? lean_implicit_sched_built(f64(p), p->stiff_levels, p->lognw)
+                                   : lean_implicit_pack_sched_built(f64(p), p->stiff_levels);
+}
 // crb_solve_controlled: one beam per workgroup; the closed loop (fb) at the levels of M, the implicit scheme at all levels of A
 bool lean_controlled_ok(const crb_plan* p, bool fb) {
     const bool shape = p->NT == (64 << p->lognw) && lean_grav_ok(p) && !env_set("CRB_DISABLE_LEAN") &&
@@ -1535,7 +1542,11 @@ int launch_implicit_lv(const crb_plan* p, const KParams<T>& k, const StiffParams
     // does not fill the GPU at one wave per SIMD keeps the whole file per wave (ONE 10-element beam: 3.6 instead of 4.3 us
     // per step).  The full tables of long beams take the file whole.
     const long waves = long(grid.x) * ((p->NT + 63) / 64);
-    if (LV <= 5 && waves > 1024) hipLaunchKernelGGL((crb_implicit_kernel<T, LV, 256, (LV <= 5 ? 2 : 1)>), grid, block, smem, st, k, q);
+    if (k.sched_stride) {   // a control schedule: the SCHED instances; the two-wave form up to 2 levels (beyond, it would spill)
+        if (LV <= 2 && waves > 1024)
+            hipLaunchKernelGGL((crb_implicit_kernel<T, LV, 256, (LV <= 2 ? 2 : 1), false, true>), grid, block, smem, st, k, q);
+        else hipLaunchKernelGGL((crb_implicit_kernel<T, LV, 256, 1, false, true>), grid, block, smem, st, k, q);
+    } else if (LV <= 5 && waves > 1024) hipLaunchKernelGGL((crb_implicit_kernel<T, LV, 256, (LV <= 5 ? 2 : 1)>), grid, block, smem, st, k, q);
     else hipLaunchKernelGGL((crb_implicit_kernel<T, LV, 256, 1>), grid, block, smem, st, k, q);
     HIP_TRY(hipGetLastError());
     return CRB_OK;
@@ -1545,11 +1556,13 @@ int launch_implicit(const crb_plan* p, const KParams<T>& k, const StiffParams<T>
 #ifdef CRB_FAST_BUILD
     return fail(CRB_EUNSUPPORTED, "CRB_FAST_BUILD: implicit stepper not built");
 #else
-    if (lean_implicit_ok(p)) {
+    if (k.sched_stride ? lean_implicit_sched_ok(p) : lean_implicit_ok(p)) {
         // one wave per SIMD (the tables of A fill the register file): 256 CUs x 4 / waves per beam workgroups are resident
         const bool grav = grav_on(p);
         const bool shared = shared_tables(*p);   // (the tables of A are per beam exactly where the plan's own are)
-        int resident = 256 * 4 / (1 << p->lognw) * implicit_lean_minw(p->stiff_levels, grav, p->lognw);   // (waves per SIMD: crb_stiff.h)
+        const int minw = k.sched_stride ? implicit_lean_sched_minw(p->stiff_levels, grav, p->lognw, p->G > 1)
+                                        : implicit_lean_minw(p->stiff_levels, grav, p->lognw);   // (waves per SIMD: crb_stiff.h)
+        int resident = 256 * 4 / (1 << p->lognw) * minw;
         if (const int cap = int(env_int("CRB_LEAN_MAX_GROUPS", 0)); cap > 0) resident = cap;   // (tests)
         const int groups = (p->B + p->G - 1) / p->G;
         HIP_TRY(crb::launch_implicit_lean(k, q, shared ? walk_grid(groups, resident) : groups, p->stiff_levels, p->lognw, grav,
@@ -1583,7 +1596,7 @@ int launch_implicit_damped(const crb_plan* p, const KParams<T>& k, const StiffPa
 
 template <typename T>
 int step_implicit_impl(const crb_plan* p, void* x, double t0, double h, int n_steps, int n_iter, double rho, const Forcing& f,
-                       const Recording& rec, hipStream_t st) {
+                       const Schedule& sc, const Recording& rec, hipStream_t st) {
     const bool damped = rho < 1.0;
     // generalised-alpha coefficients (crb_stiff.h: StiffParams); rho = 1 is the midpoint rule with kappa = h^2 / 4
     const double am_ = (2.0 * rho - 1.0) / (rho + 1.0), af_ = rho / (rho + 1.0);
@@ -1593,6 +1606,7 @@ int step_implicit_impl(const crb_plan* p, void* x, double t0, double h, int n_st
     KParams<T> k = base_params<T>(p);
     k.x = static_cast<T*>(x);
     set_io(k, f, &rec);
+    set_sched(p, k, sc, 0);   // (never with the damped variant)
     k.t0 = t0; k.dt = h; k.n_steps = n_steps;
     arm_status(p, k, n_steps);
     StiffParams<T> q;
@@ -1627,7 +1641,34 @@ int step_implicit_impl(const crb_plan* p, void* x, double t0, double h, int n_st
 
 extern "C" int crb_step_implicit(const crb_plan* p, void* x, double t0, double h, int n_steps, int n_iter,
                                  const crb_input_desc* in, const crb_record_desc* rec, double* t_end, void* stream) {
-    return crb_step_implicit_damped(p, x, t0, h, n_steps, n_iter, 1.0, in, rec, t_end, stream);
+    return crb_step_implicit_sched(p, x, t0, h, n_steps, n_iter, in, nullptr, rec, t_end, stream);
+}
+
+extern "C" int crb_step_implicit_sched(const crb_plan* p, void* x, double t0, double h, int n_steps, int n_iter,
+                                       const crb_input_desc* in, const crb_input_schedule* sched, const crb_record_desc* rec,
+                                       double* t_end, void* stream) {
+    if (!sched) return crb_step_implicit_damped(p, x, t0, h, n_steps, n_iter, 1.0, in, rec, t_end, stream);
+    // with a schedule every refusal comes before the device is touched: CRB_EINVAL (the stepper's own cases, then the
+    // schedule's), CRB_EUNSUPPORTED, CRB_ENODEV
+    const char* who = "crb_step_implicit_sched";
+    if (!p) return fail(CRB_EINVAL, std::string(who) + ": null plan");
+    if (!x) return fail(CRB_EINVAL, std::string(who) + ": null pointer");
+    if (n_steps < 0) return fail(CRB_EINVAL, std::string(who) + ": n_steps must be >= 0");
+    if (!(h > 0)) return fail(CRB_EINVAL, std::string(who) + ": h must be positive");
+    if (n_iter < 1) return fail(CRB_EINVAL, std::string(who) + ": n_iter must be >= 1");
+    Recording r;
+    if (int rc = decode_record(p, rec, n_steps, true, who, &r)) return rc;
+    Forcing f;
+    if (int rc = decode_input(p, in, who, &f)) return rc;
+    Schedule sc;
+    if (int rc = decode_schedule(sched, in, n_steps, who, &sc)) return rc;
+    if (p->dtype != CRB_F64)
+        return fail(CRB_EUNSUPPORTED, std::string(who) + ": the implicit stepper needs an fp64 plan (the iteration matrix is too ill-conditioned for fp32)");
+    if (p->NT > 256) return fail(CRB_EUNSUPPORTED, std::string(who) + ": beams of more than 256 thread-carried nodes are not supported");
+    if (int rc = need_device(p, who)) return rc;
+    if (t_end) *t_end = clock_after(t0, h, n_steps);
+    if (n_steps == 0) return CRB_OK;
+    return step_implicit_impl<double>(p, x, t0, h, n_steps, n_iter, 1.0, f, sc, r, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int crb_step_implicit_damped(const crb_plan* p, void* x, double t0, double h, int n_steps, int n_iter, double rho_inf,
@@ -1646,7 +1687,7 @@ extern "C" int crb_step_implicit_damped(const crb_plan* p, void* x, double t0, d
     if (int rc = decode_input(p, in, "crb_step_implicit", &f)) return rc;
     if (t_end) *t_end = clock_after(t0, h, n_steps);
     if (n_steps == 0) return CRB_OK;
-    return step_implicit_impl<double>(p, x, t0, h, n_steps, n_iter, rho_inf, f, r, static_cast<hipStream_t>(stream));
+    return step_implicit_impl<double>(p, x, t0, h, n_steps, n_iter, rho_inf, f, Schedule(), r, static_cast<hipStream_t>(stream));
 }
 
 // ------------------------------------------------------------------ step-size control in the kernel (crb_ctrl.h)
@@ -2800,7 +2841,13 @@ extern "C" size_t crb_implicit_adjoint_work_bytes(const crb_plan* p, int every, 
 extern "C" int crb_step_implicit_checkpoint(const crb_plan* p, void* x, double t0, double h, int n_steps, int n_iter, int every,
                                             const crb_input_desc* in, const crb_record_desc* rec, void* ckpt, double* t_end,
                                             void* stream) {
-    const std::string who("crb_step_implicit_checkpoint");
+    return crb_step_implicit_checkpoint_sched(p, x, t0, h, n_steps, n_iter, every, in, nullptr, rec, ckpt, t_end, stream);
+}
+
+extern "C" int crb_step_implicit_checkpoint_sched(const crb_plan* p, void* x, double t0, double h, int n_steps, int n_iter,
+                                                  int every, const crb_input_desc* in, const crb_input_schedule* sched,
+                                                  const crb_record_desc* rec, void* ckpt, double* t_end, void* stream) {
+    const std::string who(sched ? "crb_step_implicit_checkpoint_sched" : "crb_step_implicit_checkpoint");
     if (!p) return fail(CRB_EINVAL, who + ": null plan");
     if (!x || !ckpt) return fail(CRB_EINVAL, who + ": null state or checkpoint buffer");
     if (x == ckpt) return fail(CRB_EINVAL, who + ": the checkpoint buffer must not alias the state");
@@ -2810,6 +2857,8 @@ extern "C" int crb_step_implicit_checkpoint(const crb_plan* p, void* x, double t
     Forcing f;
     if (int rc = decode_input(p, in, who.c_str(), &f)) return rc;
     if (r.out && (r.out == x || r.out == ckpt)) return fail(CRB_EINVAL, who + ": the record must not alias the state or the checkpoints");
+    Schedule sc;
+    if (int rc = decode_schedule(sched, in, n_steps, who.c_str(), &sc)) return rc;
     if (int rc = imp_adjoint_plan_checks(p, who)) return rc;
     if (int rc = need_device(p, who.c_str())) return rc;
     if (t_end) *t_end = clock_after(t0, h, n_steps);
@@ -2820,6 +2869,7 @@ extern "C" int crb_step_implicit_checkpoint(const crb_plan* p, void* x, double t
     if (int rc = imp_adjoint_params(p, h, st, &k)) return rc;
     k.x = static_cast<double*>(x);
     set_io(k, f, &r);
+    set_sched(p, k, sc, 0);
     k.t0 = t0; k.n_steps = n_steps;
     AdjParams<double> q = adj_params(p);
     q.states = static_cast<double*>(ckpt);
@@ -2835,12 +2885,20 @@ extern "C" int crb_step_implicit_checkpoint(const crb_plan* p, void* x, double t
 extern "C" int crb_step_implicit_adjoint(const crb_plan* p, const void* ckpt, void* lam, int n_cot, double t0, double h, int n_steps,
                                          int n_iter, int every, const crb_input_desc* in, const crb_record_desc* rec_bar,
                                          const crb_input_cotangent* grad, void* work, void* stream) {
-    const std::string who("crb_step_implicit_adjoint");
+    return crb_step_implicit_adjoint_sched(p, ckpt, lam, n_cot, t0, h, n_steps, n_iter, every, in, rec_bar, grad, nullptr, nullptr,
+                                           work, stream);
+}
+
+extern "C" int crb_step_implicit_adjoint_sched(const crb_plan* p, const void* ckpt, void* lam, int n_cot, double t0, double h,
+                                               int n_steps, int n_iter, int every, const crb_input_desc* in,
+                                               const crb_record_desc* rec_bar, const crb_input_cotangent* grad,
+                                               const crb_input_schedule* sched, void* sched_bar, void* work, void* stream) {
+    const std::string who(sched ? "crb_step_implicit_adjoint_sched" : "crb_step_implicit_adjoint");
     if (!p) return fail(CRB_EINVAL, who + ": null plan");
     if (!ckpt || !lam) return fail(CRB_EINVAL, who + ": null checkpoint buffer or cotangent");
     if (!work) return fail(CRB_EINVAL, who + ": null work buffer (crb_implicit_adjoint_work_bytes)");
     void* const amp_bar = grad ? grad->amp_bar : nullptr;
-    void* const f_bar = grad ? grad->f_held_bar : nullptr;
+    void* f_bar = grad ? grad->f_held_bar : nullptr;
     const void* const rec_out = rec_bar ? rec_bar->out : nullptr;
     const void* const held = in ? in->f_held : nullptr;
     const void* bufs[6] = {ckpt, work, amp_bar, f_bar, rec_out, held};
@@ -2856,6 +2914,14 @@ extern "C" int crb_step_implicit_adjoint(const crb_plan* p, const void* ckpt, vo
     if (int rc = decode_input(p, in, who.c_str(), &f)) return rc;
     if (amp_bar && !f.impulse)
         return fail(CRB_EINVAL, who + ": amp_bar needs an impulse input (its amplitude is what it differentiates)");
+    Schedule sc;
+    if (int rc = decode_schedule(sched, in, n_steps, who.c_str(), &sc)) return rc;
+    if (sc.f && f_bar)
+        return fail(CRB_EINVAL, who + ": a schedule and grad->f_held_bar are given together (sched_bar takes its place)");
+    if (sched_bar && !sc.f) return fail(CRB_EINVAL, who + ": sched_bar needs a schedule (sched is null)");
+    if (sched_bar && (sched_bar == lam || sched_bar == work || sched_bar == ckpt || sched_bar == sc.f || sched_bar == amp_bar))
+        return fail(CRB_EINVAL, who + ": sched_bar must not alias lam, the work buffer, the checkpoints, f_sched or amp_bar");
+    if (sc.f) f_bar = sched_bar;   // (one accumulator in the sweep: the interval's record)
     if (int rc = imp_adjoint_plan_checks(p, who)) return rc;
     if (int rc = need_device(p, who.c_str())) return rc;
     if (n_steps == 0) return CRB_OK;
@@ -2877,6 +2943,7 @@ extern "C" int crb_step_implicit_adjoint(const crb_plan* p, const void* ckpt, vo
         KParams<double> k = base;
         k.t0 = clock_after(t0, h, k0);   // (the checkpoint pass's clock at the segment start: the same additions)
         k.n_steps = n;
+        set_sched(p, k, sc, k0);   // (the recompute starts mid-rollout: its interval and phase)
         // 1. the segment's step data from its checkpoint
         AdjParams<double> q = adj_params(p);
         q.states = wstates;
@@ -2895,6 +2962,10 @@ extern "C" int crb_step_implicit_adjoint(const crb_plan* p, const void* ckpt, vo
         b.lam = static_cast<double*>(lam);
         b.amp_bar = static_cast<double*>(amp_bar);
         b.f_bar = static_cast<double*>(f_bar);
+        if (sc.f) {   // the sweep starts in the interval of the segment's last step and walks down from there
+            if (f_bar) b.f_bar += size_t((k0 + n - 1) / sc.hold) * sched_interval_elems(p);
+            b.fbar_cot_stride = size_t(sc.K) * sched_interval_elems(p);
+        }
         b.step0 = k0;
         ImpAdjParams<double> ib;
         std::memset(&ib, 0, sizeof(ib));

@@ -582,7 +582,7 @@ int crb_step_rk4_rec(const crb_plan* plan, void* x, double t0, double dt, int n_
 typedef struct crb_input_schedule {
     const void* f_sched;   /* device [n_intervals][B][n_node][4], plan dtype */
     int32_t n_intervals;   /* K >= 1 */
-    int32_t hold;          /* RK4 steps per interval, >= 1 */
+    int32_t hold;          /* steps per interval, >= 1 (RK4 steps; implicit steps in the crb_step_implicit*_sched calls) */
 } crb_input_schedule;
 
 /* The RK4 rollout family with a control schedule: each call is its counterpart above (the same arguments, clock, impulse
@@ -649,14 +649,49 @@ int crb_step_rk4_adjoint_params_sched(const crb_plan* plan, const void* ckpt, vo
  * plan or buffer, aliasing buffers, n_cot outside 1 ... 65535, n_steps < 0, every < 1, n_iter outside 1 ... 16, h <= 0, a bad
  * input or record description, amp_bar without an impulse input; CRB_EUNSUPPORTED for fp32 plans and beams of more than 256
  * thread-carried nodes; CRB_ENODEV for host-only plans.  *t_end is written only by a call that is not refused.
- * Not covered: the damped variant (rho_inf < 1), control schedules, the closed loop, and parameter gradients (E and I enter A
- * and K0, so with a fixed iteration count the dependence is not the linear sum crb_step_rk4_adjoint_params computes). */
+ * Not covered: the damped variant (rho_inf < 1), the closed loop, and parameter gradients (E and I enter A and K0, so with a
+ * fixed iteration count the dependence is not the linear sum crb_step_rk4_adjoint_params computes).  Control schedules: the
+ * *_sched calls below. */
 size_t crb_implicit_adjoint_work_bytes(const crb_plan* plan, int every, int n_iter, int n_cot);
 int crb_step_implicit_checkpoint(const crb_plan* plan, void* x, double t0, double h, int n_steps, int n_iter, int every,
                                  const crb_input_desc* input, const crb_record_desc* rec, void* ckpt, double* t_end, void* stream);
 int crb_step_implicit_adjoint(const crb_plan* plan, const void* ckpt, void* lam, int n_cot, double t0, double h, int n_steps,
                               int n_iter, int every, const crb_input_desc* input, const crb_record_desc* rec_bar,
                               const crb_input_cotangent* grad, void* work, void* stream);
+
+/* ---- The implicit family with a control schedule (crb_input_schedule; `hold` counts implicit steps: step i of the call
+ * applies vector i / hold at its midpoint, on top of the impulse; n_steps <= n_intervals * hold, the last interval may be cut
+ * short).  Each call is its counterpart above -- the same arguments, clock, impulse window, recording and status -- and, with
+ * sched == NULL (and sched_bar == NULL), exactly that call.  The schedule is switched inside the kernels: one launch (one
+ * launch pair per checkpoint segment for the adjoint), whatever n_intervals.
+ * A scheduled call IS the chain of one call per interval with f_held = that interval's vector, bitwise.  crb_step_implicit
+ * starts the first step of a call from the iterate a^0 = 0, so the first step of EVERY interval starts its modified-Newton
+ * iteration from a^0 = 0, and the adjoint drops the carried cotangent of the starting iterate there, as it does at step 0 of a
+ * call.  Consequence: a schedule of K equal vectors is the chain of K calls, not bitwise the one call with that f_held; the
+ * two differ by the size of the iteration's convergence error (n_iter = 2: DESIGN.md section 10 has the measured figure).
+ *   crb_step_implicit_sched             crb_step_implicit (the damped variant has no scheduled form)
+ *   crb_step_implicit_checkpoint_sched  crb_step_implicit_checkpoint; the checkpoint layout is unchanged, and the `a` plane of
+ *                                       a checkpoint taken at an interval's first step holds zeros
+ *   crb_step_implicit_adjoint_sched     crb_step_implicit_adjoint run after crb_step_implicit_checkpoint_sched with the same
+ *                                       schedule; sched_bar: device [n_cot][n_intervals][B][n_node][4], dL/d f_sched,
+ *                                       ACCUMULATED as f_held_bar is (intervals the rollout does not reach are left as they
+ *                                       are; padding and constrained entries as in f_held_bar), or NULL.  The work buffer is
+ *                                       that of crb_implicit_adjoint_work_bytes.
+ * Refusals with a schedule, all before the device is touched, crb_last_error() naming the entry point and the argument, in this
+ * order: the counterpart's own CRB_EINVAL cases in their order; then CRB_EINVAL for a NULL f_sched, n_intervals < 1, hold < 1,
+ * n_steps > n_intervals * hold, a schedule together with input->f_held or with grad->f_held_bar, sched_bar without a schedule,
+ * sched_bar aliasing lam, work, ckpt, f_sched or amp_bar; then CRB_EUNSUPPORTED for fp32 plans and beams of more than 256
+ * thread-carried nodes; then CRB_ENODEV for host-only plans. */
+int crb_step_implicit_sched(const crb_plan* plan, void* x, double t0, double h, int n_steps, int n_iter,
+                            const crb_input_desc* input, const crb_input_schedule* sched, const crb_record_desc* rec,
+                            double* t_end, void* stream);
+int crb_step_implicit_checkpoint_sched(const crb_plan* plan, void* x, double t0, double h, int n_steps, int n_iter, int every,
+                                       const crb_input_desc* input, const crb_input_schedule* sched, const crb_record_desc* rec,
+                                       void* ckpt, double* t_end, void* stream);
+int crb_step_implicit_adjoint_sched(const crb_plan* plan, const void* ckpt, void* lam, int n_cot, double t0, double h,
+                                    int n_steps, int n_iter, int every, const crb_input_desc* input,
+                                    const crb_record_desc* rec_bar, const crb_input_cotangent* grad,
+                                    const crb_input_schedule* sched, void* sched_bar, void* work, void* stream);
 
 /* out[b] = x[b][plane][node][dof]  (e.g. tip displacement = plane 0, node n_elem, dof 1;
  * lqr_control.py:168) */

@@ -170,6 +170,8 @@ def load():
     L.crb_step_rk4_feedback_grouped.argtypes = [vp, vp, C.c_double, C.c_double, i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_void_p), vp,
                                                 C.POINTER(InputDesc), vp, C.POINTER(C.c_double), vp]
     L.crb_plan_set_status.argtypes = [vp, vp, C.c_longlong]
+    L.crb_plan_status_steps.restype = C.c_longlong
+    L.crb_plan_status_steps.argtypes = [vp]
     L.crb_tangent_stiffness.argtypes = [vp, vp, vp, vp]
     L.crb_solve_static.argtypes = [vp, vp, C.POINTER(InputDesc), i32, i32, C.c_double, C.c_double, vp, vp, vp]
     L.crb_static_jvp.argtypes = [vp, vp, vp, i32, vp, vp, vp]
@@ -223,6 +225,10 @@ def load():
                                                      C.POINTER(RecordDesc), vp, _dp, vp]
     L.crb_step_implicit_adjoint_sched.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, i32, i32, i32, C.POINTER(InputDesc),
                                                   C.POINTER(RecordDesc), C.POINTER(InputCotangent), sched, vp, vp, vp]
+    L.crb_step_implicit_tangent.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, i32, i32, C.POINTER(InputDesc),
+                                            C.POINTER(InputTangent), _dp, vp]
+    L.crb_step_implicit_tangent_sched.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, i32, i32, C.POINTER(InputDesc),
+                                                  C.POINTER(InputTangent), sched, vp, _dp, vp]
     _lib = L
     return L
 

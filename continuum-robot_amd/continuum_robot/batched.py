@@ -745,9 +745,21 @@ class BeamEnsemble:
         that of the discrete RK4 map itself, exact.  fp64 ensembles only.
         ``held_force=ControlSchedule(U, hold)`` runs a control sequence U [K, B, n] as step(control=U, control_hold=hold)
         does; ``d_held_force`` is then its tangent, [K, B, n] or [D, K, B, n]."""
-        dx, single = self._dirs(dx0_red, 2 * self.n, "step_tangent: dx0_red")
+        def launch(dxd, D, t_start, desc, tan, sd, dsd, t_end):   # (without a schedule, sd and dsd None: crb_step_rk4_tangent)
+            return self._lib.crb_step_rk4_tangent_sched(self.plan.h, self._ptr(self.state), self._ptr(dxd), int(D), t_start,
+                                                        float(dt), int(n_steps), C.byref(desc), C.byref(tan), self._ref(sd),
+                                                        self._ptr(dsd), C.byref(t_end), self._stream())
+        return self._rollout_tangent("step_tangent", "RK4 steps", launch, n_steps, dx0_red, impulse_amp, impulse_duration,
+                                     impulse_index, held_force, d_impulse_amp, d_held_force, t0)
+
+    def _rollout_tangent(self, who, unit, launch, n_steps, dx0_red, impulse_amp, impulse_duration, impulse_index, held_force,
+                         d_impulse_amp, d_held_force, t0):
+        """The body step_tangent and step_implicit_tangent share: decodes the seeds and the input tangents, runs
+        ``launch(dxd, D, t_start, desc, tan, sd, dsd, t_end)`` (the library call on the resident state) and returns the
+        tangent in the shape of ``dx0_red``.  ``who`` / ``unit``: the caller's name and what a schedule's hold counts."""
+        dx, single = self._dirs(dx0_red, 2 * self.n, f"{who}: dx0_red")
         D = dx.shape[0]
-        held_force, sch = self._control(held_force, None, None, n_steps, "step_tangent")
+        held_force, sch = self._control(held_force, None, None, n_steps, who, unit)
         t_start = self.time if t0 is None else float(t0)   # (``time`` moves only when the launch is accepted)
         if d_impulse_amp is not None and impulse_amp is None:
             impulse_amp = torch.zeros((self.n_beams,), dtype=self.dtype, device=self.device)
@@ -757,7 +769,7 @@ class BeamEnsemble:
         if d_impulse_amp is not None:
             da = torch.as_tensor(d_impulse_amp, dtype=self.dtype, device=self.device)
             if tuple(da.shape) not in ((self.n_beams,), (D, self.n_beams)):
-                raise ValueError(f"step_tangent: d_impulse_amp must be [{self.n_beams}] or [{D}, {self.n_beams}]")
+                raise ValueError(f"{who}: d_impulse_amp must be [{self.n_beams}] or [{D}, {self.n_beams}]")
             da = da.expand(D, self.n_beams).contiguous()
             tan.d_amp = da.data_ptr()
             keep.append(da)
@@ -768,28 +780,80 @@ class BeamEnsemble:
             if dU.dim() == 3:
                 dU = dU.unsqueeze(0)
             if dU.dim() != 4 or tuple(dU.shape[1:]) != (K, self.n_beams, self.n) or dU.shape[0] not in (1, D):
-                raise ValueError(f"step_tangent: the tangent of a control schedule must be [{K}, {self.n_beams}, {self.n}] or "
+                raise ValueError(f"{who}: the tangent of a control schedule must be [{K}, {self.n_beams}, {self.n}] or "
                                  f"[{D}, {K}, {self.n_beams}, {self.n}], got {tuple(dU.shape)}")
             dsd = self._pack_dirs(dU.expand(D, -1, -1, -1).reshape(D * K, self.n_beams, self.n), False)
             keep.append(dsd)
         elif d_held_force is not None:
-            dh, _ = self._dirs(d_held_force, self.n, "step_tangent: d_held_force")
+            dh, _ = self._dirs(d_held_force, self.n, f"{who}: d_held_force")
             if dh.shape[0] not in (1, D):
-                raise ValueError("step_tangent: d_held_force must have the directions of dx0_red")
+                raise ValueError(f"{who}: d_held_force must have the directions of dx0_red")
             dhd = self._pack_dirs(dh.expand(D, -1, -1), False)
             tan.df_held = dhd.data_ptr()
             keep.append(dhd)
         t_end = C.c_double(0.0)
         sd, packed = self._sched_desc(sch)
         keep.append(packed)
-        with self._on_device():   # (without a schedule, sd and dsd None, this is crb_step_rk4_tangent)
-            nat.check(self._lib.crb_step_rk4_tangent_sched(self.plan.h, self._ptr(self.state), self._ptr(dxd), int(D), t_start,
-                                                           float(dt), int(n_steps), C.byref(desc), C.byref(tan), self._ref(sd),
-                                                           self._ptr(dsd), C.byref(t_end), self._stream()))
+        with self._on_device():
+            nat.check(launch(dxd, D, t_start, desc, tan, sd, dsd, t_end))
         self._keep = keep + [dxd]
         self.time = t_end.value
         out = self._unpack_dirs(dxd)
         return out[0] if single else out
+
+    def step_implicit_tangent(self, n_steps: int, h: float, dx0_red, n_iter: int = 2, impulse_amp=None,
+                              impulse_duration: float = 0.01, impulse_index: int = -2, held_force=None, d_impulse_amp=None,
+                              d_held_force=None, t0: Optional[float] = None):
+        """``step_implicit()`` with the tangent of the rollout alongside (crb_step_implicit_tangent) -- forward mode through
+        the stepper that takes h = 1e-4 ... 1e-3 s: advances ``state`` and ``time`` as step_implicit() does (``time`` moves
+        only when the launch is accepted) and returns dx(T) = dx(T)/dx(0) dx0 + dx(T)/d amp d_impulse_amp + dx(T)/d f_held
+        d_held_force.  Shapes, [B, .] / [D, B, .] broadcasting and ``held_force=ControlSchedule(U, hold)`` with
+        ``d_held_force`` [K, B, n] / [D, K, B, n] (``hold`` counting implicit steps) are step_tangent's.  The derivative is
+        that of the discrete map step_implicit computes -- ``n_iter`` (1 ... 16) modified-Newton iterations per step, each
+        step's iteration and its tangent starting from the previous step's iterate, from 0 at the first step of a call and of
+        every schedule interval -- the map whose transpose step_implicit_adjoint applies; not of the converged midpoint rule.
+        The base state agrees with step_implicit to rounding, not bitwise.  fp64 ensembles only.
+        Not available: the damped variant (``rho_inf`` < 1), tangents of recorded samples, the closed loop, parameter
+        tangents."""
+        def launch(dxd, D, t_start, desc, tan, sd, dsd, t_end):   # (without a schedule: crb_step_implicit_tangent)
+            return self._lib.crb_step_implicit_tangent_sched(self.plan.h, self._ptr(self.state), self._ptr(dxd), int(D), t_start,
+                                                             float(h), int(n_steps), int(n_iter), C.byref(desc), C.byref(tan),
+                                                             self._ref(sd), self._ptr(dsd), C.byref(t_end), self._stream())
+        return self._rollout_tangent("step_implicit_tangent", "implicit steps", launch, n_steps, dx0_red, impulse_amp,
+                                     impulse_duration, impulse_index, held_force, d_impulse_amp, d_held_force, t0)
+
+    def linearize_implicit(self, h: float, n_steps: int = 1, n_iter: int = 2, x_red=None, held_force=None):
+        """The discrete-time linearisation of the implicit stepper: (A_d [B, 2n, 2n], B_d [B, 2n, n]), the Jacobians of
+        x(t + n_steps h) with respect to x(t) and to a force held over those steps, of the sampled plant
+        x_{k+1} = Phi_h(x_k, u_k) that ``step_implicit(n_steps, h, n_iter, held_force=u_k)`` applies -- what a digital LQR
+        (the sampled form of LinearQuadraticRegulator, linear_quadratic_regulator.py:84-147) or a linear MPC designs on
+        (examples/digital_lqr.py).  Taken at (``x_red`` [B, 2n], ``held_force`` [B, n]); None = the resident state and 0.
+        Two launches of crb_step_implicit_tangent with identity seeds (2n state, n input directions) on a copy: ``state``,
+        ``time`` and ``status`` are untouched.  Padding rows and columns of ``mixed_topology`` ensembles are zero."""
+        B, n = self.n_beams, self.n
+        x0 = self.state.clone() if x_red is None else self.pack_state(x_red)
+        held = None if held_force is None else self._dev(held_force, (B, n))
+        eye2 = torch.eye(2 * n, dtype=self.dtype, device=self.device)
+        eye1 = torch.eye(n, dtype=self.dtype, device=self.device)
+        saved = (self.state, self.time, getattr(self, "_status", None))
+        had_status = saved[2] is not None
+        try:
+            if had_status:   # (the launches below must not report into the ensemble's status, nor count as its steps)
+                with self._on_device():
+                    steps_done = int(self._lib.crb_plan_status_steps(self.plan.h))
+                    nat.check(self._lib.crb_plan_set_status(self.plan.h, None, 0))
+            self.state = x0.clone()
+            dA = self.step_implicit_tangent(n_steps, h, eye2[:, None, :].expand(2 * n, B, 2 * n), n_iter=n_iter, held_force=held,
+                                            t0=0.0)
+            self.state = x0
+            dB = self.step_implicit_tangent(n_steps, h, torch.zeros((n, B, 2 * n), dtype=self.dtype, device=self.device),
+                                            n_iter=n_iter, held_force=held, d_held_force=eye1[:, None, :].expand(n, B, n), t0=0.0)
+        finally:
+            self.state, self.time = saved[0], saved[1]
+            if had_status:
+                with self._on_device():
+                    nat.check(self._lib.crb_plan_set_status(self.plan.h, self._ptr(saved[2]), steps_done))
+        return dA.permute(1, 2, 0).contiguous(), dB.permute(1, 2, 0).contiguous()
 
     # ------------------------------------------------------------------ adjoint (reverse mode, crb_adjoint.h)
     ADJOINT_WORK_BUDGET = 1 << 30   # bytes the default checkpoint interval keeps crb_step_rk4_adjoint's work buffer under

@@ -20,6 +20,7 @@
 #include "crb_tangent_launch.h"
 #include "crb_adjoint_launch.h"
 #include "crb_implicit_adjoint_launch.h"
+#include "crb_implicit_tangent_launch.h"
 #include "crb_feedback_adjoint_launch.h"
 #include "crb_host.h"
 #include "crb_blocked.h"
@@ -779,6 +780,8 @@ extern "C" int crb_plan_set_status(const crb_plan* p, void* status, long long st
     p->status_steps = steps_done;
     return CRB_OK;
 }
+
+extern "C" long long crb_plan_status_steps(const crb_plan* p) { return p ? p->status_steps : -1; }
 
 extern "C" int crb_plan_get_layout(const crb_plan* p, crb_layout* o) {
     if (!p || !o) return fail(CRB_EINVAL, "null argument");
@@ -2975,6 +2978,66 @@ extern "C" int crb_step_implicit_adjoint_sched(const crb_plan* p, const void* ck
         ib.carry_in = g < nseg - 1 ? 1 : 0;
         HIP_TRY(crb::launch_imp_adj_backward(k, b, ib, groups, n_cot, p->NT, st));
     }
+    return CRB_OK;
+}
+
+// ---- tangent of the implicit stepper (crb_implicit_tangent.h)
+extern "C" int crb_step_implicit_tangent(const crb_plan* p, void* x, void* dx, int n_dir, double t0, double h, int n_steps, int n_iter,
+                                         const crb_input_desc* in, const crb_input_tangent* din, double* t_end, void* stream) {
+    return crb_step_implicit_tangent_sched(p, x, dx, n_dir, t0, h, n_steps, n_iter, in, din, nullptr, nullptr, t_end, stream);
+}
+
+extern "C" int crb_step_implicit_tangent_sched(const crb_plan* p, void* x, void* dx, int n_dir, double t0, double h, int n_steps,
+                                               int n_iter, const crb_input_desc* in, const crb_input_tangent* din,
+                                               const crb_input_schedule* sched, const void* d_sched, double* t_end, void* stream) {
+    // every refusal before the device is touched, in the order the implicit adjoint documents: CRB_EINVAL (the call's own cases,
+    // then the schedule's), CRB_EUNSUPPORTED, CRB_ENODEV
+    const std::string who(sched || d_sched ? "crb_step_implicit_tangent_sched" : "crb_step_implicit_tangent");
+    if (!p) return fail(CRB_EINVAL, who + ": null plan");
+    if (!x || !dx) return fail(CRB_EINVAL, who + ": null state or tangent");
+    if (n_dir < 1 || n_dir > 65535) return fail(CRB_EINVAL, who + ": n_dir must be in [1, 65535]");
+    if (n_steps < 0) return fail(CRB_EINVAL, who + ": n_steps must be >= 0");
+    if (n_iter < 1 || n_iter > IMP_ADJ_MAX_ITER) return fail(CRB_EINVAL, who + ": n_iter must be in [1, 16]");
+    if (!(h > 0)) return fail(CRB_EINVAL, who + ": h must be positive");
+    Forcing f;
+    if (int rc = decode_input(p, in, who.c_str(), &f)) return rc;
+    if (din && din->d_amp && !f.impulse)
+        return fail(CRB_EINVAL, who + ": d_amp needs an impulse input (its amplitude is what it differentiates)");
+    if (d_sched && !sched) return fail(CRB_EINVAL, who + ": d_sched needs a schedule (sched is null)");
+    Schedule sc;
+    if (int rc = decode_schedule(sched, in, n_steps, who.c_str(), &sc)) return rc;
+    if (sc.f && din && din->df_held) return fail(CRB_EINVAL, who + ": a schedule and dinput->df_held are given together");
+    if (p->dtype != CRB_F64) return fail(CRB_EUNSUPPORTED, who + ": the tangent of the implicit stepper needs an fp64 plan");
+    if (p->NT > TANGENT_MAX_NT) return fail(CRB_EUNSUPPORTED, who + ": beams of more than 256 thread-carried nodes are not supported");
+    if (int rc = need_device(p, who.c_str())) return rc;
+    if (t_end) *t_end = clock_after(t0, h, n_steps);
+    if (n_steps == 0) return CRB_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    KParams<double> k;
+    if (int rc = imp_adjoint_params(p, h, st, &k)) return rc;   // (A's tables where M's are, k.dt = h)
+    k.x = static_cast<double*>(x);
+    set_io(k, f);
+    k.t0 = t0; k.n_steps = n_steps;
+    arm_status(p, k, n_steps);
+    TangentParams<double> q{};
+    q.x0 = k.x;
+    if (n_dir > 1) {   // (instance d = 0 writes the base back while the others may still be loading it: they read a copy)
+        const size_t bytes = size_t(p->B) * 2 * p->n_node * 4 * sizeof(double);
+        if (!p->d_tan_x0) HIP_TRY(hipMalloc(&p->d_tan_x0, bytes));
+        HIP_TRY(hipMemcpyAsync(p->d_tan_x0, x, bytes, hipMemcpyDeviceToDevice, st));
+        q.x0 = static_cast<const double*>(p->d_tan_x0);
+    }
+    q.dx = static_cast<double*>(dx);
+    if (din) {
+        q.du_held = static_cast<const double*>(din->df_held);
+        q.d_amp = static_cast<const double*>(din->d_amp);
+    }
+    if (sc.f) {
+        set_sched(p, k, sc, 0);
+        q.du_held = static_cast<const double*>(d_sched);
+        q.du_dir_stride = size_t(sc.K) * sched_interval_elems(p);
+    }
+    HIP_TRY(crb::launch_imp_jvp_step(k, q, n_iter, sc.f != nullptr, (p->B + p->G - 1) / p->G, n_dir, p->NT, st));
     return CRB_OK;
 }
 

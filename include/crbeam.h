@@ -453,6 +453,10 @@ int crb_solve_controlled(const crb_plan* plan, void* x, double t0, double dt_eva
  * (segments.py:178-208) is linearly unstable for long chains and solve_ivp simply returns NaN rows; this turns that into a
  * condition the planning layer can read per rollout.  The beams are independent: a diverged beam never affects another. */
 int crb_plan_set_status(const crb_plan* plan, void* status, long long steps_done);
+/* The step count the status reporting stands at (steps_done of crb_plan_set_status plus the steps of every launch since), so
+ * that a caller can switch the reporting off around launches on a copy of the state and restore it exactly
+ * (BeamEnsemble.linearize_implicit); -1 for a NULL plan. */
+long long crb_plan_status_steps(const crb_plan* plan);
 
 /* Feedback force of a whole ensemble, u = K (r - x) (FullStateLinear.compute_input,
  * control/full_state_linear.py:81; loop of examples/lqr_control.py:95-111), as one MFMA GEMM in the plan's dtype
@@ -692,6 +696,31 @@ int crb_step_implicit_adjoint_sched(const crb_plan* plan, const void* ckpt, void
                                     int n_steps, int n_iter, int every, const crb_input_desc* input,
                                     const crb_record_desc* rec_bar, const crb_input_cotangent* grad,
                                     const crb_input_schedule* sched, void* sched_bar, void* work, void* stream);
+
+/* ---- Tangent of the implicit stepper: forward-mode derivatives of stiff rollouts (csrc/crb_implicit_tangent.h).
+ * crb_step_implicit with the tangent of its discrete map alongside: the exact derivative of what crb_step_implicit computes
+ * (n_iter modified-Newton iterations per step on A = M + h^2/4 K0, each step's iteration and its tangent starting from the
+ * previous step's final iterate, both 0 at the first step of a call) -- the statement the implicit adjoint transposes -- at the
+ * steps h = 1e-4 ... 1e-3 s that take the horizons the examples integrate with solve_ivp(method="LSODA")
+ * (examples/example_utilities.py:153-159).  With identity seeds it gives the discrete-time pair (A_d, B_d) of the sampled
+ * plant x_{k+1} = Phi_h(x_k, u_k) that a sampled design of control/linear_quadratic_regulator.py's controller needs.
+ *   x, dx, n_dir, input, dinput   as crb_step_rk4_tangent (x advances in place, dx [n_dir][B][2][n_node][4] in place, per-beam
+ *                                 status written); the clock and the midpoint sampling of the impulse are crb_step_implicit's
+ *   sched, d_sched                as crb_step_rk4_tangent_sched, `hold` counting implicit steps.  A scheduled call is the chain
+ *                                 of one call per interval with dx carried: the first step of every interval starts from
+ *                                 a^0 = 0 and da^0 = 0
+ * Refusals, all before the device is touched, crb_last_error() naming the entry point, in this order: CRB_EINVAL for a NULL
+ * plan, state or tangent, n_dir outside 1 ... 65535, n_steps < 0, n_iter outside 1 ... 16, h <= 0, a bad input description,
+ * d_amp without an impulse input, then the schedule's cases (a NULL f_sched, n_intervals < 1, hold < 1,
+ * n_steps > n_intervals * hold, a schedule together with input->f_held or dinput->df_held, d_sched without a schedule); then
+ * CRB_EUNSUPPORTED for fp32 plans and beams of more than 256 thread-carried nodes; then CRB_ENODEV for host-only plans.
+ * *t_end is written only by a call that is not refused; n_steps == 0 returns CRB_OK and touches nothing else.
+ * Not covered: the damped variant (rho_inf < 1), tangents of recorded samples, the closed loop, parameter tangents. */
+int crb_step_implicit_tangent(const crb_plan* plan, void* x, void* dx, int n_dir, double t0, double h, int n_steps, int n_iter,
+                              const crb_input_desc* input, const crb_input_tangent* dinput, double* t_end, void* stream);
+int crb_step_implicit_tangent_sched(const crb_plan* plan, void* x, void* dx, int n_dir, double t0, double h, int n_steps,
+                                    int n_iter, const crb_input_desc* input, const crb_input_tangent* dinput,
+                                    const crb_input_schedule* sched, const void* d_sched, double* t_end, void* stream);
 
 /* out[b] = x[b][plane][node][dof]  (e.g. tip displacement = plane 0, node n_elem, dof 1;
  * lqr_control.py:168) */

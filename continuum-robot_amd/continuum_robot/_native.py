@@ -229,6 +229,11 @@ def load():
                                             C.POINTER(InputTangent), _dp, vp]
     L.crb_step_implicit_tangent_sched.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, i32, i32, C.POINTER(InputDesc),
                                                   C.POINTER(InputTangent), sched, vp, _dp, vp]
+    L.crb_step_implicit_feedback.argtypes = [vp, vp, C.c_double, C.c_double, i32, i32, i32, vp, vp, C.POINTER(InputDesc),
+                                             C.POINTER(RecordDesc), vp, vp, _dp, vp]
+    L.crb_implicit_feedback_work_bytes.restype = C.c_size_t
+    L.crb_implicit_feedback_work_bytes.argtypes = [vp]
+    L.crb_implicit_feedback_path.argtypes = [vp]
     _lib = L
     return L
 

@@ -1361,6 +1361,72 @@ class BeamEnsemble:
         self.time = t_end.value
         return (self.time, samples) if record is not None else self.time
 
+    def step_implicit_feedback(self, n_steps: int, h: float, gain, reference=None, hold: int = 1, n_iter: int = 2,
+                               impulse_amp=None, impulse_duration: float = 0.01, impulse_index: int = -2, held_force=None,
+                               t0: Optional[float] = None, record=None, record_every: int = 1, return_control: bool = False):
+        """A digital (sampled-data) state-feedback loop in ONE native call (crb_step_implicit_feedback): ``n_steps`` implicit
+        midpoint steps of size ``h``; every ``hold`` steps the controller samples the state as it stands and holds
+        u_k = held_force + K (r - x_k) until the next sample (zero-order hold), the tip impulse on top -- the loop that
+        examples/digital_lqr.py closes from Python with unpack_state(), a matmul and step_implicit(hold, h, held_force=u) per
+        sample, and exactly the chain of those calls.  The held input is constant over a step, so the iteration matrix is the
+        open loop's and the loop is as stable at h = 1e-4 ... 1e-3 s as the open loop is (``step_feedback`` evaluates
+        u = K (r - x) inside the RK4 stages and needs dt <= ~8e-6 s).
+
+        gain       [n, 2n], reduced ordering (e.g. from ``linearize_implicit`` and a discrete Riccati solve), one gain for the
+                   whole ensemble (a list of gains raises NotImplementedError)
+        reference  [B, 2n] or None (= regulation to 0)
+        hold       implicit steps per controller sample (>= 1); the last sample may be cut short by ``n_steps``
+        record     as in ``step_implicit``; ``record_every`` must divide ``hold`` or be a multiple of it
+        Returns ``time``, then ``samples`` when ``record`` is given, then ``control`` [K, B, n] (K = ceil(n_steps / hold),
+        reduced ordering: the held input of every sample) when ``return_control`` is set -- ``ControlSchedule(control, hold)``
+        replays the call through ``step_implicit``.  ``implicit_feedback_path()`` says which form runs.  fp64 ensembles with
+        one free-DOF set."""
+        who = "step_implicit_feedback"
+        if isinstance(gain, (list, tuple)):
+            raise NotImplementedError(f"{who}: a list of gains (per-beam or grouped gains) is not available in the implicit closed "
+                                      f"loop; pass one [{self.n}, {2 * self.n}] gain for the whole ensemble")
+        if int(hold) != hold or int(hold) < 1:
+            raise ValueError(f"{who}: hold must be an integer >= 1 (implicit steps per sample)")
+        hold = int(hold)
+        K = torch.as_tensor(gain, dtype=self.dtype, device=self.device).contiguous()
+        if tuple(K.shape) != (self.n, 2 * self.n):
+            raise ValueError(f"{who}: gain must be [{self.n}, {2 * self.n}], got {tuple(K.shape)}")
+        ref = None
+        if reference is not None:
+            ref = torch.as_tensor(reference, dtype=self.dtype, device=self.device).contiguous()
+            if tuple(ref.shape) != (self.n_beams, 2 * self.n):
+                raise ValueError(f"{who}: reference must be [{self.n_beams}, {2 * self.n}], got {tuple(ref.shape)}")
+        if t0 is not None:
+            self.time = float(t0)
+        desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index, held_force)
+        rec, samples = self._record_desc(record, n_steps, record_every)
+        n_samples = -(-int(n_steps) // hold)
+        u_out = None
+        if return_control:
+            u_out = torch.zeros((max(n_samples, 1), self.n_beams, self.n_node, 4), dtype=self.dtype, device=self.device)
+        nbytes = int(self._lib.crb_implicit_feedback_work_bytes(self.plan.h))
+        work = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=self.device)
+        t_end = C.c_double(0.0)
+        with self._on_device():
+            nat.check(self._lib.crb_step_implicit_feedback(self.plan.h, self._ptr(self.state), self.time, float(h), int(n_steps),
+                                                           int(n_iter), hold, self._ptr(K), self._ptr(ref), C.byref(desc),
+                                                           self._ref(rec), self._ptr(u_out), self._ptr(work), C.byref(t_end),
+                                                           self._stream()))
+        self._keep = keep + [samples, K, ref, u_out, work]
+        self.time = float(t_end.value)
+        out = (self.time,)
+        if record is not None:
+            out += (samples,)
+        if return_control:
+            out += (self._unpack_force_dirs(u_out[:n_samples]) if n_samples > 0 else
+                    torch.zeros((0, self.n_beams, self.n), dtype=self.dtype, device=self.device),)
+        return out if len(out) > 1 else self.time
+
+    def implicit_feedback_path(self) -> str:
+        """Which form ``step_implicit_feedback`` takes for this ensemble: "in-kernel" (beams of one wave whose gain fits LDS: the
+        whole call is one launch) or "chain" (per sample one ensemble GEMM and one launch of the implicit stepper)."""
+        return {0: "chain", 1: "in-kernel"}[int(self._lib.crb_implicit_feedback_path(self.plan.h))]
+
     def solve_ivp(self, t_span, t_eval, method: str = "LSODA", impulse_amp=None, impulse_duration: float = 0.01,
                   impulse_index: int = -2, held_force=None, substeps: Union[int, str, None] = None,
                   rtol: float = 1e-3, atol: float = 1e-6, control: str = "all", gain=None, reference=None,

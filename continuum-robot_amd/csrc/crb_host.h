@@ -26,6 +26,9 @@ namespace crb {
 //   CRB_FUSED_FEEDBACK=0|1: crb_step_rk4_feedback never / whenever the gain fits LDS in its fused form (unset: chosen by
 //       size) -- test_fused_feedback_stepper_matches_the_stage_split_one_and_the_oracle,
 //       test_fused_feedback_stepper_walks_over_groups_of_beams
+//   CRB_IMPLICIT_FEEDBACK=0|1: crb_step_implicit_feedback as a chain of one GEMM and one implicit launch per sample / in its
+//       in-kernel form wherever the gain fits LDS (unset: there, for ensembles whose workgroups are all resident) --
+//       tests/test_implicit_feedback.py
 //   CRB_CTRL_STREAM_GAIN=1: crb_solve_controlled's closed loop reads the gain from global memory even where it fits LDS --
 //       test_controlled_closed_loop_large.py::test_streamed_gain_on_small_gains_takes_the_same_steps
 //   CRB_LOOP=0|1: crb_step_rk4_feedback never / whenever eligible in its persistent form (unset: 512 beams and more) --

@@ -41,11 +41,29 @@ struct StiffParams {
     double kappa, cv, c_qv, c_qa, c_va, tf_frac, alpha_m, inv1m, c_q0, c_q1, c_v0, c_v1;
 };
 
+// FB: what the sampled-data feedback instance (crb_step_implicit_feedback) needs beyond StiffParams.  Only that instance takes
+// this block as its second kernel argument: the argument layout of every other instance is StiffParams, unchanged.
+template <typename T>
+struct StiffFbParams : StiffParams<T> {
+    T* u_out;                 // [ceil(n_steps / hold)][B][n_node][4]: the held input of every sample, or nullptr
+    int hold;                 // implicit steps per sample
+};
+template <typename T, bool FB>
+struct StiffArg { typedef StiffParams<T> type; };
+template <typename T>
+struct StiffArg<T, true> { typedef StiffFbParams<T> type; };
+
 // SCHED: a control schedule (crb_input_schedule, KParams sched_*) -- at the top of a step that is an interval's first, uh is
 // reloaded from that interval's record and the starting iterate is reset to 0: the call is the chain of one call per interval.
-template <typename T, int LV, int MAXT, int MINW, bool DAMPED = false, bool SCHED = false>
-__global__ void __launch_bounds__(MAXT, MINW) crb_implicit_kernel(const KParams<T> p, const StiffParams<T> q) {
+// FB: zero-order-hold state feedback (KParams fb_gain / fb_ref / red_map / n_red, StiffFbParams) -- at the top of a step that is
+// a sample's first, e = r - x is formed from the state as it stands, uh = f_held + K e becomes the held input of the sample
+// (and its record of u_out) and the starting iterate is reset to 0: the call is the chain of one held-force call per
+// sample.  The input is constant over a step, so A, its tables and the iteration are those of the open loop.  The gain sits
+// in LDS behind the exchange columns, as in crb_beam_kernel<..., FB>; workgroups of ONE wave (beams of up to 32 slots).
+template <typename T, int LV, int MAXT, int MINW, bool DAMPED = false, bool SCHED = false, bool FB = false>
+__global__ void __launch_bounds__(MAXT, MINW) crb_implicit_kernel(const KParams<T> p, const typename StiffArg<T, FB>::type q) {
     static_assert(!(DAMPED && SCHED), "the damped variant has no scheduled form");
+    static_assert(!(FB && (DAMPED || SCHED)), "the feedback form holds its own input: no schedule, no damped variant");
     const int NT = blockDim.x;
     const Lds<T> lds = carve_lds<T>(NT);
     Topo tp;
@@ -120,8 +138,44 @@ __global__ void __launch_bounds__(MAXT, MINW) crb_implicit_kernel(const KParams<
         for (int c = 0; c < 3; ++c) { acc_n[c] = q.a0[xoff + plane + c] * sc.mask[c]; am[c] = acc_n[c]; }
     }
 
+    // FB: reduced indices and reference of this node, the gain into LDS (transposed, zero-padded), its MFMA fragments
+    const int fb_n = p.n_red, fb_n2p = fb_padded(2 * p.n_red);
+    T* const fbx = lds.r1 + 3 * NT;                       // [G][2n padded]  r - x of the sample, per beam of the workgroup
+    T* const fbK = fbx + size_t(p.G) * fb_n2p;            // [2n padded][n]  gain, transposed
+    T* const fbu = fbK + size_t(fb_n2p) * fb_n;           // [G][FBM_UPAD]   K e of the sample (matrix-core form)
+    const bool fb_mfma = FB && fb_on_matrix_cores(p.G, fb_n);
+    T fb_af[FBM_MT][FBM_KS];
+    T rq[3] = {T(0), T(0), T(0)}, rv[3] = {T(0), T(0), T(0)}, fh[3] = {T(0), T(0), T(0)};
+    int red[3] = {-1, -1, -1};
+    if constexpr (FB) {
+        const int fb_n2 = 2 * fb_n;
+        if (valid) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                fh[c] = uh[c];
+                red[c] = p.red_map[3 * node + c];
+                if (red[c] >= 0 && p.fb_ref) {
+                    rq[c] = p.fb_ref[size_t(beam) * fb_n2 + red[c]];
+                    rv[c] = p.fb_ref[size_t(beam) * fb_n2 + fb_n + red[c]];
+                }
+            }
+        }
+        for (int idx = tp.t; idx < fb_n * fb_n2; idx += NT) {
+            const int i = idx / fb_n2, k = idx - i * fb_n2;
+            fbK[size_t(k) * fb_n + i] = p.fb_gain[idx];
+        }
+        for (int idx = tp.t; idx < (fb_n2p - fb_n2) * fb_n; idx += NT) fbK[size_t(fb_n2) * fb_n + idx] = T(0);   // zero columns
+        for (int idx = tp.t; idx < p.G * fb_n2p; idx += NT) fbx[idx] = T(0);   // (entries no thread owns -- padding, beams past B -- stay 0)
+        __syncthreads();
+        if (fb_mfma) fbm_gain_fragments<T>(fb_af, fbK, fb_n, fb_n2p, tp.lane);
+    }
+
     const T h = T(q.h), hh = DAMPED ? T(q.cv) : T(0.5 * q.h), alpha = DAMPED ? T(q.kappa) : T(0.25 * q.h * q.h), alpha2 = T(0.5 * q.h * q.h);
     double tc = p.t0;
+    // FB: steps until the next sample is taken (uniform over the workgroup), and this node's record of the current sample
+    int fb_left = 0;
+    T* fb_rec = nullptr;
+    if constexpr (FB) fb_rec = q.u_out ? q.u_out + aoff : nullptr;
     // SCHED: steps until the next interval's force takes uh's place, and this node's record of the current interval
     int sched_left = SCHED ? p.sched_first : -1;
     const T* sched_u = p.u_held + aoff;
@@ -137,6 +191,34 @@ __global__ void __launch_bounds__(MAXT, MINW) crb_implicit_kernel(const KParams<
                 }
             }
             --sched_left;
+        }
+        if constexpr (FB) {
+            if (fb_left == 0) {   // (uniform over the workgroup: every thread, padding included, takes part in the barriers)
+                fb_left = q.hold;
+                T* const e = fbx + size_t(valid ? g : 0) * fb_n2p;
+                if (valid) {   // a thread writes its own node's entries of its own beam's row, nothing else
+#pragma unroll
+                    for (int c = 0; c < 3; ++c)
+                        if (red[c] >= 0) { e[red[c]] = rq[c] - q0[c]; e[fb_n + red[c]] = rv[c] - v0[c]; }
+                }
+                T ufb[3];
+                fb_feedback<T>(fb_mfma, fb_af, fbx, fbK, fbu, p.G, valid ? g : 0, fb_n, fb_n2p, tp.lane, valid, red, ufb);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    uh[c] = fh[c] + ufb[c];
+                    am[c] = T(0);   // the sample starts as a call does: a^0 = 0
+                }
+                if (fb_rec) {
+                    if (valid) {
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) fb_rec[c] = red[c] >= 0 ? uh[c] : T(0);   // (free DOFs only, as the GEMM's rows)
+                        fb_rec[3] = T(0);
+                    }
+                    fb_rec += size_t(p.B) * plane;
+                }
+                __syncthreads();   // the next sample's e and K e are written only after every read of this one's
+            }
+            --fb_left;
         }
         const double tm = __dadd_rn(tc, (DAMPED ? q.tf_frac : 0.5) * q.h), t1 = __dadd_rn(tc, q.h);
         const T av = (tm < p.duration) ? amp : T(0);

@@ -21,6 +21,7 @@
 #include "crb_adjoint_launch.h"
 #include "crb_implicit_adjoint_launch.h"
 #include "crb_implicit_tangent_launch.h"
+#include "crb_implicit_feedback_launch.h"
 #include "crb_feedback_adjoint_launch.h"
 #include "crb_host.h"
 #include "crb_blocked.h"
@@ -2206,6 +2207,155 @@ extern "C" int crb_feedback_force(const crb_plan* p, const void* xs, const void*
         return fail(CRB_EUNSUPPORTED, "crb_feedback_force: one gain matrix for the ensemble needs one free-DOF set (uniform boundary conditions / lengths)");
     return p->dtype == CRB_F64 ? feedback_force_impl<double>(p, xs, gain, ref, u, stream)
                                : feedback_force_impl<float>(p, xs, gain, ref, u, stream);
+}
+
+// ------------------------------------------------------------------ sampled-data state feedback in the implicit stepper
+// crb_step_implicit_feedback: u_k = f_held + K (r - x) sampled every `hold` steps and held (zero-order hold), the chain of one
+// crb_step_implicit call per sample.  In-kernel form (crb_stiff.h, FB): beams of one wave whose gain fits LDS, the whole call
+// one launch.  Chain form: per sample one GEMM over the ensemble (crb_feedback_force) and one launch of the implicit stepper.
+namespace {
+// the gain fits LDS next to the exchange columns (the limit of fused_feedback_ok) and a beam lives in one wave
+bool implicit_feedback_fits(const crb_plan* p) {
+    return f64(p) && !p->mixed_topology && p->lognw == 0 && p->NT == 64 && crb::implicit_feedback_built(p->levels_full) &&
+           crb::implicit_feedback_lds_bytes(p->NT, p->G, p->n_free) <= size_t(144) * 1024;
+}
+// CRB_IMPLICIT_FEEDBACK=0: the chain form; =1: the in-kernel form wherever the gain fits; unset: wherever it fits AND every
+// workgroup of the launch is resident at once.  A workgroup is ONE wave at one wave per SIMD with its own copy of the gain: a
+// CU holds min(4, 160 KB / LDS bytes) of them, and an ensemble that needs several rounds of workgroups is faster as a chain,
+// whose steps run at the lean kernels' occupancy (hold = 1: 4096 x 30 elements, one workgroup per CU, 8 rounds, 78 against
+// 23 us per sample; 512 x 30, resident, 10.2 against 14.1; 4096 x 10, 683 workgroups in one round, 4.9 against 11.2 --
+// DESIGN.md section 10, which also names the case this rule loses: 16384 x 10 at hold <= 2)
+bool implicit_feedback_in_kernel(const crb_plan* p) {
+    if (!implicit_feedback_fits(p)) return false;
+    if (const char* v = env("CRB_IMPLICIT_FEEDBACK")) return std::atoi(v) != 0;
+    const size_t per_cu = (size_t(160) * 1024) / crb::implicit_feedback_lds_bytes(p->NT, p->G, p->n_free);
+    const size_t groups = size_t((p->B + p->G - 1) / p->G);
+    return groups <= 256 * (per_cu < 4 ? per_cu : 4);
+}
+StiffParams<double> stiff_params(const crb_plan* p, double h, int n_iter) {
+    StiffParams<double> q{};
+    q.a_levels = static_cast<const double*>(p->d_alevels);
+    q.a_final = static_cast<const double*>(p->d_afinal);
+    q.alv_stride = p->asm_in->nd > 1 ? size_t(p->levels_full) * p->S * PCR_LEVEL_VALS : 0;
+    q.afin_stride = p->asm_in->nd > 1 ? size_t(p->S) * PCR_FINAL_VALS : 0;
+    q.h = h;
+    q.n_iter = n_iter;
+    return q;
+}
+int implicit_feedback_fused(const crb_plan* p, void* x, double t0, double h, int n_steps, int n_iter, int hold, const void* gain,
+                            const void* ref, const Forcing& f, const Recording& rec, void* u_out, hipStream_t st) {
+#ifdef CRB_FAST_BUILD
+    return fail(CRB_EUNSUPPORTED, "CRB_FAST_BUILD: implicit stepper not built");
+#else
+    if (int rc = ensure_red_map(p)) return rc;
+    if (int rc = stiff_tables<double>(p, 0.25 * h * h, st)) return rc;
+    KParams<double> k = base_params<double>(p);
+    k.x = static_cast<double*>(x);
+    set_io(k, f, &rec);
+    k.t0 = t0; k.dt = h; k.n_steps = n_steps;
+    arm_status(p, k, n_steps);
+    k.red_map = p->d_red_map;
+    k.n_red = p->n_free;
+    k.fb_gain = static_cast<const double*>(gain);
+    k.fb_ref = static_cast<const double*>(ref);
+    // (the kernel writes the records of the thread-carried nodes: a dropped fixed node's entries read as zero)
+    if (u_out)
+        HIP_TRY(hipMemsetAsync(u_out, 0, size_t((n_steps + hold - 1) / hold) * size_t(p->B) * size_t(p->n_node) * 4 * sizeof(double), st));
+    StiffFbParams<double> q{};
+    static_cast<StiffParams<double>&>(q) = stiff_params(p, h, n_iter);
+    q.u_out = static_cast<double*>(u_out);
+    q.hold = hold;
+    const hipError_t e = crb::launch_implicit_feedback(k, q, p->stiff_levels, (p->B + p->G - 1) / p->G,
+                                                       crb::implicit_feedback_lds_bytes(p->NT, p->G, p->n_free), st);
+    if (e != hipSuccess) return fail(CRB_EHIP, std::string("crb_step_implicit_feedback: ") + hipGetErrorString(e));
+    return CRB_OK;
+#endif
+}
+int implicit_feedback_chain(const crb_plan* p, void* x, double t0, double h, int n_steps, int n_iter, int hold, const void* gain,
+                            const void* ref, const Forcing& f, const Recording& rec, void* u_out, void* work, hipStream_t st) {
+    if (int rc = stiff_tables<double>(p, 0.25 * h * h, st)) return rc;
+    const StiffParams<double> q = stiff_params(p, h, n_iter);
+    const size_t force = size_t(p->B) * size_t(p->n_node) * 4, plane2 = size_t(p->B) * 2 * size_t(p->n_node) * 4;
+    const int n_samples = (n_steps + hold - 1) / hold;
+    // entries of a force record that the GEMM does not write (constrained DOFs, the padding component) read as zero
+    if (u_out) HIP_TRY(hipMemsetAsync(u_out, 0, size_t(n_samples) * force * sizeof(double), st));
+    else HIP_TRY(hipMemsetAsync(work, 0, force * sizeof(double), st));
+    // a beam that goes non-finite is marked with the step count at the end of the CALL, as the one launch of the other form does
+    KParams<double> armed = base_params<double>(p);
+    arm_status(p, armed, n_steps);
+    double t = t0;
+    for (int s = 0, ks = 0; s < n_steps; s += hold, ++ks) {
+        const int hs = n_steps - s < hold ? n_steps - s : hold;
+        double* const u = u_out ? static_cast<double*>(u_out) + size_t(ks) * force : static_cast<double*>(work);
+        if (int rc = feedback_force_impl<double>(p, x, gain, ref, u, st)) return rc;
+        if (f.held)
+            HIP_TRY(crb::launch_feedback_held(u, static_cast<const double*>(f.held), p->d_row_off, p->n_free, p->B,
+                                              size_t(p->n_node) * 4, st));
+        Forcing fs = f;
+        fs.held = u;
+        // the sample's slice of the recording: `every` divides hold (hs / every samples) or is a multiple of it (one sample at
+        // the end of every (every / hold)-th whole sample)
+        Recording rs;
+        if (rec.out) {
+            long first = -1;
+            if (hold % rec.every == 0) {
+                if (hs / rec.every > 0) { rs = rec; first = s / rec.every; }
+            } else if (hs == hold && (s + hold) % rec.every == 0) {
+                rs = rec; rs.every = hold; first = (s + hold) / rec.every - 1;
+            }
+            if (first >= 0)
+                rs.out = static_cast<double*>(rec.out) + size_t(first) * (rec.slot == REC_ALL_SLOTS ? plane2 : size_t(1));
+        }
+        KParams<double> k = base_params<double>(p);
+        k.x = static_cast<double*>(x);
+        set_io(k, fs, &rs);
+        k.t0 = t; k.dt = h; k.n_steps = hs;
+        k.status = armed.status; k.status_value = armed.status_value;
+        if (int rc = launch_implicit<double>(p, k, q, st)) return rc;
+        t = clock_after(t, h, hs);
+    }
+    return CRB_OK;
+}
+}  // namespace
+
+extern "C" size_t crb_implicit_feedback_work_bytes(const crb_plan* p) {
+    if (!p) return 0;
+    return size_t(p->B) * size_t(p->n_node) * 4 * sizeof(double);   // one force record (the chain form's held input)
+}
+
+extern "C" int crb_implicit_feedback_path(const crb_plan* p) {
+    if (!p) return 0;
+    return implicit_feedback_in_kernel(p) ? 1 : 0;
+}
+
+extern "C" int crb_step_implicit_feedback(const crb_plan* p, void* x, double t0, double h, int n_steps, int n_iter, int hold,
+                                          const void* gain, const void* ref, const crb_input_desc* in, const crb_record_desc* rec,
+                                          void* u_out, void* work, double* t_end, void* stream) {
+    // every refusal before the device is touched, in the order of crb_step_implicit_sched: CRB_EINVAL, CRB_EUNSUPPORTED, CRB_ENODEV
+    const std::string who("crb_step_implicit_feedback");
+    if (!p) return fail(CRB_EINVAL, who + ": null plan");
+    if (!x || !gain || !work) return fail(CRB_EINVAL, who + ": null pointer");
+    if (n_steps < 0) return fail(CRB_EINVAL, who + ": n_steps must be >= 0");
+    if (!(h > 0)) return fail(CRB_EINVAL, who + ": h must be positive");
+    if (n_iter < 1) return fail(CRB_EINVAL, who + ": n_iter must be >= 1");
+    if (hold < 1) return fail(CRB_EINVAL, who + ": hold must be >= 1");
+    Recording r;
+    if (int rc = decode_record(p, rec, n_steps, true, who.c_str(), &r)) return rc;
+    if (rec && hold % rec->every != 0 && rec->every % hold != 0)
+        return fail(CRB_EINVAL, who + ": the record stride must divide hold or be a multiple of it");
+    Forcing f;
+    if (int rc = decode_input(p, in, who.c_str(), &f)) return rc;
+    if (p->dtype != CRB_F64)
+        return fail(CRB_EUNSUPPORTED, who + ": the implicit stepper needs an fp64 plan (the iteration matrix is too ill-conditioned for fp32)");
+    if (p->NT > 256) return fail(CRB_EUNSUPPORTED, who + ": beams of more than 256 thread-carried nodes are not supported");
+    if (p->mixed_topology)
+        return fail(CRB_EUNSUPPORTED, who + ": one gain matrix for the ensemble needs one free-DOF set (uniform boundary conditions / lengths)");
+    if (int rc = need_device(p, who.c_str())) return rc;
+    if (t_end) *t_end = clock_after(t0, h, n_steps);
+    if (n_steps == 0) return CRB_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (implicit_feedback_in_kernel(p)) return implicit_feedback_fused(p, x, t0, h, n_steps, n_iter, hold, gain, ref, f, r, u_out, st);
+    return implicit_feedback_chain(p, x, t0, h, n_steps, n_iter, hold, gain, ref, f, r, u_out, work, st);
 }
 
 namespace {

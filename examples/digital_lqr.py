@@ -6,7 +6,9 @@ x_{k+1} = Phi_h(x_k, u_k) that one implicit step of h = 1e-3 s applies with u_k 
 that map's Jacobians (A_d, B_d) -- two launches of the implicit stepper's tangent with identity seeds -- and
 scipy.linalg.solve_discrete_are designs the gain on them.  The loop u_k = -K x_k then runs for B rods under different tip
 impulses, one `step_implicit(1, h, n_iter=1, held_force=u_k)` per sample.  (No gravity or drag here: x = 0 is the equilibrium
-the regulator holds, and the open loop of the undamped rod rings on.)
+the regulator holds, and the open loop of the undamped rod rings on.)  The same loop then runs in ONE call,
+`step_implicit_feedback(samples, h, K, hold=1, n_iter=1)`: the controller samples and holds inside the native call, and the time
+per sample of both and the largest difference between their tip traces are printed.
 
     python examples/digital_lqr.py [--elements 6] [--beams 64] [--t-final 1.0]
 """
@@ -62,10 +64,24 @@ def main(argv=None):
         wall = time.perf_counter() - t0
         rows.append((label, float(tip[-tail:].abs().max()), float(tip.abs().max()), wall / samples))
 
+    # the same digital loop in one native call: the zero-order-hold controller inside the implicit stepper
+    ens.zero_state()
+    ens.step_implicit_feedback(min(samples, 10), H, K_dev, hold=1, n_iter=1, impulse_amp=amps)          # (warm-up)
+    ens.zero_state()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    _, trace = ens.step_implicit_feedback(samples, H, K_dev, hold=1, n_iter=1, impulse_amp=amps, record=(ens.n_elem, "w"))
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t0
+    rows.append((f"one call ({ens.implicit_feedback_path()})", float(trace[:, -tail:].abs().max()), float(trace.abs().max()),
+                 wall / samples))
+    differ = float((trace.T - tip).abs().max())                      # (tip: the host loop's closed-loop trace)
+
     print(f"{args.beams} rods x {args.elements} linear elements, {samples} samples of {H:g} s, impulses {amps[0]:.1f} .. {amps[-1]:.1f} N")
     print(f"spectral radius: A_d {radius(A_d):.6f}, A_d - B_d K {radius(A_d - B_d @ K):.6f}")
     for label, late, peak, per in rows:
-        print(f"{label:<12} tip |w| over the last {tail} samples: {late:.3e} m   (peak {peak:.3e} m)   {per * 1e6:.0f} us per sample")
+        print(f"{label:<20} tip |w| over the last {tail} samples: {late:.3e} m   (peak {peak:.3e} m)   {per * 1e6:.0f} us per sample")
+    print(f"largest difference between the tip traces of the host loop and the one call: {differ:.3e} m")
     return rows, radius(A_d - B_d @ K)
 
 

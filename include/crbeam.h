@@ -722,6 +722,38 @@ int crb_step_implicit_tangent_sched(const crb_plan* plan, void* x, void* dx, int
                                     int n_iter, const crb_input_desc* input, const crb_input_tangent* dinput,
                                     const crb_input_schedule* sched, const void* d_sched, double* t_end, void* stream);
 
+/* ---- Sampled-data state feedback inside the implicit stepper: a digital (zero-order-hold) controller on the stiff loop.
+ * n_steps implicit-midpoint steps of size h; sample k covers steps k * hold ... (k + 1) * hold - 1 (the last sample may be cut
+ * short by n_steps).  At the top of a sample's first step e = r - x is formed from the state as it stands (reduced ordering),
+ * u_k = f_held + K e becomes the held input of the sample and the starting iterate is reset to 0; the impulse is added on top
+ * as in every implicit call.  The call IS the chain of one crb_step_implicit call per sample with f_held = u_k.  u_k is
+ * constant over a step, so the iteration matrix A = M + h^2/4 K0 is the open loop's: the feedback adds no stiffness (inside
+ * the RK4 stages, crb_step_rk4_feedback, the LQR loop needs dt <= 8.6e-6 s).
+ *   gain    device [n][2n] row-major, reduced ordering (as crb_step_rk4_feedback); one gain for the ensemble
+ *   ref     device [B][2n] reduced ordering, or NULL (= 0)
+ *   input   impulse and f_held [B][n_node][4] as in crb_step_implicit; rec as there, its stride `every` a divisor or a
+ *           multiple of hold
+ *   u_out   device [ceil(n_steps / hold)][B][n_node][4] or NULL: the total held input u_k of every sample in the layout of a
+ *           crb_input_schedule's records (zeros at constrained DOFs) -- crb_step_implicit_sched with f_sched = u_out and this
+ *           hold replays the call bitwise wherever it runs the general implicit kernel
+ *   work    device, crb_implicit_feedback_work_bytes(plan) bytes (never NULL)
+ * Two forms, the same map (they differ by the rounding of K e, whose summation order differs):
+ *   in-kernel (crb_implicit_feedback_path = 1): beams that live in one wave and whose gain fits LDS (up to ~30 elements) -- the
+ *           whole call is ONE launch, the product in LDS or on the matrix cores (gains of 21 ... 32 rows)
+ *   chain (0): everything else -- per sample one ensemble GEMM (crb_feedback_force) and one crb_step_implicit launch, issued
+ *           inside this call.  CRB_IMPLICIT_FEEDBACK=0 forces this form, =1 the in-kernel form wherever the gain fits.
+ * A beam that goes non-finite is marked (crb_plan_set_status) with the ensemble's step count at the end of the call.
+ * Refusals, all before the device is touched, crb_last_error() naming the entry point, in this order: CRB_EINVAL for a NULL
+ * plan, x, gain or work, n_steps < 0, h <= 0, n_iter < 1, hold < 1, a bad record or a record stride that neither divides hold
+ * nor is a multiple of it, a bad input description; then CRB_EUNSUPPORTED for fp32 plans, beams of more than 256 thread-carried
+ * nodes, ensembles of mixed topology or per-beam free-DOF sets; then CRB_ENODEV for host-only plans.  n_steps == 0 sets *t_end
+ * and returns CRB_OK.  Not covered: per-beam gain groups, the damped variant, the adjoint of this map. */
+int crb_step_implicit_feedback(const crb_plan* plan, void* x, double t0, double h, int n_steps, int n_iter, int hold,
+                               const void* gain, const void* ref, const crb_input_desc* input, const crb_record_desc* rec,
+                               void* u_out, void* work, double* t_end, void* stream);
+size_t crb_implicit_feedback_work_bytes(const crb_plan* plan);
+int crb_implicit_feedback_path(const crb_plan* plan);   /* 0 chain, 1 in-kernel */
+
 /* out[b] = x[b][plane][node][dof]  (e.g. tip displacement = plane 0, node n_elem, dof 1;
  * lqr_control.py:168) */
 int crb_gather_dof(const crb_plan* plan, const void* x, int plane, int node, int dof, void* out, void* stream);

@@ -898,80 +898,65 @@ class BeamEnsemble:
         (crb_rk4_adjoint_params_work_bytes) is sized instead; ``feedback_cotangents``: that of a ``step_feedback_adjoint`` call
         (crb_rk4_feedback_adjoint_work_bytes); ``implicit`` = (n_iter, n_cot): that of a ``step_implicit_adjoint`` call
         (crb_implicit_adjoint_work_bytes)."""
+        if checkpoint_every is not None:   # (given: no family's work buffer is sized)
+            return self._interval(None, n_steps, checkpoint_every, (), 1)
+        if implicit is not None:
+            if param_cotangents is not None or feedback_cotangents is not None:
+                raise ValueError("checkpoint_interval: implicit and param_cotangents / feedback_cotangents are given together")
+            return self._interval(_IMPLICIT, n_steps, None, (None, implicit[0]), implicit[1])
+        if feedback_cotangents is not None:
+            if param_cotangents is not None:
+                raise ValueError("checkpoint_interval: param_cotangents and feedback_cotangents are given together")
+            return self._interval(_FEEDBACK, n_steps, None, (), feedback_cotangents)
+        if param_cotangents is not None:
+            return self._interval(_RK4_PARAMS, n_steps, None, (), param_cotangents)
+        return self._interval(_RK4, n_steps, None, (), 1)
+
+    def _interval(self, fam, n_steps, checkpoint_every, step, n_cot):
+        """checkpoint_interval for the adjoint family ``fam`` (_AdjointFamily) with its step arguments and ``n_cot`` cotangents"""
         if checkpoint_every is not None:
             if int(checkpoint_every) < 1:
                 raise ValueError("checkpoint_every must be >= 1")
             return int(checkpoint_every)
         every = max(1, int(np.ceil(np.sqrt(max(int(n_steps), 1)))))
-        if implicit is not None:
-            if param_cotangents is not None or feedback_cotangents is not None:
-                raise ValueError("checkpoint_interval: implicit and param_cotangents / feedback_cotangents are given together")
-            work_bytes = lambda e: self._lib.crb_implicit_adjoint_work_bytes(self.plan.h, e, int(implicit[0]), int(implicit[1]))  # noqa: E731
-        elif feedback_cotangents is not None:
-            if param_cotangents is not None:
-                raise ValueError("checkpoint_interval: param_cotangents and feedback_cotangents are given together")
-            work_bytes = lambda e: self._lib.crb_rk4_feedback_adjoint_work_bytes(self.plan.h, e, int(feedback_cotangents))  # noqa: E731
-        elif param_cotangents is None:
-            work_bytes = lambda e: self._lib.crb_rk4_adjoint_work_bytes(self.plan.h, e)  # noqa: E731
-        else:
-            work_bytes = lambda e: self._lib.crb_rk4_adjoint_params_work_bytes(self.plan.h, e, int(param_cotangents))  # noqa: E731
-        while every > 1 and work_bytes(every) > self.ADJOINT_WORK_BUDGET:
+        while every > 1 and fam.work_bytes(self, every, step, int(n_cot)) > self.ADJOINT_WORK_BUDGET:
             every -= 1
         return every
 
-    def _checkpoint(self, x, n_steps, dt, t0, desc, every, rec, sd=None):
-        """crb_step_rk4_checkpoint (with the crb_input_schedule ``sd``: crb_step_rk4_checkpoint_sched) on the device state
-        ``x`` (advanced in place): returns the checkpoint buffer"""
+    def _work_buffer(self, fam, every, step, n_cot):
+        """the device work buffer of ``fam``'s checkpoint pass or sweep: its work-bytes call in whole doubles, never empty"""
+        nbytes = int(fam.work_bytes(self, int(every), step, int(n_cot)))
+        return torch.empty((max(1, nbytes) + 7) // 8, dtype=torch.float64, device=self.device)
+
+    def _checkpoint_pass(self, fam, x, n_steps, t0, step, desc, every, rec, sd=None):
+        """``fam``'s checkpoint call (with the crb_input_schedule ``sd``: its *_sched form) on the device state ``x``
+        (advanced in place): returns the checkpoint buffer, [n_seg] of ``fam.ckpt_shape``"""
         nseg = max(1, -(-int(n_steps) // every))
-        ckpt = torch.empty((nseg,) + tuple(self.state.shape), dtype=self.dtype, device=self.device)
+        ckpt = torch.empty((nseg,) + fam.ckpt_shape(self), dtype=self.dtype, device=self.device)
         t_end = C.c_double(0.0)
         with self._on_device():
-            nat.check(self._lib.crb_step_rk4_checkpoint_sched(self.plan.h, self._ptr(x), float(t0), float(dt), int(n_steps),
-                                                              int(every), C.byref(desc), self._ref(sd), self._ref(rec),
-                                                              self._ptr(ckpt), C.byref(t_end), self._stream()))
+            rc, held = fam.checkpoint(self, x, ckpt, int(n_steps), int(every), float(t0), step, desc, sd, rec, t_end)
+            nat.check(rc)
+        # The lifetime rule of the adjoint calls: a device buffer that an enqueued launch reads or writes stays referenced
+        # from _keep until a later call replaces the list.  The pass and the sweep each start a new list with what they
+        # allocated or were handed (``held``: the pass's own work buffer; ``step`` holds the closed loop's gain and
+        # reference); their callers append the rest -- input descriptions, packed schedules, record buffers -- right after.
+        # Replacing the list releases the previous call's buffers while its launches may still be queued: that relies on every
+        # call running on torch's current stream, on which the caching allocator hands freed memory out in stream order.
+        self._keep = [held, step, x]
         return ckpt
 
-    def _adjoint(self, ckpt, lamd, n_steps, dt, t0, desc, every, rec_bar, want_amp, want_params=False, sd=None):
-        """crb_step_rk4_adjoint: lamd [D, B, 2, n_node, 4] in place; returns (amp_bar [D, B] or None, f_bar [D, B, n_node, 4]).
-        ``want_params``: crb_step_rk4_adjoint_params instead, and a third return param_bar [D, B, n_node, 8].
-        ``sd``: the crb_input_schedule of the forward pass -- the *_sched calls, and f_bar is the schedule's cotangent
-        [D, K, B, n_node, 4]."""
+    def _sweep(self, fam, ckpt, lamd, n_steps, t0, step, desc, every, rec_bar, want, sd=None):
+        """``fam``'s backward sweep over the checkpoints, lamd [D, B, 2, n_node, 4] in place: returns the cotangent buffers
+        ``fam.outputs`` allocated (``want``: whether the optional first one is asked for).  ``sd``: the crb_input_schedule of
+        the forward pass -- the *_sched call, and the force cotangent is the schedule's, [D, K, B, n_node, 4]."""
         D = lamd.shape[0]
-        grad = nat.InputCotangent()
-        amp_bar = torch.zeros((D, self.n_beams), dtype=self.dtype, device=self.device) if want_amp else None
-        f_bar = torch.zeros((D,) + (() if sd is None else (int(sd.n_intervals),)) + (self.n_beams, self.n_node, 4),
-                            dtype=self.dtype, device=self.device)
-        grad.amp_bar = amp_bar.data_ptr() if amp_bar is not None else None
-        grad.f_held_bar = f_bar.data_ptr() if sd is None else None
-        if want_params:
-            return self._adjoint_params(ckpt, lamd, n_steps, dt, t0, desc, every, rec_bar, grad, amp_bar, f_bar, sd)
-        work = torch.empty((max(1, int(self._lib.crb_rk4_adjoint_work_bytes(self.plan.h, every))) + 7) // 8,
-                           dtype=torch.float64, device=self.device)
-        with self._on_device():   # (f_bar is grad.f_held_bar without a schedule, sched_bar with one)
-            nat.check(self._lib.crb_step_rk4_adjoint_sched(self.plan.h, self._ptr(ckpt), self._ptr(lamd), int(D), float(t0),
-                                                           float(dt), int(n_steps), int(every), C.byref(desc), self._ref(rec_bar),
-                                                           C.byref(grad), self._ref(sd), self._ptr(f_bar if sd is not None else None),
-                                                           self._ptr(work), self._stream()))
-        self._keep = [work, ckpt, lamd, amp_bar, f_bar]
-        return amp_bar, f_bar
-
-    def _adjoint_params(self, ckpt, lamd, n_steps, dt, t0, desc, every, rec_bar, grad, amp_bar, f_bar, sd=None):
-        """crb_step_rk4_adjoint_params (with ``sd``: ..._sched) on _adjoint's buffers: returns (amp_bar, f_bar, param_bar
-        [D, B, n_node, 8])"""
-        D = lamd.shape[0]
-        pgrad = nat.ParamCotangent()
-        param_bar = torch.zeros((D, self.n_beams, self.n_node, 8), dtype=self.dtype, device=self.device)
-        pgrad.param_bar = param_bar.data_ptr()
-        work = torch.empty((max(1, int(self._lib.crb_rk4_adjoint_params_work_bytes(self.plan.h, every, int(D)))) + 7) // 8,
-                           dtype=torch.float64, device=self.device)
+        outs = fam.outputs(self, D, want, sd)
+        work = self._work_buffer(fam, every, step, D)
         with self._on_device():
-            nat.check(self._lib.crb_step_rk4_adjoint_params_sched(self.plan.h, self._ptr(ckpt), self._ptr(lamd), int(D),
-                                                                  float(t0), float(dt), int(n_steps), int(every), C.byref(desc),
-                                                                  self._ref(rec_bar), C.byref(grad), C.byref(pgrad),
-                                                                  self._ref(sd), self._ptr(f_bar if sd is not None else None),
-                                                                  self._ptr(work), self._stream()))
-        self._keep = [work, ckpt, lamd, amp_bar, f_bar, param_bar]
-        return amp_bar, f_bar, param_bar
+            nat.check(fam.sweep(self, ckpt, lamd, int(n_steps), int(every), float(t0), step, desc, sd, rec_bar, outs, work))
+        self._keep = [work, ckpt, lamd, step, outs]   # (the lifetime rule: _checkpoint_pass)
+        return outs
 
     def _param_columns(self):
         """Per-beam parameter columns padded to [B, n_elem] (1 past a beam's own elements, so that divisions stay finite
@@ -1048,8 +1033,8 @@ class BeamEnsemble:
         return is then dL/d control, [K, B, n] ([D, K, B, n]); intervals the rollout does not reach, and entries past a beam's
         own DOF count in mixed-topology ensembles, are zero.
         ``step_adjoint_params`` also gives the gradient with respect to the rod's own parameters."""
-        return self._step_adjoint(False, n_steps, dt, lam_red, x0_red, impulse_amp, impulse_duration, impulse_index, held_force,
-                                  t0, record, record_every, lam_record, checkpoint_every)
+        return self._rollout_adjoint(_RK4, n_steps, (dt, None, None), lam_red, x0_red, impulse_amp, impulse_duration,
+                                     impulse_index, held_force, t0, record, record_every, lam_record, checkpoint_every)
 
     def step_adjoint_params(self, n_steps: int, dt: float, lam_red, x0_red=None, impulse_amp=None,
                             impulse_duration: float = 0.01, impulse_index: int = -2, held_force=None,
@@ -1071,31 +1056,30 @@ class BeamEnsemble:
         Entries past a beam's own element / node count (mixed-topology ensembles) are zero.  Not available: gradients with
         respect to length, cross_area and density (they enter the mass matrix and its reduction tables), parameters as
         autograd inputs of ``rollout`` (its forward would need parameter overrides)."""
-        return self._step_adjoint(True, n_steps, dt, lam_red, x0_red, impulse_amp, impulse_duration, impulse_index, held_force,
-                                  t0, record, record_every, lam_record, checkpoint_every, control, control_hold)
+        return self._rollout_adjoint(_RK4_PARAMS, n_steps, (dt, control, control_hold), lam_red, x0_red, impulse_amp,
+                                     impulse_duration, impulse_index, held_force, t0, record, record_every, lam_record,
+                                     checkpoint_every)
 
-    def _step_adjoint(self, param_grads, n_steps, dt, lam_red, x0_red, impulse_amp, impulse_duration, impulse_index, held_force,
-                      t0, record, record_every, lam_record, checkpoint_every, control=None, control_hold=None):
-        lam, single = self._dirs(lam_red, 2 * self.n, "step_adjoint: lam_red")
+    def _rollout_adjoint(self, fam, n_steps, args, lam_red, x0_red, impulse_amp, impulse_duration, impulse_index, held_force, t0,
+                         record, record_every, lam_record, checkpoint_every):
+        """The body step_adjoint, step_adjoint_params, step_implicit_adjoint and step_feedback_adjoint share: the checkpoint
+        pass and the backward sweep of the adjoint family ``fam`` (_AdjointFamily), whose ``prepare`` turns the caller's own
+        arguments ``args`` into the step arguments, and the cotangents in the shape of ``lam_red``."""
+        lam, single = self._dirs(lam_red, 2 * self.n, f"{fam.who}: lam_red")
         D = lam.shape[0]
-        held_force, sch = self._control(held_force, control, control_hold, n_steps, "step_adjoint")
+        step, held_force, sch, want = fam.prepare(self, n_steps, args, held_force, impulse_amp, record)
         t0 = self.time if t0 is None else float(t0)
-        every = self.checkpoint_interval(n_steps, checkpoint_every, D if param_grads else None)
+        every = self._interval(fam, n_steps, checkpoint_every, step, D)
         desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index, held_force)
         sd, packed = self._sched_desc(sch)
         x = self.state.clone() if x0_red is None else self.pack_state(x0_red)
-        ckpt = self._checkpoint(x, n_steps, dt, t0, desc, every, None, sd)
+        ckpt = self._checkpoint_pass(fam, x, n_steps, t0, step, desc, every, None, sd)
         rec_bar, cot = self._record_cotangent(record, n_steps, record_every, lam_record, D)
         lamd = self._pack_dirs(lam, True)
-        res = self._adjoint(ckpt, lamd, n_steps, dt, t0, desc, every, rec_bar, impulse_amp is not None, param_grads, sd)
-        amp_bar, f_bar = res[0], res[1]
+        outs = self._sweep(fam, ckpt, lamd, n_steps, t0, step, desc, every, rec_bar, want, sd)
         self._keep += keep + [x, cot, packed]
-        xb, fb = self._unpack_dirs(lamd), (self._unpack_force_dirs(f_bar) if sd is None else self._unpack_sched_dirs(f_bar))
-        out = (xb[0], (amp_bar[0] if amp_bar is not None else None), fb[0]) if single else (xb, amp_bar, fb)
-        if param_grads:
-            pd = self._param_dict(res[2])
-            out += ({k: v[0] for k, v in pd.items()} if single else pd,)
-        return out
+        res = (self._unpack_dirs(lamd),) + fam.unpack(self, outs, sd)
+        return tuple(_first(v) for v in res) if single else res
 
     def rollout(self, x0_red, n_steps: int, dt: float, impulse_amp=None, held_force=None, impulse_duration: float = 0.01,
                 impulse_index: int = -2, t0: float = 0.0, record=None, record_every: int = 1,
@@ -1111,49 +1095,13 @@ class BeamEnsemble:
         held_force, sch = self._control(held_force, control, control_hold, n_steps, "rollout")
         held = None if held_force is None else torch.as_tensor(held_force, dtype=self.dtype, device=self.device)
         ctrl, hold = (None, None) if sch is None else sch
-        opts = dict(n_steps=int(n_steps), dt=float(dt), t0=float(t0), duration=float(impulse_duration),
+        opts = dict(n_steps=int(n_steps), step=(float(dt),), t0=float(t0), duration=float(impulse_duration),
                     index=int(impulse_index), record=record, record_every=int(record_every),
                     every=self.checkpoint_interval(n_steps, checkpoint_every), hold=hold)
-        xT, samples = _Rollout.apply(self, opts, x0, amp, held, ctrl)
+        xT, samples = _Rollout.apply(self, _RK4, opts, x0, amp, held, ctrl)
         return (xT, samples) if record is not None else xT
 
     # ------------------------------------------------------------------ adjoint of the implicit stepper (crb_implicit_adjoint.h)
-    def _implicit_checkpoint(self, x, n_steps, h, n_iter, t0, desc, every, rec, sd=None):
-        """crb_step_implicit_checkpoint (with the crb_input_schedule ``sd``: crb_step_implicit_checkpoint_sched) on the device
-        state ``x`` (advanced in place): returns the checkpoint buffer [n_seg, B, 3, n_node, 4] (q, v and the starting iterate
-        of each segment's first step)"""
-        nseg = max(1, -(-int(n_steps) // every))
-        ckpt = torch.empty((nseg, self.n_beams, 3, self.n_node, 4), dtype=self.dtype, device=self.device)
-        t_end = C.c_double(0.0)
-        with self._on_device():
-            nat.check(self._lib.crb_step_implicit_checkpoint_sched(self.plan.h, self._ptr(x), float(t0), float(h), int(n_steps),
-                                                                   int(n_iter), int(every), C.byref(desc), self._ref(sd),
-                                                                   self._ref(rec), self._ptr(ckpt), C.byref(t_end),
-                                                                   self._stream()))
-        return ckpt
-
-    def _implicit_adjoint(self, ckpt, lamd, n_steps, h, n_iter, t0, desc, every, rec_bar, want_amp, sd=None):
-        """crb_step_implicit_adjoint: lamd [D, B, 2, n_node, 4] in place; returns (amp_bar [D, B] or None,
-        f_bar [D, B, n_node, 4]).  ``sd``: the crb_input_schedule of the forward pass -- crb_step_implicit_adjoint_sched, and
-        f_bar is the schedule's cotangent [D, K, B, n_node, 4]."""
-        D = lamd.shape[0]
-        grad = nat.InputCotangent()
-        amp_bar = torch.zeros((D, self.n_beams), dtype=self.dtype, device=self.device) if want_amp else None
-        f_bar = torch.zeros((D,) + (() if sd is None else (int(sd.n_intervals),)) + (self.n_beams, self.n_node, 4),
-                            dtype=self.dtype, device=self.device)
-        grad.amp_bar = amp_bar.data_ptr() if amp_bar is not None else None
-        grad.f_held_bar = f_bar.data_ptr() if sd is None else None
-        nbytes = int(self._lib.crb_implicit_adjoint_work_bytes(self.plan.h, int(every), int(n_iter), int(D)))
-        work = torch.empty((max(1, nbytes) + 7) // 8, dtype=torch.float64, device=self.device)
-        with self._on_device():   # (f_bar is grad.f_held_bar without a schedule, sched_bar with one)
-            nat.check(self._lib.crb_step_implicit_adjoint_sched(self.plan.h, self._ptr(ckpt), self._ptr(lamd), int(D), float(t0),
-                                                                float(h), int(n_steps), int(n_iter), int(every), C.byref(desc),
-                                                                self._ref(rec_bar), C.byref(grad), self._ref(sd),
-                                                                self._ptr(f_bar if sd is not None else None), self._ptr(work),
-                                                                self._stream()))
-        self._keep = [work, ckpt, lamd, amp_bar, f_bar]
-        return amp_bar, f_bar
-
     def step_implicit_adjoint(self, n_steps: int, h: float, lam_red, n_iter: int = 2, x0_red=None, impulse_amp=None,
                               impulse_duration: float = 0.01, impulse_index: int = -2, held_force=None,
                               t0: Optional[float] = None, record=None, record_every: int = 1, lam_record=None,
@@ -1173,22 +1121,8 @@ class BeamEnsemble:
         starts its iteration from 0 and the cotangent carried through the starting iterate is dropped there.
         Not available: the damped variant (``rho_inf`` < 1), the closed loop, and gradients with respect to the rod's own
         parameters (E and I enter the iteration matrix)."""
-        lam, single = self._dirs(lam_red, 2 * self.n, "step_implicit_adjoint: lam_red")
-        D = lam.shape[0]
-        held_force, sch = self._control(held_force, None, None, n_steps, "step_implicit_adjoint", "implicit steps")
-        t0 = self.time if t0 is None else float(t0)
-        every = self.checkpoint_interval(n_steps, checkpoint_every, implicit=(n_iter, D))
-        desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index, held_force)
-        sd, packed = self._sched_desc(sch)
-        x = self.state.clone() if x0_red is None else self.pack_state(x0_red)
-        ckpt = self._implicit_checkpoint(x, n_steps, h, n_iter, t0, desc, every, None, sd)
-        rec_bar, cot = self._record_cotangent(record, n_steps, record_every, lam_record, D)
-        lamd = self._pack_dirs(lam, True)
-        amp_bar, f_bar = self._implicit_adjoint(ckpt, lamd, n_steps, h, n_iter, t0, desc, every, rec_bar, impulse_amp is not None,
-                                                sd)
-        self._keep += keep + [x, cot, packed]
-        xb, fb = self._unpack_dirs(lamd), (self._unpack_force_dirs(f_bar) if sd is None else self._unpack_sched_dirs(f_bar))
-        return (xb[0], (amp_bar[0] if amp_bar is not None else None), fb[0]) if single else (xb, amp_bar, fb)
+        return self._rollout_adjoint(_IMPLICIT, n_steps, (h, n_iter), lam_red, x0_red, impulse_amp, impulse_duration,
+                                     impulse_index, held_force, t0, record, record_every, lam_record, checkpoint_every)
 
     def rollout_implicit(self, x0_red, n_steps: int, h: float, n_iter: int = 2, impulse_amp=None, held_force=None,
                          impulse_duration: float = 0.01, impulse_index: int = -2, t0: float = 0.0, record=None,
@@ -1207,10 +1141,10 @@ class BeamEnsemble:
         held_force, sch = self._control(held_force, control, control_hold, n_steps, "rollout_implicit", "implicit steps")
         held = None if held_force is None else torch.as_tensor(held_force, dtype=self.dtype, device=self.device)
         ctrl, hold = (None, None) if sch is None else sch
-        opts = dict(n_steps=int(n_steps), h=float(h), n_iter=int(n_iter), t0=float(t0), duration=float(impulse_duration),
+        opts = dict(n_steps=int(n_steps), step=(float(h), int(n_iter)), t0=float(t0), duration=float(impulse_duration),
                     index=int(impulse_index), record=record, record_every=int(record_every),
                     every=self.checkpoint_interval(n_steps, checkpoint_every, implicit=(n_iter, 1)), hold=hold)
-        xT, samples = _ImplicitRollout.apply(self, opts, x0, amp, held, ctrl)
+        xT, samples = _Rollout.apply(self, _IMPLICIT, opts, x0, amp, held, ctrl)
         return (xT, samples) if record is not None else xT
 
     # ------------------------------------------------------------------ adjoint of the closed loop (crb_feedback_adjoint.h)
@@ -1220,42 +1154,6 @@ class BeamEnsemble:
             raise NotImplementedError(f"{who}: a list of gains (per-beam or grouped gains) is not differentiable; pass one "
                                       f"[{self.n}, {2 * self.n}] gain for the whole ensemble")
         return self._dev(gain.detach() if isinstance(gain, torch.Tensor) else gain, (self.n, 2 * self.n))
-
-    def _feedback_adjoint_work(self, every, n_cot):
-        nbytes = int(self._lib.crb_rk4_feedback_adjoint_work_bytes(self.plan.h, int(every), int(n_cot)))
-        return torch.empty((max(1, nbytes) + 7) // 8, dtype=torch.float64, device=self.device)
-
-    def _feedback_checkpoint(self, x, n_steps, dt, t0, K, ref, desc, every, rec):
-        """crb_step_rk4_feedback_checkpoint on the device state ``x`` (advanced in place): returns the checkpoint buffer"""
-        nseg = max(1, -(-int(n_steps) // every))
-        ckpt = torch.empty((nseg,) + tuple(self.state.shape), dtype=self.dtype, device=self.device)
-        work = self._feedback_adjoint_work(every, 1)
-        t_end = C.c_double(0.0)
-        with self._on_device():
-            nat.check(self._lib.crb_step_rk4_feedback_checkpoint(self.plan.h, self._ptr(x), float(t0), float(dt), int(n_steps),
-                                                                 int(every), self._ptr(K), self._ptr(ref), C.byref(desc),
-                                                                 self._ref(rec), self._ptr(ckpt), self._ptr(work),
-                                                                 C.byref(t_end), self._stream()))
-        self._keep = [work, K, ref, x]
-        return ckpt
-
-    def _feedback_adjoint(self, ckpt, lamd, n_steps, dt, t0, K, ref, desc, every, rec_bar, want_gain=True):
-        """crb_step_rk4_feedback_adjoint: lamd [D, B, 2, n_node, 4] in place; returns (gain_bar [D, n, 2n] or None,
-        ref_bar [D, B, 2n])"""
-        D = lamd.shape[0]
-        grad = nat.FeedbackCotangent()
-        gain_bar = torch.zeros((D, self.n, 2 * self.n), dtype=self.dtype, device=self.device) if want_gain else None
-        ref_bar = torch.zeros((D, self.n_beams, 2 * self.n), dtype=self.dtype, device=self.device)
-        grad.gain_bar = gain_bar.data_ptr() if gain_bar is not None else None
-        grad.ref_bar = ref_bar.data_ptr()
-        work = self._feedback_adjoint_work(every, D)
-        with self._on_device():
-            nat.check(self._lib.crb_step_rk4_feedback_adjoint(self.plan.h, self._ptr(ckpt), self._ptr(lamd), int(D), float(t0),
-                                                              float(dt), int(n_steps), int(every), self._ptr(K), self._ptr(ref),
-                                                              C.byref(desc), self._ref(rec_bar), C.byref(grad), self._ptr(work),
-                                                              self._stream()))
-        self._keep = [work, ckpt, lamd, K, ref, gain_bar, ref_bar]
-        return gain_bar, ref_bar
 
     def step_feedback_adjoint(self, n_steps: int, dt: float, lam_red, gain, reference=None, x0_red=None, impulse_amp=None,
                               impulse_duration: float = 0.01, impulse_index: int = -2, held_force=None,
@@ -1274,25 +1172,9 @@ class BeamEnsemble:
         skips the gain-gradient product (gain_bar is None; the other returns are bitwise the same).  A non-finite cotangent
         of one beam stays in that beam's rows of xbar0 and ref_bar but reaches gain_bar, a sum over the beams.  fp64
         ensembles with one free-DOF set only."""
-        lam, single = self._dirs(lam_red, 2 * self.n, "step_feedback_adjoint: lam_red")
-        D = lam.shape[0]
-        K = self._feedback_gain(gain, "step_feedback_adjoint")
-        ref = None if reference is None else self._dev(reference, (self.n_beams, 2 * self.n))
-        if record is not None and isinstance(record, str):
-            raise NotImplementedError("step_feedback_adjoint: whole-state snapshots (record='all') are not available in the closed loop")
-        t0 = self.time if t0 is None else float(t0)
-        every = self.checkpoint_interval(n_steps, checkpoint_every, feedback_cotangents=D)
-        desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index, held_force)
-        x = self.state.clone() if x0_red is None else self.pack_state(x0_red)
-        ckpt = self._feedback_checkpoint(x, n_steps, dt, t0, K, ref, desc, every, None)
-        rec_bar, cot = self._record_cotangent(record, n_steps, record_every, lam_record, D)
-        lamd = self._pack_dirs(lam, True)
-        gain_bar, ref_bar = self._feedback_adjoint(ckpt, lamd, n_steps, dt, t0, K, ref, desc, every, rec_bar, want_gain)
-        self._keep += keep + [x, cot]
-        xb = self._unpack_dirs(lamd)
-        if single:
-            return xb[0], (gain_bar[0] if gain_bar is not None else None), ref_bar[0]
-        return xb, gain_bar, ref_bar
+        return self._rollout_adjoint(_FEEDBACK, n_steps, (dt, gain, reference, want_gain), lam_red, x0_red, impulse_amp,
+                                     impulse_duration, impulse_index, held_force, t0, record, record_every, lam_record,
+                                     checkpoint_every)
 
     def rollout_feedback(self, x0_red, n_steps: int, dt: float, gain, reference=None, impulse_amp=None,
                          impulse_duration: float = 0.01, impulse_index: int = -2, held_force=None, t0: float = 0.0,
@@ -1946,26 +1828,193 @@ class BeamEnsemble:
         return self.state[rows, 0, nodes, 1].clone()
 
 
+class _AdjointFamily(NamedTuple):
+    """What differs between the checkpointed adjoints that BeamEnsemble._rollout_adjoint, _checkpoint_pass, _sweep and the
+    rollout Functions serve.  ``step`` is the family's own tuple of step arguments, opaque to the shared code; the callables
+    take the ensemble first."""
+    who: str              # the public method's name in error texts
+    prepare: object       # (ens, n_steps, args, held_force, impulse_amp, record) -> (step, held_force, schedule, want)
+    ckpt_shape: object    # (ens) -> the shape of one segment's checkpoint
+    work_bytes: object    # (ens, every, step, n_cot) -> the library's work-bytes call
+    checkpoint: object    # (ens, x, ckpt, n_steps, every, t0, step, desc, sd, rec, t_end) -> (return code, what it allocated)
+    outputs: object       # (ens, D, want, sd) -> the cotangent buffers of the sweep, the optional one (``want``) first
+    sweep: object         # (ens, ckpt, lamd, n_steps, every, t0, step, desc, sd, rec_bar, outs, work) -> return code
+    unpack: object        # (ens, outs, sd) -> the returns after xbar0, each with its leading D axis
+
+
+def _first(v):
+    """one return of _rollout_adjoint without its leading D axis (a dict of them entry by entry)"""
+    if isinstance(v, dict):
+        return {k: t[0] for k, t in v.items()}
+    return None if v is None else v[0]
+
+
+def _input_outputs(ens, D, want_amp, sd):
+    """[amp_bar [D, B] or None, f_bar [D, B, n_node, 4] -- with a schedule its cotangent, [D, K, B, n_node, 4]]"""
+    amp_bar = torch.zeros((D, ens.n_beams), dtype=ens.dtype, device=ens.device) if want_amp else None
+    f_bar = torch.zeros((D,) + (() if sd is None else (int(sd.n_intervals),)) + (ens.n_beams, ens.n_node, 4),
+                        dtype=ens.dtype, device=ens.device)
+    return [amp_bar, f_bar]
+
+
+def _input_cotangent(ens, outs, sd):
+    """(crb_input_cotangent, sched_bar) of _input_outputs: f_bar is grad.f_held_bar without a schedule, sched_bar with one"""
+    grad = nat.InputCotangent()
+    grad.amp_bar = outs[0].data_ptr() if outs[0] is not None else None
+    grad.f_held_bar = outs[1].data_ptr() if sd is None else None
+    return grad, ens._ptr(outs[1] if sd is not None else None)
+
+
+def _input_unpack(ens, outs, sd):
+    return outs[0], (ens._unpack_force_dirs(outs[1]) if sd is None else ens._unpack_sched_dirs(outs[1]))
+
+
+def _rk4_prepare(ens, n_steps, args, held_force, impulse_amp, record):
+    dt, control, control_hold = args
+    held_force, sch = ens._control(held_force, control, control_hold, n_steps, "step_adjoint")
+    return (dt,), held_force, sch, impulse_amp is not None
+
+
+def _rk4_checkpoint(ens, x, ckpt, n_steps, every, t0, step, desc, sd, rec, t_end):
+    return ens._lib.crb_step_rk4_checkpoint_sched(ens.plan.h, ens._ptr(x), t0, float(step[0]), n_steps, every, C.byref(desc),
+                                                  ens._ref(sd), ens._ref(rec), ens._ptr(ckpt), C.byref(t_end),
+                                                  ens._stream()), None
+
+
+def _rk4_sweep(ens, ckpt, lamd, n_steps, every, t0, step, desc, sd, rec_bar, outs, work):
+    grad, sched_bar = _input_cotangent(ens, outs, sd)
+    return ens._lib.crb_step_rk4_adjoint_sched(ens.plan.h, ens._ptr(ckpt), ens._ptr(lamd), int(lamd.shape[0]), t0,
+                                               float(step[0]), n_steps, every, C.byref(desc), ens._ref(rec_bar), C.byref(grad),
+                                               ens._ref(sd), sched_bar, ens._ptr(work), ens._stream())
+
+
+def _rk4_params_sweep(ens, ckpt, lamd, n_steps, every, t0, step, desc, sd, rec_bar, outs, work):
+    grad, sched_bar = _input_cotangent(ens, outs, sd)
+    pgrad = nat.ParamCotangent()
+    pgrad.param_bar = outs[2].data_ptr()
+    return ens._lib.crb_step_rk4_adjoint_params_sched(ens.plan.h, ens._ptr(ckpt), ens._ptr(lamd), int(lamd.shape[0]), t0,
+                                                      float(step[0]), n_steps, every, C.byref(desc), ens._ref(rec_bar),
+                                                      C.byref(grad), C.byref(pgrad), ens._ref(sd), sched_bar, ens._ptr(work),
+                                                      ens._stream())
+
+
+_RK4 = _AdjointFamily(
+    who="step_adjoint", prepare=_rk4_prepare, ckpt_shape=lambda ens: tuple(ens.state.shape),
+    work_bytes=lambda ens, every, step, n_cot: ens._lib.crb_rk4_adjoint_work_bytes(ens.plan.h, every),
+    checkpoint=_rk4_checkpoint, outputs=_input_outputs, sweep=_rk4_sweep, unpack=_input_unpack)
+
+# step_adjoint_params: the same pass, the storing sweep, and a third buffer param_bar [D, B, n_node, 8] returned as a dict
+_RK4_PARAMS = _RK4._replace(
+    work_bytes=lambda ens, every, step, n_cot: ens._lib.crb_rk4_adjoint_params_work_bytes(ens.plan.h, every, n_cot),
+    outputs=lambda ens, D, want_amp, sd: _input_outputs(ens, D, want_amp, sd) + [
+        torch.zeros((D, ens.n_beams, ens.n_node, 8), dtype=ens.dtype, device=ens.device)],
+    sweep=_rk4_params_sweep,
+    unpack=lambda ens, outs, sd: _input_unpack(ens, outs, sd) + (ens._param_dict(outs[2]),))
+
+
+def _implicit_prepare(ens, n_steps, args, held_force, impulse_amp, record):
+    held_force, sch = ens._control(held_force, None, None, n_steps, "step_implicit_adjoint", "implicit steps")
+    return args, held_force, sch, impulse_amp is not None
+
+
+def _implicit_checkpoint(ens, x, ckpt, n_steps, every, t0, step, desc, sd, rec, t_end):
+    return ens._lib.crb_step_implicit_checkpoint_sched(ens.plan.h, ens._ptr(x), t0, float(step[0]), n_steps, int(step[1]), every,
+                                                       C.byref(desc), ens._ref(sd), ens._ref(rec), ens._ptr(ckpt),
+                                                       C.byref(t_end), ens._stream()), None
+
+
+def _implicit_sweep(ens, ckpt, lamd, n_steps, every, t0, step, desc, sd, rec_bar, outs, work):
+    grad, sched_bar = _input_cotangent(ens, outs, sd)
+    return ens._lib.crb_step_implicit_adjoint_sched(ens.plan.h, ens._ptr(ckpt), ens._ptr(lamd), int(lamd.shape[0]), t0,
+                                                    float(step[0]), n_steps, int(step[1]), every, C.byref(desc),
+                                                    ens._ref(rec_bar), C.byref(grad), ens._ref(sd), sched_bar, ens._ptr(work),
+                                                    ens._stream())
+
+
+# step = (h, n_iter); a segment's checkpoint holds q, v and the starting iterate of its first step
+_IMPLICIT = _AdjointFamily(
+    who="step_implicit_adjoint", prepare=_implicit_prepare, ckpt_shape=lambda ens: (ens.n_beams, 3, ens.n_node, 4),
+    work_bytes=lambda ens, every, step, n_cot: ens._lib.crb_implicit_adjoint_work_bytes(ens.plan.h, every, int(step[1]), n_cot),
+    checkpoint=_implicit_checkpoint, outputs=_input_outputs, sweep=_implicit_sweep, unpack=_input_unpack)
+
+
+def _feedback_prepare(ens, n_steps, args, held_force, impulse_amp, record):
+    dt, gain, reference, want_gain = args
+    K = ens._feedback_gain(gain, "step_feedback_adjoint")
+    ref = None if reference is None else ens._dev(reference, (ens.n_beams, 2 * ens.n))
+    if record is not None and isinstance(record, str):
+        raise NotImplementedError("step_feedback_adjoint: whole-state snapshots (record='all') are not available in the closed loop")
+    return (dt, K, ref), held_force, None, want_gain
+
+
+def _feedback_checkpoint(ens, x, ckpt, n_steps, every, t0, step, desc, sd, rec, t_end):
+    dt, K, ref = step
+    work = ens._work_buffer(_FEEDBACK, every, step, 1)
+    return ens._lib.crb_step_rk4_feedback_checkpoint(ens.plan.h, ens._ptr(x), t0, float(dt), n_steps, every, ens._ptr(K),
+                                                     ens._ptr(ref), C.byref(desc), ens._ref(rec), ens._ptr(ckpt), ens._ptr(work),
+                                                     C.byref(t_end), ens._stream()), work
+
+
+def _feedback_outputs(ens, D, want_gain, sd):
+    """[gain_bar [D, n, 2n] or None, ref_bar [D, B, 2n]]"""
+    gain_bar = torch.zeros((D, ens.n, 2 * ens.n), dtype=ens.dtype, device=ens.device) if want_gain else None
+    return [gain_bar, torch.zeros((D, ens.n_beams, 2 * ens.n), dtype=ens.dtype, device=ens.device)]
+
+
+def _feedback_sweep(ens, ckpt, lamd, n_steps, every, t0, step, desc, sd, rec_bar, outs, work):
+    dt, K, ref = step
+    grad = nat.FeedbackCotangent()
+    grad.gain_bar = outs[0].data_ptr() if outs[0] is not None else None
+    grad.ref_bar = outs[1].data_ptr()
+    return ens._lib.crb_step_rk4_feedback_adjoint(ens.plan.h, ens._ptr(ckpt), ens._ptr(lamd), int(lamd.shape[0]), t0, float(dt),
+                                                  n_steps, every, ens._ptr(K), ens._ptr(ref), C.byref(desc), ens._ref(rec_bar),
+                                                  C.byref(grad), ens._ptr(work), ens._stream())
+
+
+# step = (dt, gain [n, 2n], reference [B, 2n] or None) on the device; the pass needs the work buffer of one cotangent
+_FEEDBACK = _AdjointFamily(
+    who="step_feedback_adjoint", prepare=_feedback_prepare, ckpt_shape=lambda ens: tuple(ens.state.shape),
+    work_bytes=lambda ens, every, step, n_cot: ens._lib.crb_rk4_feedback_adjoint_work_bytes(ens.plan.h, every, n_cot),
+    checkpoint=_feedback_checkpoint, outputs=_feedback_outputs, sweep=_feedback_sweep,
+    unpack=lambda ens, outs, sd: tuple(outs))
+
+
+def _rollout_result(ctx, ens, opts, x, samples):
+    """what a rollout's forward returns: x(T) reduced and the samples (without a record an empty placeholder that takes no
+    gradient)"""
+    if samples is None:
+        samples = torch.zeros(0, dtype=ens.dtype, device=ens.device)
+    if opts["record"] is None:
+        ctx.mark_non_differentiable(samples)
+    return ens.unpack_state(x), samples
+
+
+def _rollout_seed(ens, o, g_x, g_samples):
+    """the seeds of a rollout's backward from the output gradients (a missing g_x is zero): (lamd, rec_bar, cot)"""
+    g_x = torch.zeros((ens.n_beams, 2 * ens.n), dtype=ens.dtype, device=ens.device) if g_x is None else g_x
+    lamd = ens._pack_dirs(g_x.to(ens.dtype).reshape(1, ens.n_beams, 2 * ens.n).contiguous(), True)
+    rec_bar, cot = ens._record_cotangent(o["record"], o["n_steps"], o["record_every"],
+                                         g_samples if o["record"] is not None else None, 1)
+    return lamd, rec_bar, cot
+
+
 class _Rollout(torch.autograd.Function):
-    """BeamEnsemble.rollout: forward = crb_step_rk4_checkpoint, backward = crb_step_rk4_adjoint on the saved checkpoints"""
+    """BeamEnsemble.rollout (``fam`` = _RK4) and rollout_implicit (_IMPLICIT): forward = the family's checkpoint pass,
+    backward = its sweep on the saved checkpoints"""
 
     @staticmethod
-    def forward(ctx, ens, opts, x0, amp, held, ctrl):
+    def forward(ctx, ens, fam, opts, x0, amp, held, ctrl):
         desc, keep = ens._input_desc(None if amp is None else amp.detach(), opts["duration"], opts["index"],
                                      None if held is None else held.detach())
         sd, packed = ens._sched_desc(None if ctrl is None else (ctrl.detach(), opts["hold"]))
         x = ens.pack_state(x0.detach())
         rec, samples = ens._record_desc(opts["record"], opts["n_steps"], opts["record_every"])
-        ckpt = ens._checkpoint(x, opts["n_steps"], opts["dt"], opts["t0"], desc, opts["every"], rec, sd)
-        ens._keep = keep + [x, samples, packed]
-        ctx.ens, ctx.opts = ens, opts
+        ckpt = ens._checkpoint_pass(fam, x, opts["n_steps"], opts["t0"], opts["step"], desc, opts["every"], rec, sd)
+        ens._keep += keep + [samples, packed]
+        ctx.ens, ctx.fam, ctx.opts = ens, fam, opts
         ctx.has_amp, ctx.has_held, ctx.has_ctrl = amp is not None, held is not None, ctrl is not None
         ctx.save_for_backward(ckpt, None if amp is None else amp.detach(), None if held is None else held.detach(), packed)
-        if samples is None:
-            samples = torch.zeros(0, dtype=ens.dtype, device=ens.device)
-        if opts["record"] is None:
-            ctx.mark_non_differentiable(samples)
-        return ens.unpack_state(x), samples
+        return _rollout_result(ctx, ens, opts, x, samples)
 
     @staticmethod
     @once_differentiable
@@ -1974,61 +2023,15 @@ class _Rollout(torch.autograd.Function):
         ckpt, amp, held, packed = ctx.saved_tensors
         desc, keep = ens._input_desc(amp, o["duration"], o["index"], held)
         sd = nat.InputSchedule(packed.data_ptr(), int(packed.shape[0]), int(o["hold"])) if ctx.has_ctrl else None
-        g_x = torch.zeros((ens.n_beams, 2 * ens.n), dtype=ens.dtype, device=ens.device) if g_x is None else g_x
-        lamd = ens._pack_dirs(g_x.to(ens.dtype).reshape(1, ens.n_beams, 2 * ens.n).contiguous(), True)
-        rec_bar, cot = ens._record_cotangent(o["record"], o["n_steps"], o["record_every"],
-                                             g_samples if o["record"] is not None else None, 1)
-        amp_bar, f_bar = ens._adjoint(ckpt, lamd, o["n_steps"], o["dt"], o["t0"], desc, o["every"], rec_bar, ctx.has_amp,
-                                      False, sd)
+        lamd, rec_bar, cot = _rollout_seed(ens, o, g_x, g_samples)
+        amp_bar, f_bar = ens._sweep(ctx.fam, ckpt, lamd, o["n_steps"], o["t0"], o["step"], desc, o["every"], rec_bar,
+                                    ctx.has_amp, sd)
         ens._keep += keep + [cot, packed]
-        gx0 = ens._unpack_dirs(lamd)[0] if ctx.needs_input_grad[2] else None
-        gamp = amp_bar[0] if (ctx.has_amp and ctx.needs_input_grad[3]) else None
-        gheld = ens._unpack_force_dirs(f_bar)[0] if (ctx.has_held and ctx.needs_input_grad[4]) else None
-        gctrl = ens._unpack_sched_dirs(f_bar)[0] if (ctx.has_ctrl and ctx.needs_input_grad[5]) else None
-        return None, None, gx0, gamp, gheld, gctrl
-
-
-class _ImplicitRollout(torch.autograd.Function):
-    """BeamEnsemble.rollout_implicit: forward = crb_step_implicit_checkpoint(_sched), backward =
-    crb_step_implicit_adjoint(_sched) on the saved checkpoints"""
-
-    @staticmethod
-    def forward(ctx, ens, opts, x0, amp, held, ctrl):
-        desc, keep = ens._input_desc(None if amp is None else amp.detach(), opts["duration"], opts["index"],
-                                     None if held is None else held.detach())
-        sd, packed = ens._sched_desc(None if ctrl is None else (ctrl.detach(), opts["hold"]))
-        x = ens.pack_state(x0.detach())
-        rec, samples = ens._record_desc(opts["record"], opts["n_steps"], opts["record_every"])
-        ckpt = ens._implicit_checkpoint(x, opts["n_steps"], opts["h"], opts["n_iter"], opts["t0"], desc, opts["every"], rec, sd)
-        ens._keep = keep + [x, samples, packed]
-        ctx.ens, ctx.opts = ens, opts
-        ctx.has_amp, ctx.has_held, ctx.has_ctrl = amp is not None, held is not None, ctrl is not None
-        ctx.save_for_backward(ckpt, None if amp is None else amp.detach(), None if held is None else held.detach(), packed)
-        if samples is None:
-            samples = torch.zeros(0, dtype=ens.dtype, device=ens.device)
-        if opts["record"] is None:
-            ctx.mark_non_differentiable(samples)
-        return ens.unpack_state(x), samples
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g_x, g_samples):
-        ens, o = ctx.ens, ctx.opts
-        ckpt, amp, held, packed = ctx.saved_tensors
-        desc, keep = ens._input_desc(amp, o["duration"], o["index"], held)
-        sd = nat.InputSchedule(packed.data_ptr(), int(packed.shape[0]), int(o["hold"])) if ctx.has_ctrl else None
-        g_x = torch.zeros((ens.n_beams, 2 * ens.n), dtype=ens.dtype, device=ens.device) if g_x is None else g_x
-        lamd = ens._pack_dirs(g_x.to(ens.dtype).reshape(1, ens.n_beams, 2 * ens.n).contiguous(), True)
-        rec_bar, cot = ens._record_cotangent(o["record"], o["n_steps"], o["record_every"],
-                                             g_samples if o["record"] is not None else None, 1)
-        amp_bar, f_bar = ens._implicit_adjoint(ckpt, lamd, o["n_steps"], o["h"], o["n_iter"], o["t0"], desc, o["every"],
-                                               rec_bar, ctx.has_amp, sd)
-        ens._keep += keep + [cot, packed]
-        gx0 = ens._unpack_dirs(lamd)[0] if ctx.needs_input_grad[2] else None
-        gamp = amp_bar[0] if (ctx.has_amp and ctx.needs_input_grad[3]) else None
-        gheld = ens._unpack_force_dirs(f_bar)[0] if (ctx.has_held and ctx.needs_input_grad[4]) else None
-        gctrl = ens._unpack_sched_dirs(f_bar)[0] if (ctx.has_ctrl and ctx.needs_input_grad[5]) else None
-        return None, None, gx0, gamp, gheld, gctrl
+        gx0 = ens._unpack_dirs(lamd)[0] if ctx.needs_input_grad[3] else None
+        gamp = amp_bar[0] if (ctx.has_amp and ctx.needs_input_grad[4]) else None
+        gheld = ens._unpack_force_dirs(f_bar)[0] if (ctx.has_held and ctx.needs_input_grad[5]) else None
+        gctrl = ens._unpack_sched_dirs(f_bar)[0] if (ctx.has_ctrl and ctx.needs_input_grad[6]) else None
+        return None, None, None, gx0, gamp, gheld, gctrl
 
 
 class _FeedbackRollout(torch.autograd.Function):
@@ -2042,15 +2045,11 @@ class _FeedbackRollout(torch.autograd.Function):
         desc, keep = ens._input_desc(opts["amp"], opts["duration"], opts["index"], opts["held"])
         x = ens.pack_state(x0.detach())
         rec, samples = ens._record_desc(opts["record"], opts["n_steps"], opts["record_every"])
-        ckpt = ens._feedback_checkpoint(x, opts["n_steps"], opts["dt"], opts["t0"], K, r, desc, opts["every"], rec)
+        ckpt = ens._checkpoint_pass(_FEEDBACK, x, opts["n_steps"], opts["t0"], (opts["dt"], K, r), desc, opts["every"], rec)
         ens._keep += keep + [samples]
         ctx.ens, ctx.opts, ctx.has_ref = ens, opts, ref is not None
         ctx.save_for_backward(ckpt, K, r)
-        if samples is None:
-            samples = torch.zeros(0, dtype=ens.dtype, device=ens.device)
-        if opts["record"] is None:
-            ctx.mark_non_differentiable(samples)
-        return ens.unpack_state(x), samples
+        return _rollout_result(ctx, ens, opts, x, samples)
 
     @staticmethod
     @once_differentiable
@@ -2058,12 +2057,9 @@ class _FeedbackRollout(torch.autograd.Function):
         ens, o = ctx.ens, ctx.opts
         ckpt, K, r = ctx.saved_tensors
         desc, keep = ens._input_desc(o["amp"], o["duration"], o["index"], o["held"])
-        g_x = torch.zeros((ens.n_beams, 2 * ens.n), dtype=ens.dtype, device=ens.device) if g_x is None else g_x
-        lamd = ens._pack_dirs(g_x.to(ens.dtype).reshape(1, ens.n_beams, 2 * ens.n).contiguous(), True)
-        rec_bar, cot = ens._record_cotangent(o["record"], o["n_steps"], o["record_every"],
-                                             g_samples if o["record"] is not None else None, 1)
-        gain_bar, ref_bar = ens._feedback_adjoint(ckpt, lamd, o["n_steps"], o["dt"], o["t0"], K, r, desc, o["every"], rec_bar,
-                                                  ctx.needs_input_grad[3])
+        lamd, rec_bar, cot = _rollout_seed(ens, o, g_x, g_samples)
+        gain_bar, ref_bar = ens._sweep(_FEEDBACK, ckpt, lamd, o["n_steps"], o["t0"], (o["dt"], K, r), desc, o["every"], rec_bar,
+                                       ctx.needs_input_grad[3])
         ens._keep += keep + [cot]
         gx0 = ens._unpack_dirs(lamd)[0] if ctx.needs_input_grad[2] else None
         ggain = gain_bar[0] if ctx.needs_input_grad[3] else None

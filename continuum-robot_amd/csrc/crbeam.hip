@@ -151,6 +151,15 @@ extern "C" const char* crb_last_error(void) { return g_err.c_str(); }
 
 namespace {
 
+// a parameter block with every byte zero (padding too)
+template <typename P>
+P zeroed() { P q; std::memset(&q, 0, sizeof(q)); return q; }
+// thread blocks of a launch over the ensemble: G beams each
+int beam_groups(const crb_plan* p) { return (p->B + p->G - 1) / p->G; }
+// doubles (elements) of the device state [B][2][n_node][4] and of a force-shaped buffer [B][n_node][4]
+size_t state_doubles(const crb_plan* p) { return size_t(p->B) * 2 * size_t(p->n_node) * 4; }
+size_t force_doubles(const crb_plan* p) { return size_t(p->B) * size_t(p->n_node) * 4; }
+
 void mass_from_blocks(crb_plan* p, const std::vector<NodeBlocks>& blk) {
     const int n = int(p->free_index.size()), S = p->S;   // (beam 0's reduced size; n_free is the ensemble's maximum)
     p->h_mass.assign(size_t(n) * n, 0.0);
@@ -296,8 +305,7 @@ int device_assemble(crb_plan* p, const crb_beam_desc* descs, int nd, const std::
         p->fin_stride = size_t(S) * PCR_FINAL_VALS;
     }
 
-    AsmParams a;
-    std::memset(&a, 0, sizeof(a));
+    AsmParams a = zeroed<AsmParams>();
     a.L = dL.p; a.E = dE.p; a.I = dI.p; a.rho = dRho.p; a.A = dA.p;
     a.nonlinear = dNl.p; a.free_dof = dFree.p; a.wet = dWet.p; a.cd = dCd.p; a.grav = dGrav.p;
     a.fluid_density = d->fluid_density; a.flags = d->flags;
@@ -662,8 +670,7 @@ static int plan_create_impl(crb_plan** out, int device, int dtype, int n_beams, 
     std::vector<NodeBlocks> cur(S), nxt(S);
     auto fm = [&](int node, int c) { return node >= 0 && node < nn && free_dof[3 * node + c] != 0; };
     for (int j = 0; j < S; ++j) {
-        NodeBlocks nb;
-        std::memset(&nb, 0, sizeof(nb));
+        NodeBlocks nb = zeroed<NodeBlocks>();
         const int node = j + p->off;
         const int el = node - 1, er = node;
         if (el >= 0) mass_add_as_left_elem(nb, d->length[el], d->density[el] * d->cross_area[el], j >= 1);
@@ -904,8 +911,7 @@ int need_device(const crb_plan* p, const char* who) {
 
 template <typename T>
 KParams<T> base_params(const crb_plan* p) {
-    KParams<T> k;
-    std::memset(&k, 0, sizeof(k));
+    KParams<T> k = zeroed<KParams<T>>();
     k.slot = static_cast<const SlotConst<T>*>(p->d_slot);
     k.pcr_levels = static_cast<const T*>(p->d_levels);
     k.pcr_final = static_cast<const T*>(p->d_final);
@@ -1007,13 +1013,32 @@ double clock_after(double t0, double dt, int n_steps) {
     for (int i = 0; i < n_steps; ++i) t = t + dt;
     return t;
 }
-// the decoded forcing (and recording) in a launch's parameter block
+// body(g, k0, n, t) for checkpoint segment g of an adjoint rollout -- steps k0 .. k0 + n - 1 of the call, from the clock t the
+// checkpoint pass held at step k0 (the same additions) -- from the last segment down, until one returns non-zero
+template <typename F>
+int for_segments_reversed(int n_steps, int every, double t0, double dt, F&& body) {
+    for (int g = (n_steps + every - 1) / every - 1; g >= 0; --g) {
+        const int k0 = g * every, n = (n_steps - k0) < every ? (n_steps - k0) : every;
+        if (int rc = body(g, k0, n, clock_after(t0, dt, k0))) return rc;
+    }
+    return CRB_OK;
+}
+// the decoded recording, and the decoded forcing (and recording), in a launch's parameter block
+template <typename T>
+void set_record(KParams<T>& k, const Recording& r) {
+    k.rec_out = static_cast<T*>(r.out); k.rec_slot = r.slot; k.rec_comp = r.comp; k.rec_every = r.every; k.rec_n = r.count;
+}
 template <typename T>
 void set_io(KParams<T>& k, const Forcing& f, const Recording* r = nullptr) {
     k.u_held = static_cast<const T*>(f.held);
     k.amp = static_cast<const T*>(f.amp);
     k.imp_slot = f.slot; k.imp_dof = f.dof; k.duration = f.duration; k.imp_node_b = f.node_b;
-    if (r) { k.rec_out = static_cast<T*>(r->out); k.rec_slot = r->slot; k.rec_comp = r->comp; k.rec_every = r->every; k.rec_n = r->count; }
+    if (r) set_record(k, *r);
+}
+
+// the direction / cotangent count of a derivative call (`name`), refused where each entry point's own documented order has it
+int check_count(const std::string& who, const char* name, int n) {
+    return n < 1 || n > 65535 ? fail(CRB_EINVAL, who + ": " + name + " must be in [1, 65535]") : CRB_OK;
 }
 
 // The control schedule of a call (crb_input_schedule), checked against the call's steps and input; f == nullptr: none.
@@ -1036,13 +1061,11 @@ int decode_schedule(const crb_input_schedule* s, const crb_input_desc* in, int n
     out->hold = s->hold;
     return CRB_OK;
 }
-// elements from one interval of a schedule-shaped tensor [K][B][n_node][4] to the next
-size_t sched_interval_elems(const crb_plan* p) { return size_t(p->B) * size_t(p->n_node) * 4; }
 // the schedule in the parameter block of a launch whose first step is step `first_step` of the call
 template <typename T>
 void set_sched(const crb_plan* p, KParams<T>& k, const Schedule& s, int first_step) {
     if (!s.f) return;
-    k.sched_stride = sched_interval_elems(p);
+    k.sched_stride = force_doubles(p);   // (elements from one interval of a schedule-shaped tensor [K][B][n_node][4] to the next)
     k.sched_hold = s.hold;
     k.sched_first = s.hold - first_step % s.hold;
     k.u_held = static_cast<const T*>(s.f) + size_t(first_step / s.hold) * k.sched_stride;
@@ -1131,8 +1154,7 @@ bool fused_feedback_ok(const crb_plan* p, const void* held) {
     // several rounds of workgroups is faster through the stage-split path (2048 x 27 elements: 125 against 67 us/step;
     // 64 x 27: 31 against 48; up to 16 elements the fused form wins at every size: 21 against 40 - 48 us/step)
     const size_t per_cu = (size_t(160) * 1024) / need;
-    const size_t groups = size_t((p->B + p->G - 1) / p->G);
-    return need <= size_t(52) * 1024 || groups <= per_cu * 256;
+    return need <= size_t(52) * 1024 || size_t(beam_groups(p)) <= per_cu * 256;
 }
 // ... and its packed lean form: several beams per wave (its right-hand side costs half of the general kernel's)
 template <typename T>
@@ -1157,7 +1179,7 @@ bool loop_ok(const crb_plan* p, const void* held) {
 
 template <typename T, int MODE, int LV, bool LEAN>
 int launch_beam_lean(const crb_plan* p, const KParams<T>& k, hipStream_t st) {
-    const dim3 grid((p->B + p->G - 1) / p->G), block(p->NT);
+    const dim3 grid(beam_groups(p)), block(p->NT);
     const size_t smem = lds_bytes<T>(p->NT);
     // register budget: <=256-thread groups run 2 groups per CU (2 waves/SIMD, 256 VGPRs) so that the
     // solve multipliers stay in registers; 1024-thread groups get what their size allows
@@ -1425,7 +1447,7 @@ extern "C" int crb_rhs_host(const crb_plan* p, const double* x_red, const double
     k.out = p->d_stage + B * 3 * n;
     k.red_map = p->d_red_map;
     k.n_red = int(n);
-    const bool flagged = (p->B + p->G - 1) / p->G == 1;
+    const bool flagged = beam_groups(p) == 1;
     if (flagged) {
         k.done_flag = reinterpret_cast<unsigned long long*>(p->d_stage + B * 5 * n);
         k.done_seq = ++p->host_seq;
@@ -1447,7 +1469,7 @@ extern "C" int crb_internal_force_host(const crb_plan* p, const double* q_red, d
     k.out = p->d_stage + B * 3 * n;
     k.red_map = p->d_red_map;
     k.n_red = int(n);
-    const bool flagged = (p->B + p->G - 1) / p->G == 1;
+    const bool flagged = beam_groups(p) == 1;
     if (flagged) {
         k.done_flag = reinterpret_cast<unsigned long long*>(p->d_stage + B * 5 * n);
         k.done_seq = ++p->host_seq;
@@ -1538,7 +1560,7 @@ int stiff_tables(const crb_plan* p, double alpha, hipStream_t st) {
 
 template <typename T, int LV>
 int launch_implicit_lv(const crb_plan* p, const KParams<T>& k, const StiffParams<T>& q, hipStream_t st) {
-    const dim3 grid((p->B + p->G - 1) / p->G), block(p->NT);
+    const dim3 grid(beam_groups(p)), block(p->NT);
     const size_t smem = lds_bytes<T>(p->NT);
     // one wave per SIMD: the thread's rows of A's tables (10 per level, up to 8 levels) stay in registers
     if (p->NT > 256) return fail(CRB_EUNSUPPORTED, "crb_step_implicit: beams of more than 256 thread-carried nodes are not supported");
@@ -1568,7 +1590,7 @@ int launch_implicit(const crb_plan* p, const KParams<T>& k, const StiffParams<T>
                                         : implicit_lean_minw(p->stiff_levels, grav, p->lognw);   // (waves per SIMD: crb_stiff.h)
         int resident = 256 * 4 / (1 << p->lognw) * minw;
         if (const int cap = int(env_int("CRB_LEAN_MAX_GROUPS", 0)); cap > 0) resident = cap;   // (tests)
-        const int groups = (p->B + p->G - 1) / p->G;
+        const int groups = beam_groups(p);
         HIP_TRY(crb::launch_implicit_lean(k, q, shared ? walk_grid(groups, resident) : groups, p->stiff_levels, p->lognw, grav,
                                           p->elem_mode, st));
         return CRB_OK;
@@ -1582,7 +1604,7 @@ int launch_implicit(const crb_plan* p, const KParams<T>& k, const StiffParams<T>
 // the general implicit kernel in its damped form (generalised-alpha): any level count, one wave per SIMD
 template <typename T, int LV>
 int launch_implicit_damped_lv(const crb_plan* p, const KParams<T>& k, const StiffParams<T>& q, hipStream_t st) {
-    const dim3 grid((p->B + p->G - 1) / p->G), block(p->NT);
+    const dim3 grid(beam_groups(p)), block(p->NT);
     hipLaunchKernelGGL((crb_implicit_kernel<T, LV, 256, 1, true>), grid, block, lds_bytes<T>(p->NT), st, k, q);
     HIP_TRY(hipGetLastError());
     return CRB_OK;
@@ -1623,7 +1645,7 @@ int step_implicit_impl(const crb_plan* p, void* x, double t0, double h, int n_st
     q.a0 = nullptr;
     if (!damped) return launch_implicit<T>(p, k, q, st);
     // a_0: the RHS of the state at t0 with the input of t0 (one launch of the RHS kernel into the plan's scratch)
-    if (!p->d_rhs0) HIP_TRY(hipMalloc(&p->d_rhs0, size_t(p->B) * 2 * p->n_node * 4 * sizeof(T)));
+    if (!p->d_rhs0) HIP_TRY(hipMalloc(&p->d_rhs0, state_doubles(p) * sizeof(T)));
     {
         KParams<T> r = base_params<T>(p);
         r.x = static_cast<T*>(x);
@@ -1805,8 +1827,7 @@ extern "C" int crb_solve_controlled(const crb_plan* p, void* x, double t0, doubl
             pieces.push_back(c);
         }
     }
-    crb::CtrlParams<double> q;
-    std::memset(&q, 0, sizeof(q));
+    crb::CtrlParams<double> q = zeroed<crb::CtrlParams<double>>();
     if (!fb) {
         if (p->levels_full > 8) return fail(CRB_EUNSUPPORTED, "crb_solve_controlled: beams of more than 256 thread-carried nodes are not supported");
         const int lf = p->levels_full, nd = p->asm_in->nd;
@@ -1926,7 +1947,7 @@ int rk4_stage(const crb_plan* p, void* x, const void* xs, void* acc, void* xs_ne
 template <typename Force>
 int feedback_rollout(const crb_plan* p, void* x, double t0, double dt, int n_steps, const Forcing& f, void* work, Force force,
                      void* stream) {
-    const size_t state = size_t(p->B) * 2 * p->n_node * 4 * (p->dtype == CRB_F64 ? sizeof(double) : sizeof(float));
+    const size_t state = state_doubles(p) * (p->dtype == CRB_F64 ? sizeof(double) : sizeof(float));
     char* w = static_cast<char*>(work);
     void* acc = w;
     void* bufs[2] = {w + state, w + 2 * state};
@@ -1951,7 +1972,7 @@ int feedback_rollout(const crb_plan* p, void* x, double t0, double dt, int n_ste
 
 template <typename T, int LV>
 int launch_fused_feedback_lv(const crb_plan* p, const KParams<T>& k, hipStream_t st) {
-    const dim3 grid((p->B + p->G - 1) / p->G), block(p->NT);
+    const dim3 grid(beam_groups(p)), block(p->NT);
     const size_t smem = fb_lds_bytes<T>(p->NT, p->G, p->n_free);
     HIP_TRY(lds_opt_in(crb_beam_kernel<T, MODE_STEP, LV, 64, 1, false, true>, smem));
     hipLaunchKernelGGL((crb_beam_kernel<T, MODE_STEP, LV, 64, 1, false, true>), grid, block, smem, st, k);
@@ -1991,8 +2012,7 @@ int loop_feedback(const crb_plan* p, void* x, double t0, double dt, int n_steps,
     const int nb = loop_nb(p->lognw), n_rb = (p->B + 63) / 64;
     const crb::LoopWork lay = crb::loop_work_layout(nb, n_rb < crb::LOOP_MAX_GROUPS ? n_rb : crb::LOOP_MAX_GROUPS);
     char* w = static_cast<char*>(work);
-    crb::LoopParams<double> P;
-    std::memset(&P, 0, sizeof(P));
+    crb::LoopParams<double> P = zeroed<crb::LoopParams<double>>();
     P.k = base_params<double>(p);
     P.k.x = static_cast<double*>(x);
     P.k.t0 = t0; P.k.dt = dt; P.k.n_steps = n_steps;
@@ -2021,7 +2041,7 @@ int loop_feedback(const crb_plan* p, void* x, double t0, double dt, int n_steps,
 
 extern "C" size_t crb_feedback_work_bytes(const crb_plan* p) {
     if (!p) return 0;
-    const size_t state = size_t(p->B) * 2 * p->n_node * 4 * (p->dtype == CRB_F64 ? sizeof(double) : sizeof(float)), force = state / 2;
+    const size_t state = state_doubles(p) * (p->dtype == CRB_F64 ? sizeof(double) : sizeof(float)), force = state / 2;
     size_t need = 3 * state + force;
     if (loop_shape_ok(p)) {
         const int n_rb = (p->B + 63) / 64;
@@ -2229,8 +2249,7 @@ bool implicit_feedback_in_kernel(const crb_plan* p) {
     if (!implicit_feedback_fits(p)) return false;
     if (const char* v = env("CRB_IMPLICIT_FEEDBACK")) return std::atoi(v) != 0;
     const size_t per_cu = (size_t(160) * 1024) / crb::implicit_feedback_lds_bytes(p->NT, p->G, p->n_free);
-    const size_t groups = size_t((p->B + p->G - 1) / p->G);
-    return groups <= 256 * (per_cu < 4 ? per_cu : 4);
+    return size_t(beam_groups(p)) <= 256 * (per_cu < 4 ? per_cu : 4);
 }
 StiffParams<double> stiff_params(const crb_plan* p, double h, int n_iter) {
     StiffParams<double> q{};
@@ -2260,12 +2279,12 @@ int implicit_feedback_fused(const crb_plan* p, void* x, double t0, double h, int
     k.fb_ref = static_cast<const double*>(ref);
     // (the kernel writes the records of the thread-carried nodes: a dropped fixed node's entries read as zero)
     if (u_out)
-        HIP_TRY(hipMemsetAsync(u_out, 0, size_t((n_steps + hold - 1) / hold) * size_t(p->B) * size_t(p->n_node) * 4 * sizeof(double), st));
+        HIP_TRY(hipMemsetAsync(u_out, 0, size_t((n_steps + hold - 1) / hold) * force_doubles(p) * sizeof(double), st));
     StiffFbParams<double> q{};
     static_cast<StiffParams<double>&>(q) = stiff_params(p, h, n_iter);
     q.u_out = static_cast<double*>(u_out);
     q.hold = hold;
-    const hipError_t e = crb::launch_implicit_feedback(k, q, p->stiff_levels, (p->B + p->G - 1) / p->G,
+    const hipError_t e = crb::launch_implicit_feedback(k, q, p->stiff_levels, beam_groups(p),
                                                        crb::implicit_feedback_lds_bytes(p->NT, p->G, p->n_free), st);
     if (e != hipSuccess) return fail(CRB_EHIP, std::string("crb_step_implicit_feedback: ") + hipGetErrorString(e));
     return CRB_OK;
@@ -2275,7 +2294,7 @@ int implicit_feedback_chain(const crb_plan* p, void* x, double t0, double h, int
                             const void* ref, const Forcing& f, const Recording& rec, void* u_out, void* work, hipStream_t st) {
     if (int rc = stiff_tables<double>(p, 0.25 * h * h, st)) return rc;
     const StiffParams<double> q = stiff_params(p, h, n_iter);
-    const size_t force = size_t(p->B) * size_t(p->n_node) * 4, plane2 = size_t(p->B) * 2 * size_t(p->n_node) * 4;
+    const size_t force = force_doubles(p), plane2 = state_doubles(p);
     const int n_samples = (n_steps + hold - 1) / hold;
     // entries of a force record that the GEMM does not write (constrained DOFs, the padding component) read as zero
     if (u_out) HIP_TRY(hipMemsetAsync(u_out, 0, size_t(n_samples) * force * sizeof(double), st));
@@ -2320,7 +2339,7 @@ int implicit_feedback_chain(const crb_plan* p, void* x, double t0, double h, int
 
 extern "C" size_t crb_implicit_feedback_work_bytes(const crb_plan* p) {
     if (!p) return 0;
-    return size_t(p->B) * size_t(p->n_node) * 4 * sizeof(double);   // one force record (the chain form's held input)
+    return force_doubles(p) * sizeof(double);   // one force record (the chain form's held input)
 }
 
 extern "C" int crb_implicit_feedback_path(const crb_plan* p) {
@@ -2519,12 +2538,11 @@ extern "C" int crb_tangent_stiffness(const crb_plan* p, const void* x, void* out
     if (int rc = static_checks(p, "crb_tangent_stiffness")) return rc;
     if (!x || !out) return fail(CRB_EINVAL, "crb_tangent_stiffness: null pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int groups = (p->B + p->G - 1) / p->G;
     return with_dtype(p, [&](auto t) -> int {
         using T = decltype(t);
         StaticParams<T> q{};
         q.blocks = static_cast<T*>(out);
-        HIP_TRY(crb::launch_tangent(static_params<T>(p, x), q, groups, p->NT, st));
+        HIP_TRY(crb::launch_tangent(static_params<T>(p, x), q, beam_groups(p), p->NT, st));
         return CRB_OK;
     });
 }
@@ -2561,7 +2579,7 @@ extern "C" int crb_solve_static(const crb_plan* p, void* x, const crb_input_desc
     q.atol = atol;
     q.iters = iters;
     q.residual = static_cast<double*>(residual);
-    HIP_TRY(crb::launch_static(k, q, (p->B + p->G - 1) / p->G, p->NT, static_cast<hipStream_t>(stream)));
+    HIP_TRY(crb::launch_static(k, q, beam_groups(p), p->NT, static_cast<hipStream_t>(stream)));
     return CRB_OK;
 }
 
@@ -2572,7 +2590,37 @@ int tangent_checks(const crb_plan* p, int n_dir, const char* who) {
     if (p->dtype != CRB_F64) return fail(CRB_EUNSUPPORTED, std::string(who) + ": the tangent kernels need an fp64 plan");
     if (p->NT > TANGENT_MAX_NT)
         return fail(CRB_EUNSUPPORTED, std::string(who) + ": beams of more than 256 thread-carried nodes are not supported");
-    if (n_dir < 1 || n_dir > 65535) return fail(CRB_EINVAL, std::string(who) + ": n_dir must be in [1, 65535]");
+    return check_count(who, "n_dir", n_dir);
+}
+// What the two tangent rollouts share once the caller has put its family's tables and step size into k: the state, forcing,
+// clock and status in k, the TangentParams -- the seeds dx, the input tangents (with a schedule its tangent d_sched in
+// df_held's place) and, for more than one direction, a copy of the base state -- and the family's launch(k, q).
+template <typename L>
+int tangent_rollout(const crb_plan* p, KParams<double> k, void* x, void* dx, int n_dir, double t0, int n_steps, const Forcing& f,
+                    const crb_input_tangent* din, const Schedule& sc, const void* d_sched, hipStream_t st, L&& launch) {
+    k.x = static_cast<double*>(x);
+    set_io(k, f);
+    k.t0 = t0; k.n_steps = n_steps;
+    arm_status(p, k, n_steps);
+    TangentParams<double> q{};
+    q.x0 = k.x;
+    if (n_dir > 1) {   // (instance d = 0 writes the base back while the others may still be loading it: they read a copy)
+        const size_t bytes = state_doubles(p) * sizeof(double);
+        if (!p->d_tan_x0) HIP_TRY(hipMalloc(&p->d_tan_x0, bytes));
+        HIP_TRY(hipMemcpyAsync(p->d_tan_x0, x, bytes, hipMemcpyDeviceToDevice, st));
+        q.x0 = static_cast<const double*>(p->d_tan_x0);
+    }
+    q.dx = static_cast<double*>(dx);
+    if (din) {
+        q.du_held = static_cast<const double*>(din->df_held);
+        q.d_amp = static_cast<const double*>(din->d_amp);
+    }
+    if (sc.f) {
+        set_sched(p, k, sc, 0);
+        q.du_held = static_cast<const double*>(d_sched);
+        q.du_dir_stride = size_t(sc.K) * force_doubles(p);
+    }
+    HIP_TRY(launch(k, q));
     return CRB_OK;
 }
 }  // namespace
@@ -2590,7 +2638,7 @@ extern "C" int crb_rhs_jvp(const crb_plan* p, const void* x, const void* u, cons
     q.dx = static_cast<double*>(const_cast<void*>(dx));
     q.dxdot = static_cast<double*>(dxdot);
     q.du_held = static_cast<const double*>(du);
-    HIP_TRY(crb::launch_jvp_rhs(k, q, (p->B + p->G - 1) / p->G, n_dir, p->NT, static_cast<hipStream_t>(stream)));
+    HIP_TRY(crb::launch_jvp_rhs(k, q, beam_groups(p), n_dir, p->NT, static_cast<hipStream_t>(stream)));
     return CRB_OK;
 }
 
@@ -2623,30 +2671,10 @@ extern "C" int crb_step_rk4_tangent_sched(const crb_plan* p, void* x, void* dx, 
     if (n_steps == 0) return CRB_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     KParams<double> k = base_params<double>(p);
-    k.x = static_cast<double*>(x);
-    set_io(k, f);
-    k.t0 = t0; k.dt = dt; k.n_steps = n_steps;
-    arm_status(p, k, n_steps);
-    TangentParams<double> q{};
-    q.x0 = k.x;
-    if (n_dir > 1) {   // (instance d = 0 writes the base back while the others may still be loading it: they read a copy)
-        const size_t bytes = size_t(p->B) * 2 * p->n_node * 4 * sizeof(double);
-        if (!p->d_tan_x0) HIP_TRY(hipMalloc(&p->d_tan_x0, bytes));
-        HIP_TRY(hipMemcpyAsync(p->d_tan_x0, x, bytes, hipMemcpyDeviceToDevice, st));
-        q.x0 = static_cast<const double*>(p->d_tan_x0);
-    }
-    q.dx = static_cast<double*>(dx);
-    if (din) {
-        q.du_held = static_cast<const double*>(din->df_held);
-        q.d_amp = static_cast<const double*>(din->d_amp);
-    }
-    if (sc.f) {
-        set_sched(p, k, sc, 0);
-        q.du_held = static_cast<const double*>(d_sched);
-        q.du_dir_stride = size_t(sc.K) * sched_interval_elems(p);
-    }
-    HIP_TRY(crb::launch_jvp_step(k, q, (p->B + p->G - 1) / p->G, n_dir, p->NT, st));
-    return CRB_OK;
+    k.dt = dt;
+    return tangent_rollout(p, k, x, dx, n_dir, t0, n_steps, f, din, sc, d_sched, st, [&](auto& kk, auto& q) {
+        return crb::launch_jvp_step(kk, q, beam_groups(p), n_dir, p->NT, st);
+    });
 }
 
 // ------------------------------------------------------------------ adjoint RHS and rollout (crb_adjoint.h)
@@ -2700,8 +2728,7 @@ int adjoint_checks(const crb_plan* p, int n_cot, const char* who) {
     if (p->dtype != CRB_F64) return fail(CRB_EUNSUPPORTED, std::string(who) + ": the adjoint kernels need an fp64 plan");
     if (p->NT > ADJ_MAX_NT)
         return fail(CRB_EUNSUPPORTED, std::string(who) + ": beams of more than 256 thread-carried nodes are not supported");
-    if (n_cot < 1 || n_cot > 65535) return fail(CRB_EINVAL, std::string(who) + ": n_cot must be in [1, 65535]");
-    return CRB_OK;
+    return check_count(who, "n_cot", n_cot);
 }
 
 // the inverse gravity lists on the device (built and uploaded on first use; gravity-free plans need none)
@@ -2726,14 +2753,39 @@ int ensure_gadj(const crb_plan* p, const char* who) {
 }
 
 AdjParams<double> adj_params(const crb_plan* p) {
-    AdjParams<double> q;
-    std::memset(&q, 0, sizeof(q));
+    AdjParams<double> q = zeroed<AdjParams<double>>();
     q.gadj = p->d_gadj;
     q.gadj_beam = p->d_gadj_beam;
     q.store_every = 1;
     return q;
 }
-size_t state_doubles(const crb_plan* p) { return size_t(p->B) * 2 * size_t(p->n_node) * 4; }
+// the checkpoint pass: the state at the start of every segment of `every` steps into ckpt, the final state back into x
+AdjParams<double> checkpoint_params(const crb_plan* p, void* ckpt, int every) {
+    AdjParams<double> q = adj_params(p);
+    q.states = static_cast<double*>(ckpt);
+    q.store_every = every;
+    q.write_back = 1;
+    return q;
+}
+// the backward sweep over the segment of steps k0 .. k0 + n - 1: its recomputed data and clocks, lam in place, the input
+// cotangents.  With a schedule f_bar is its cotangent [n_cot][K][B][n_node][4]: the sweep starts in the interval of the
+// segment's last step and walks down (one accumulator: the interval's record).  The cotangent stride is set for every schedule,
+// as the implicit sweep always did; the RK4 sweep left it 0 without an f_bar, where no kernel reads it (crb_adjoint.h fboff).
+AdjParams<double> sweep_params(const crb_plan* p, const double* wstates, const double* wclock, void* lam, void* amp_bar, void* f_bar,
+                               const Schedule& sc, int k0, int n) {
+    AdjParams<double> b = adj_params(p);
+    b.work = wstates;
+    b.work_clock = wclock;
+    b.lam = static_cast<double*>(lam);
+    b.amp_bar = static_cast<double*>(amp_bar);
+    b.f_bar = static_cast<double*>(f_bar);
+    if (sc.f) {
+        if (f_bar) b.f_bar += size_t((k0 + n - 1) / sc.hold) * force_doubles(p);
+        b.fbar_cot_stride = size_t(sc.K) * force_doubles(p);
+    }
+    b.step0 = k0;
+    return b;
+}
 }  // namespace
 
 extern "C" int crb_plan_get_grav_transpose(const crb_plan* p, int beam, int32_t* seg, int32_t* phi, int32_t* fanin) {
@@ -2772,9 +2824,19 @@ extern "C" int crb_rhs_vjp(const crb_plan* p, const void* x, const void* u, cons
     q.lam_in = static_cast<const double*>(lam);
     q.xbar = static_cast<double*>(xbar);
     q.ubar = static_cast<double*>(ubar);
-    HIP_TRY(crb::launch_adj_rhs(k, q, (p->B + p->G - 1) / p->G, n_cot, p->NT, static_cast<hipStream_t>(stream)));
+    HIP_TRY(crb::launch_adj_rhs(k, q, beam_groups(p), n_cot, p->NT, static_cast<hipStream_t>(stream)));
     return CRB_OK;
 }
+
+namespace {
+// The work buffer of the RK4 adjoint, in doubles: a segment's stage points [every][4] states, its clocks [every], and with
+// parameter gradients (crb_rk4_adjoint_params_work_bytes) the sweep's per-stage rbar, [every][4][n_cot] force records.
+struct AdjWork { double *states, *clock, *rbar; };
+AdjWork adj_work(const crb_plan* p, void* work, int every) {
+    double* const states = static_cast<double*>(work), * const clock = states + size_t(every) * 4 * state_doubles(p);
+    return {states, clock, clock + size_t(every)};
+}
+}  // namespace
 
 extern "C" size_t crb_rk4_adjoint_work_bytes(const crb_plan* p, int every) {
     if (!p || every < 1) return 0;
@@ -2811,11 +2873,7 @@ extern "C" int crb_step_rk4_checkpoint_sched(const crb_plan* p, void* x, double 
     set_io(k, f, &r);
     set_sched(p, k, sc, 0);
     k.t0 = t0; k.dt = dt; k.n_steps = n_steps;
-    AdjParams<double> q = adj_params(p);
-    q.states = static_cast<double*>(ckpt);
-    q.store_every = every;
-    q.write_back = 1;
-    HIP_TRY(crb::launch_adj_forward(k, q, (p->B + p->G - 1) / p->G, p->NT, static_cast<hipStream_t>(stream)));
+    HIP_TRY(crb::launch_adj_forward(k, checkpoint_params(p, ckpt, every), beam_groups(p), p->NT, static_cast<hipStream_t>(stream)));
     return CRB_OK;
 }
 
@@ -2866,51 +2924,35 @@ int adjoint_rollout(const char* who_c, const crb_plan* p, const void* ckpt, void
     if (n_steps == 0) return CRB_OK;
     if (int rc = ensure_gadj(p, who_c)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int groups = (p->B + p->G - 1) / p->G;
-    const size_t sd = state_doubles(p);
-    double* const wstates = static_cast<double*>(work);
-    double* const wclock = wstates + size_t(every) * 4 * sd;
-    double* const wrbar = wclock + size_t(every);   // (crb_rk4_adjoint_params_work_bytes: after the stage points and the clocks)
-    const int nseg = (n_steps + every - 1) / every;
-    for (int g = nseg - 1; g >= 0; --g) {
-        const int k0 = g * every, n = (n_steps - k0) < every ? (n_steps - k0) : every;
-        const double tg = clock_after(t0, dt, k0);   // (the checkpoint pass's clock at the segment start: the same additions)
+    const int groups = beam_groups(p);
+    const AdjWork w = adj_work(p, work, every);
+    return for_segments_reversed(n_steps, every, t0, dt, [&](int g, int k0, int n, double tg) -> int {
         KParams<double> k = base_params<double>(p);
         set_io(k, f);
         set_sched(p, k, sc, k0);   // (the recompute starts mid-rollout: its interval and phase)
         k.dt = dt; k.t0 = tg; k.n_steps = n;
         // 1. the segment's stage points from its checkpoint
-        k.x = const_cast<double*>(static_cast<const double*>(ckpt)) + size_t(g) * sd;
+        k.x = const_cast<double*>(static_cast<const double*>(ckpt)) + size_t(g) * state_doubles(p);
         AdjParams<double> q = adj_params(p);
-        q.states = wstates;
-        q.clocks = wclock;
+        q.states = w.states;
+        q.clocks = w.clock;
         q.stage_pts = 1;
         HIP_TRY(crb::launch_adj_forward(k, q, groups, p->NT, st));
         // 2. the sweep back over it, every cotangent
         k.x = nullptr;
-        k.rec_out = static_cast<double*>(r.out); k.rec_slot = r.slot; k.rec_comp = r.comp; k.rec_every = r.every; k.rec_n = r.count;
-        AdjParams<double> b = adj_params(p);
-        b.work = wstates;
-        b.work_clock = wclock;
-        b.lam = static_cast<double*>(lam);
-        b.amp_bar = static_cast<double*>(amp_bar);
-        b.f_bar = static_cast<double*>(f_bar);
-        if (sc.f && f_bar) {   // the sweep starts in the interval of the segment's last step and walks down from there
-            b.f_bar += size_t((k0 + n - 1) / sc.hold) * sched_interval_elems(p);
-            b.fbar_cot_stride = size_t(sc.K) * sched_interval_elems(p);
-        }
-        b.step0 = k0;
+        set_record(k, r);
+        AdjParams<double> b = sweep_params(p, w.states, w.clock, lam, amp_bar, f_bar, sc, k0, n);
         if (!want_params) {
             HIP_TRY(crb::launch_adj_backward(k, b, groups, n_cot, p->NT, st));
-            continue;
+            return CRB_OK;
         }
-        b.rbar = wrbar;
+        b.rbar = w.rbar;
         b.param_bar = static_cast<double*>(param_bar);
         HIP_TRY(crb::launch_adj_backward_store(k, b, groups, n_cot, p->NT, st));
         // 3. the parameter sums of the segment, from its stage points and the sweep's rbar
         HIP_TRY(crb::launch_param_grad(k, b, groups, n_cot, p->NT, st));
-    }
-    return CRB_OK;
+        return CRB_OK;
+    });
 }
 }  // namespace
 
@@ -2931,8 +2973,7 @@ extern "C" int crb_step_rk4_adjoint_sched(const crb_plan* p, const void* ckpt, v
 
 extern "C" size_t crb_rk4_adjoint_params_work_bytes(const crb_plan* p, int every, int n_cot) {
     if (!p || every < 1 || n_cot < 1) return 0;
-    return crb_rk4_adjoint_work_bytes(p, every) +
-           size_t(every) * 4 * size_t(n_cot) * size_t(p->B) * size_t(p->n_node) * 4 * sizeof(double);
+    return crb_rk4_adjoint_work_bytes(p, every) + size_t(every) * 4 * size_t(n_cot) * force_doubles(p) * sizeof(double);
 }
 
 extern "C" int crb_step_rk4_adjoint_params(const crb_plan* p, const void* ckpt, void* lam, int n_cot, double t0, double dt,
@@ -2958,7 +2999,7 @@ constexpr int IMP_ADJ_MAX_ITER = 16;
 // the argument checks the two implicit-adjoint entry points share, in the documented order: CRB_EINVAL first (the caller adds
 // its own pointer and aliasing checks before this), then imp_adjoint_plan_checks
 int imp_adjoint_arg_checks(const std::string& who, int n_cot, int n_steps, int every, int n_iter, double h) {
-    if (n_cot < 1 || n_cot > 65535) return fail(CRB_EINVAL, who + ": n_cot must be in [1, 65535]");
+    if (int rc = check_count(who, "n_cot", n_cot)) return rc;
     if (n_steps < 0) return fail(CRB_EINVAL, who + ": n_steps must be >= 0");
     if (every < 1) return fail(CRB_EINVAL, who + ": every must be >= 1");
     if (n_iter < 1 || n_iter > IMP_ADJ_MAX_ITER) return fail(CRB_EINVAL, who + ": n_iter must be in [1, 16]");
@@ -2983,7 +3024,15 @@ int imp_adjoint_params(const crb_plan* p, double h, hipStream_t st, KParams<doub
     k->dt = h;
     return CRB_OK;
 }
-size_t force_doubles(const crb_plan* p) { return size_t(p->B) * size_t(p->n_node) * 4; }
+// The work buffer of the implicit adjoint, in doubles: a segment's step start states [every], iterates [every][n_iter] force
+// records and clocks [every], and the cotangent carried through the starting iterate from one segment to the one before it,
+// [n_cot] force records.
+struct ImpAdjWork { double *states, *iters, *clock, *carry; };
+ImpAdjWork imp_adj_work(const crb_plan* p, void* work, int every, int n_iter) {
+    double* const states = static_cast<double*>(work), * const iters = states + size_t(every) * state_doubles(p);
+    double* const clock = iters + size_t(every) * size_t(n_iter) * force_doubles(p);
+    return {states, iters, clock, clock + size_t(every)};
+}
 }  // namespace
 
 extern "C" size_t crb_implicit_adjoint_work_bytes(const crb_plan* p, int every, int n_iter, int n_cot) {
@@ -3024,14 +3073,9 @@ extern "C" int crb_step_implicit_checkpoint_sched(const crb_plan* p, void* x, do
     set_io(k, f, &r);
     set_sched(p, k, sc, 0);
     k.t0 = t0; k.n_steps = n_steps;
-    AdjParams<double> q = adj_params(p);
-    q.states = static_cast<double*>(ckpt);
-    q.store_every = every;
-    q.write_back = 1;
-    ImpAdjParams<double> iq;
-    std::memset(&iq, 0, sizeof(iq));
+    ImpAdjParams<double> iq = zeroed<ImpAdjParams<double>>();
     iq.n_iter = n_iter;
-    HIP_TRY(crb::launch_imp_adj_checkpoint(k, q, iq, (p->B + p->G - 1) / p->G, p->NT, st));
+    HIP_TRY(crb::launch_imp_adj_checkpoint(k, checkpoint_params(p, ckpt, every), iq, beam_groups(p), p->NT, st));
     return CRB_OK;
 }
 
@@ -3083,52 +3127,32 @@ extern "C" int crb_step_implicit_adjoint_sched(const crb_plan* p, const void* ck
     KParams<double> base;
     if (int rc = imp_adjoint_params(p, h, st, &base)) return rc;
     set_io(base, f);
-    const int groups = (p->B + p->G - 1) / p->G;
-    const size_t sd = state_doubles(p), fd = force_doubles(p);
-    // (crb_implicit_adjoint_work_bytes: start states, iterates, clocks, carry)
-    double* const wstates = static_cast<double*>(work);
-    double* const witers = wstates + size_t(every) * sd;
-    double* const wclock = witers + size_t(every) * size_t(n_iter) * fd;
-    double* const wcarry = wclock + size_t(every);
-    const int nseg = (n_steps + every - 1) / every;
-    for (int g = nseg - 1; g >= 0; --g) {
-        const int k0 = g * every, n = (n_steps - k0) < every ? (n_steps - k0) : every;
+    const ImpAdjWork w = imp_adj_work(p, work, every, n_iter);
+    ImpAdjParams<double> iter = zeroed<ImpAdjParams<double>>();
+    iter.n_iter = n_iter;
+    return for_segments_reversed(n_steps, every, t0, h, [&](int g, int k0, int n, double tg) -> int {
         KParams<double> k = base;
-        k.t0 = clock_after(t0, h, k0);   // (the checkpoint pass's clock at the segment start: the same additions)
+        k.t0 = tg;
         k.n_steps = n;
         set_sched(p, k, sc, k0);   // (the recompute starts mid-rollout: its interval and phase)
         // 1. the segment's step data from its checkpoint
         AdjParams<double> q = adj_params(p);
-        q.states = wstates;
-        q.clocks = wclock;
-        ImpAdjParams<double> iq;
-        std::memset(&iq, 0, sizeof(iq));
-        iq.n_iter = n_iter;
-        iq.start = static_cast<const double*>(ckpt) + size_t(g) * 3 * fd;
-        iq.iters_out = witers;
-        HIP_TRY(crb::launch_imp_adj_segment(k, q, iq, groups, p->NT, st));
+        q.states = w.states;
+        q.clocks = w.clock;
+        ImpAdjParams<double> iq = iter;
+        iq.start = static_cast<const double*>(ckpt) + size_t(g) * 3 * force_doubles(p);
+        iq.iters_out = w.iters;
+        HIP_TRY(crb::launch_imp_adj_segment(k, q, iq, beam_groups(p), p->NT, st));
         // 2. the sweep back over it, every cotangent
-        k.rec_out = static_cast<double*>(r.out); k.rec_slot = r.slot; k.rec_comp = r.comp; k.rec_every = r.every; k.rec_n = r.count;
-        AdjParams<double> b = adj_params(p);
-        b.work = wstates;
-        b.work_clock = wclock;
-        b.lam = static_cast<double*>(lam);
-        b.amp_bar = static_cast<double*>(amp_bar);
-        b.f_bar = static_cast<double*>(f_bar);
-        if (sc.f) {   // the sweep starts in the interval of the segment's last step and walks down from there
-            if (f_bar) b.f_bar += size_t((k0 + n - 1) / sc.hold) * sched_interval_elems(p);
-            b.fbar_cot_stride = size_t(sc.K) * sched_interval_elems(p);
-        }
-        b.step0 = k0;
-        ImpAdjParams<double> ib;
-        std::memset(&ib, 0, sizeof(ib));
-        ib.n_iter = n_iter;
-        ib.iters = witers;
-        ib.carry = wcarry;
-        ib.carry_in = g < nseg - 1 ? 1 : 0;
-        HIP_TRY(crb::launch_imp_adj_backward(k, b, ib, groups, n_cot, p->NT, st));
-    }
-    return CRB_OK;
+        set_record(k, r);
+        ImpAdjParams<double> ib = iter;
+        ib.iters = w.iters;
+        ib.carry = w.carry;
+        ib.carry_in = k0 + n < n_steps ? 1 : 0;   // (every segment but the one that ends the rollout)
+        HIP_TRY(crb::launch_imp_adj_backward(k, sweep_params(p, w.states, w.clock, lam, amp_bar, f_bar, sc, k0, n), ib, beam_groups(p),
+                                             n_cot, p->NT, st));
+        return CRB_OK;
+    });
 }
 
 // ---- tangent of the implicit stepper (crb_implicit_tangent.h)
@@ -3145,7 +3169,7 @@ extern "C" int crb_step_implicit_tangent_sched(const crb_plan* p, void* x, void*
     const std::string who(sched || d_sched ? "crb_step_implicit_tangent_sched" : "crb_step_implicit_tangent");
     if (!p) return fail(CRB_EINVAL, who + ": null plan");
     if (!x || !dx) return fail(CRB_EINVAL, who + ": null state or tangent");
-    if (n_dir < 1 || n_dir > 65535) return fail(CRB_EINVAL, who + ": n_dir must be in [1, 65535]");
+    if (int rc = check_count(who, "n_dir", n_dir)) return rc;
     if (n_steps < 0) return fail(CRB_EINVAL, who + ": n_steps must be >= 0");
     if (n_iter < 1 || n_iter > IMP_ADJ_MAX_ITER) return fail(CRB_EINVAL, who + ": n_iter must be in [1, 16]");
     if (!(h > 0)) return fail(CRB_EINVAL, who + ": h must be positive");
@@ -3165,39 +3189,14 @@ extern "C" int crb_step_implicit_tangent_sched(const crb_plan* p, void* x, void*
     hipStream_t st = static_cast<hipStream_t>(stream);
     KParams<double> k;
     if (int rc = imp_adjoint_params(p, h, st, &k)) return rc;   // (A's tables where M's are, k.dt = h)
-    k.x = static_cast<double*>(x);
-    set_io(k, f);
-    k.t0 = t0; k.n_steps = n_steps;
-    arm_status(p, k, n_steps);
-    TangentParams<double> q{};
-    q.x0 = k.x;
-    if (n_dir > 1) {   // (instance d = 0 writes the base back while the others may still be loading it: they read a copy)
-        const size_t bytes = size_t(p->B) * 2 * p->n_node * 4 * sizeof(double);
-        if (!p->d_tan_x0) HIP_TRY(hipMalloc(&p->d_tan_x0, bytes));
-        HIP_TRY(hipMemcpyAsync(p->d_tan_x0, x, bytes, hipMemcpyDeviceToDevice, st));
-        q.x0 = static_cast<const double*>(p->d_tan_x0);
-    }
-    q.dx = static_cast<double*>(dx);
-    if (din) {
-        q.du_held = static_cast<const double*>(din->df_held);
-        q.d_amp = static_cast<const double*>(din->d_amp);
-    }
-    if (sc.f) {
-        set_sched(p, k, sc, 0);
-        q.du_held = static_cast<const double*>(d_sched);
-        q.du_dir_stride = size_t(sc.K) * sched_interval_elems(p);
-    }
-    HIP_TRY(crb::launch_imp_jvp_step(k, q, n_iter, sc.f != nullptr, (p->B + p->G - 1) / p->G, n_dir, p->NT, st));
-    return CRB_OK;
+    return tangent_rollout(p, k, x, dx, n_dir, t0, n_steps, f, din, sc, d_sched, st, [&](auto& kk, auto& q) {
+        return crb::launch_imp_jvp_step(kk, q, n_iter, sc.f != nullptr, beam_groups(p), n_dir, p->NT, st);
+    });
 }
 
 // ---- sensitivities of the equilibrium (crb_static.h: crb_static_sens_kernel; crb_paramgrad.h: crb_static_param_kernel)
 namespace {
 // every refusal before the device is touched, so that they hold for host-only plans too
-int static_sens_checks(const crb_plan* p, int n, const std::string& who, const char* count) {
-    if (n < 1 || n > 65535) return fail(CRB_EINVAL, who + ": " + count + " must be in [1, 65535]");
-    return CRB_OK;
-}
 int static_sens_plan_checks(const crb_plan* p, const std::string& who) {
     if (p->dtype != CRB_F64) return fail(CRB_EUNSUPPORTED, who + ": the static sensitivities need an fp64 plan");
     if (p->NT > STATIC_MAX_NT)
@@ -3214,7 +3213,7 @@ extern "C" int crb_static_jvp(const crb_plan* p, const void* x, const void* du, 
     const std::string who = "crb_static_jvp";
     if (!p) return fail(CRB_EINVAL, who + ": null plan");
     if (!x || !du || !dq) return fail(CRB_EINVAL, who + ": null pointer");
-    if (int rc = static_sens_checks(p, n_dir, who, "n_dir")) return rc;
+    if (int rc = check_count(who, "n_dir", n_dir)) return rc;
     if (dq == x || dq == du || (status && (static_cast<const void*>(status) == x || static_cast<const void*>(status) == du ||
                                            static_cast<const void*>(status) == dq)))
         return fail(CRB_EINVAL, who + ": outputs must not alias inputs or each other");
@@ -3224,7 +3223,7 @@ extern "C" int crb_static_jvp(const crb_plan* p, const void* x, const void* du, 
     q.sol = static_cast<double*>(dq);
     q.n_dir = n_dir;
     q.status = status;
-    HIP_TRY(crb::launch_static_sens(static_params<double>(p, x), q, false, (p->B + p->G - 1) / p->G, p->NT,
+    HIP_TRY(crb::launch_static_sens(static_params<double>(p, x), q, false, beam_groups(p), p->NT,
                                     static_cast<hipStream_t>(stream)));
     return CRB_OK;
 }
@@ -3234,7 +3233,7 @@ extern "C" int crb_static_vjp(const crb_plan* p, const void* x, const void* q_ba
     const std::string who = "crb_static_vjp";
     if (!p) return fail(CRB_EINVAL, who + ": null plan");
     if (!x || !q_bar || !f_held_bar) return fail(CRB_EINVAL, who + ": null pointer");
-    if (int rc = static_sens_checks(p, n_cot, who, "n_cot")) return rc;
+    if (int rc = check_count(who, "n_cot", n_cot)) return rc;
     const void* const st_v = status;
     if (f_held_bar == x || f_held_bar == q_bar || (param_bar && (param_bar == x || param_bar == q_bar || param_bar == f_held_bar)) ||
         (status && (st_v == x || st_v == q_bar || st_v == f_held_bar || st_v == param_bar)))
@@ -3243,20 +3242,19 @@ extern "C" int crb_static_vjp(const crb_plan* p, const void* x, const void* q_ba
     if (param_bar)
         if (int rc = ensure_gadj(p, who.c_str())) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int groups = (p->B + p->G - 1) / p->G;
     const KParams<double> k = static_params<double>(p, x);
     StaticSensParams<double> q{};
     q.rhs = static_cast<const double*>(q_bar);
     q.sol = static_cast<double*>(f_held_bar);
     q.n_dir = n_cot;
     q.status = status;
-    HIP_TRY(crb::launch_static_sens(k, q, true, groups, p->NT, st));
+    HIP_TRY(crb::launch_static_sens(k, q, true, beam_groups(p), p->NT, st));
     if (param_bar) {
         AdjParams<double> a = adj_params(p);
         a.work = static_cast<const double*>(x);
         a.rbar = static_cast<double*>(f_held_bar);
         a.param_bar = static_cast<double*>(param_bar);
-        HIP_TRY(crb::launch_static_param(k, a, groups, n_cot, p->NT, st));
+        HIP_TRY(crb::launch_static_param(k, a, beam_groups(p), n_cot, p->NT, st));
     }
     return CRB_OK;
 }
@@ -3406,15 +3404,13 @@ extern "C" int crb_step_rk4_feedback_adjoint(const crb_plan* p, const void* ckpt
     if (n_steps == 0) return CRB_OK;
     if (int rc = ensure_gadj(p, who.c_str())) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int groups = (p->B + p->G - 1) / p->G;
     const size_t S = state_doubles(p), x_stride = size_t(2) * p->n_node * 4;
     const FbAdjWork w = fb_adj_work(p, work, every, n_cot);
     // a sample of a constrained DOF has no cotangent to hand on (the state holds 0 there)
     const bool rec_on = r.slot >= 0 && p->any_free[size_t(3) * size_t(r.slot + p->off) + size_t(r.comp % 3)];
     const size_t rec_off = rec_on ? (size_t(r.comp / 3) * p->n_node + size_t(r.slot + p->off)) * 4 + size_t(r.comp % 3) : 0;
 
-    FeedbackAdjParams q;
-    std::memset(&q, 0, sizeof(q));
+    FeedbackAdjParams q = zeroed<FeedbackAdjParams>();
     q.ubar = w.ubar;
     q.col_off = p->d_col_off;
     q.row_off = p->d_row_off;
@@ -3434,13 +3430,10 @@ extern "C" int crb_step_rk4_feedback_adjoint(const crb_plan* p, const void* ckpt
     // the launch after stage s forms the seed of stage s - 1
     const double ca_next[4] = {0.0, dt / 6.0, dt / 3.0, dt / 3.0}, cb_next[4] = {0.0, 0.5 * dt, 0.5 * dt, dt};
 
-    const int nseg = (n_steps + every - 1) / every;
-    for (int g = nseg - 1; g >= 0; --g) {
-        const int k0 = g * every, n = (n_steps - k0) < every ? (n_steps - k0) : every;
+    return for_segments_reversed(n_steps, every, t0, dt, [&](int g, int k0, int n, double t) -> int {
         // 1. the segment's stage states from its checkpoint, straight into the work buffer
         HIP_TRY(hipMemcpyAsync(w.xcur, static_cast<const double*>(ckpt) + size_t(g) * S, S * sizeof(double), hipMemcpyDeviceToDevice, st));
         HIP_TRY(hipMemsetAsync(w.u, 0, S / 2 * sizeof(double), st));
-        double t = clock_after(t0, dt, k0);   // (the checkpoint pass's clock at the segment start: the same additions)
         for (int i = 0; i < n; ++i) {
             double* const X = w.stages + size_t(i) * 4 * S;
             HIP_TRY(hipMemcpyAsync(X, w.xcur, S * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -3462,7 +3455,7 @@ extern "C" int crb_step_rk4_feedback_adjoint(const crb_plan* p, const void* ckpt
                 a.lam_in = w.seed;
                 a.xbar = w.xbar;
                 a.ubar = w.ubar;
-                HIP_TRY(crb::launch_adj_rhs(k, a, groups, n_cot, p->NT, st));
+                HIP_TRY(crb::launch_adj_rhs(k, a, beam_groups(p), n_cot, p->NT, st));
                 q.first = s == 3; q.last = s == 0;
                 q.ca = ca_next[s]; q.cb = cb_next[s];
                 HIP_TRY(crb::launch_feedback_transpose(q, st));
@@ -3472,6 +3465,6 @@ extern "C" int crb_step_rk4_feedback_adjoint(const crb_plan* p, const void* ckpt
                 }
             }
         }
-    }
-    return CRB_OK;
+        return CRB_OK;
+    });
 }

@@ -24,7 +24,7 @@ for p in (ROOT, os.path.join(ROOT, "continuum-robot_amd")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-from continuum_robot.batched import BeamEnsemble  # noqa: E402
+from continuum_robot.batched import _IMPLICIT, BeamEnsemble  # noqa: E402
 from continuum_robot.models.force_params import ForceParams  # noqa: E402
 from tests.helpers import nitinol_columns  # noqa: E402
 
@@ -70,7 +70,7 @@ def case(B, n_elem, steps, reps):
 
     def ckpt_pass():
         x.copy_(x0)
-        return ens._implicit_checkpoint(x, steps, H, N_ITER, 0.0, desc, every, None)
+        return ens._checkpoint_pass(_IMPLICIT, x, steps, 0.0, (H, N_ITER), desc, every, None)
 
     out["checkpoint_pass_us_per_step"] = 1e3 * timed(ckpt_pass, reps) / steps
     ckpt = ckpt_pass()
@@ -82,7 +82,7 @@ def case(B, n_elem, steps, reps):
 
         def sweep():
             lamd.copy_(lamd0)
-            ens._implicit_adjoint(ckpt, lamd, steps, H, N_ITER, 0.0, desc, every, None, True)
+            ens._sweep(_IMPLICIT, ckpt, lamd, steps, 0.0, (H, N_ITER), desc, every, None, True)
 
         out[f"adjoint_{D}_cot_us_per_step"] = 1e3 * timed(sweep, reps) / steps
     # (b) one gradient per simulated second, implicit and RK4

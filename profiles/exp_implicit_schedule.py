@@ -28,7 +28,7 @@ for p in (TREE, os.path.join(TREE, "continuum-robot_amd")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-from continuum_robot.batched import BeamEnsemble  # noqa: E402
+from continuum_robot.batched import _IMPLICIT, BeamEnsemble  # noqa: E402
 from continuum_robot.models.force_params import ForceParams  # noqa: E402
 from tests.helpers import nitinol_columns  # noqa: E402
 
@@ -86,14 +86,14 @@ def case(B, n_elem, steps, reps, scheduled):
 
         def ckpt_pass():
             x.copy_(x0)
-            return ens._implicit_checkpoint(x, steps, H, N_ITER, 0.0, desc, every, None, *extra)
+            return ens._checkpoint_pass(_IMPLICIT, x, steps, 0.0, (H, N_ITER), desc, every, None, *extra)
 
         put(f"checkpoint_pass_{name}", timed(ckpt_pass, reps))
         ckpt = ckpt_pass()
 
         def sweep():
             lamd.copy_(lamd0)
-            ens._implicit_adjoint(ckpt, lamd, steps, H, N_ITER, 0.0, desc, every, None, True, *extra)
+            ens._sweep(_IMPLICIT, ckpt, lamd, steps, 0.0, (H, N_ITER), desc, every, None, True, *extra)
 
         put(f"adjoint_1_cot_{name}", timed(sweep, reps))
         del keep

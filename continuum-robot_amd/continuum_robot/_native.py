@@ -234,6 +234,13 @@ def load():
     L.crb_implicit_feedback_work_bytes.restype = C.c_size_t
     L.crb_implicit_feedback_work_bytes.argtypes = [vp]
     L.crb_implicit_feedback_path.argtypes = [vp]
+    L.crb_implicit_feedback_adjoint_work_bytes.restype = C.c_size_t
+    L.crb_implicit_feedback_adjoint_work_bytes.argtypes = [vp, i32, i32, i32, i32]
+    L.crb_step_implicit_feedback_checkpoint.argtypes = [vp, vp, C.c_double, C.c_double, i32, i32, i32, i32, vp, vp,
+                                                        C.POINTER(InputDesc), C.POINTER(RecordDesc), vp, vp, vp, _dp, vp]
+    L.crb_step_implicit_feedback_adjoint.argtypes = [vp, vp, vp, vp, i32, C.c_double, C.c_double, i32, i32, i32, i32, vp, vp,
+                                                     C.POINTER(InputDesc), C.POINTER(RecordDesc), C.POINTER(FeedbackCotangent),
+                                                     C.POINTER(InputCotangent), vp, vp]
     _lib = L
     return L
 

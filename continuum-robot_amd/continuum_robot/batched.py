@@ -891,13 +891,21 @@ class BeamEnsemble:
 
     def checkpoint_interval(self, n_steps: int, checkpoint_every: Optional[int] = None,
                             param_cotangents: Optional[int] = None, feedback_cotangents: Optional[int] = None,
-                            implicit: Optional[Tuple[int, int]] = None) -> int:
+                            implicit: Optional[Tuple[int, int]] = None,
+                            implicit_feedback: Optional[Tuple[int, int, int]] = None) -> int:
         """Steps per checkpoint segment of an adjoint rollout: ``checkpoint_every``, or ceil(sqrt(n_steps)) lowered until the
         work buffer of crb_step_rk4_adjoint (crb_rk4_adjoint_work_bytes) fits ADJOINT_WORK_BUDGET.  ``param_cotangents``: the
         number of cotangents of a ``step_adjoint_params`` call, whose work buffer
         (crb_rk4_adjoint_params_work_bytes) is sized instead; ``feedback_cotangents``: that of a ``step_feedback_adjoint`` call
         (crb_rk4_feedback_adjoint_work_bytes); ``implicit`` = (n_iter, n_cot): that of a ``step_implicit_adjoint`` call
-        (crb_implicit_adjoint_work_bytes)."""
+        (crb_implicit_adjoint_work_bytes); ``implicit_feedback`` = (n_iter, hold, n_cot): that of a
+        ``step_implicit_feedback_adjoint`` call (crb_implicit_feedback_adjoint_work_bytes), whose segments are whole samples:
+        ceil(sqrt(n_steps)) rounded up to a multiple of ``hold`` and lowered by ``hold`` while the buffer exceeds the budget
+        (ValueError if one sample per segment does not fit); a given ``checkpoint_every`` must be a multiple of ``hold``."""
+        if implicit_feedback is not None:
+            if implicit is not None or param_cotangents is not None or feedback_cotangents is not None:
+                raise ValueError("checkpoint_interval: implicit_feedback and another family's argument are given together")
+            return self._implicit_feedback_interval(n_steps, checkpoint_every, *implicit_feedback)
         if checkpoint_every is not None:   # (given: no family's work buffer is sized)
             return self._interval(None, n_steps, checkpoint_every, (), 1)
         if implicit is not None:
@@ -1197,6 +1205,95 @@ class BeamEnsemble:
                     every=self.checkpoint_interval(n_steps, checkpoint_every, feedback_cotangents=1))
         xT, samples = _FeedbackRollout.apply(self, opts, x0, K, ref)
         return (xT, samples) if record is not None else xT
+
+    # ------------------------------------------------- adjoint of the sampled-data implicit loop (crb_implicit_feedback_adjoint.h)
+    def _implicit_feedback_interval(self, n_steps, checkpoint_every, n_iter, hold, n_cot):
+        """checkpoint_interval(implicit_feedback=(n_iter, hold, n_cot)): segments of whole samples"""
+        hold = int(hold)
+        if checkpoint_every is not None:
+            every = int(checkpoint_every)
+            if every < 1 or every % hold != 0:
+                raise ValueError(f"checkpoint_every = {checkpoint_every} must be a positive multiple of hold = {hold} "
+                                 f"(a checkpoint sits on a sample start)")
+            return every
+
+        def nbytes(every):
+            return int(self._lib.crb_implicit_feedback_adjoint_work_bytes(self.plan.h, every, int(n_iter), hold, int(n_cot)))
+
+        every = -(-max(1, int(np.ceil(np.sqrt(max(int(n_steps), 1))))) // hold) * hold
+        while every > hold and nbytes(every) > self.ADJOINT_WORK_BUDGET:
+            every -= hold
+        if nbytes(every) > self.ADJOINT_WORK_BUDGET:
+            raise ValueError(f"step_implicit_feedback_adjoint: the work buffer of one sample per checkpoint segment "
+                             f"({nbytes(every)} bytes at hold = {hold}) exceeds ADJOINT_WORK_BUDGET = {self.ADJOINT_WORK_BUDGET}")
+        return every
+
+    def _implicit_feedback_args(self, gain, hold, record, who):
+        """the argument errors step_implicit_feedback_adjoint and rollout_implicit_feedback share; returns hold as an int"""
+        if isinstance(gain, (list, tuple)):
+            self._feedback_gain(gain, who)
+        if int(hold) != hold or int(hold) < 1:
+            raise ValueError(f"{who}: hold must be an integer >= 1 (implicit steps per sample)")
+        if record is not None and isinstance(record, str):
+            raise NotImplementedError(f"{who}: whole-state snapshots (record='all') are not available in the differentiable loop")
+        return int(hold)
+
+    def step_implicit_feedback_adjoint(self, n_steps: int, h: float, lam_red, gain, reference=None, hold: int = 1,
+                                       n_iter: int = 2, x0_red=None, impulse_amp=None, impulse_duration: float = 0.01,
+                                       impulse_index: int = -2, held_force=None, t0: Optional[float] = None, record=None,
+                                       record_every: int = 1, lam_record=None, checkpoint_every: Optional[int] = None,
+                                       want_gain: bool = True):
+        """Gradient of a scalar loss through the digital loop of ``step_implicit_feedback`` -- u_k = held_force + K (r - x_k),
+        sampled every ``hold`` implicit steps of size ``h`` and held -- in ONE backward sweep
+        (crb_step_implicit_feedback_checkpoint + crb_step_implicit_feedback_adjoint): for the cotangent ``lam_red`` = dL/dx(T)
+        (reduced [B, 2n], or D cotangents [D, B, 2n]) and, with ``record`` = (node, name) as in step_implicit_feedback,
+        ``lam_record`` = dL/d samples, returns (xbar0 [B, 2n], gain_bar [n, 2n], ref_bar [B, 2n], amp_bar [B] or None without
+        an impulse, f_held_bar [B, n]), each with a leading D axis when ``lam_red`` has one.  ``gain`` [n, 2n] is one gain for
+        the ensemble (a list raises NotImplementedError); ``reference`` [B, 2n] or None (= 0; ref_bar is returned all the
+        same).  The derivative is the exact transpose of the discrete map: ``n_iter`` modified-Newton iterations per step,
+        every sample's first step started from the zero iterate.  The rollout starts at ``x0_red`` (None: the resident
+        state) and clock ``t0`` (None: ``time``) and always runs as the chain (one product and one launch per sample);
+        ``state``, ``time`` and ``status`` are left alone.  ``checkpoint_every``: steps per checkpoint segment, a multiple of
+        ``hold`` (ValueError otherwise; checkpoint_interval(implicit_feedback=...)); no result depends on it, bitwise.
+        ``want_gain=False`` skips the gain gradient (gain_bar is None; the other returns are bitwise the same).  A non-finite
+        cotangent of one beam stays in that beam's rows of xbar0, ref_bar and f_held_bar; it reaches gain_bar, a sum over the
+        beams.  fp64 ensembles with one free-DOF set.  Not available: the damped variant, per-beam gain groups, gradients
+        with respect to the rod's own parameters."""
+        who = "step_implicit_feedback_adjoint"
+        hold = self._implicit_feedback_args(gain, hold, record, who)
+        lam = torch.as_tensor(lam_red)
+        every = self._implicit_feedback_interval(n_steps, checkpoint_every, n_iter, hold, lam.shape[0] if lam.dim() == 3 else 1)
+        return self._rollout_adjoint(_IMPLICIT_FEEDBACK, n_steps, (h, n_iter, hold, gain, reference, want_gain), lam_red,
+                                     x0_red, impulse_amp, impulse_duration, impulse_index, held_force, t0, record,
+                                     record_every, lam_record, every)
+
+    def rollout_implicit_feedback(self, x0_red, n_steps: int, h: float, gain, reference=None, hold: int = 1, n_iter: int = 2,
+                                  impulse_amp=None, held_force=None, impulse_duration: float = 0.01, impulse_index: int = -2,
+                                  t0: float = 0.0, record=None, record_every: int = 1,
+                                  checkpoint_every: Optional[int] = None, return_control: bool = False):
+        """A differentiable digital loop: x(T) reduced [B, 2n] from ``x0_red`` after ``n_steps`` implicit steps of
+        ``step_implicit_feedback``'s map (then the ``record`` = (node, name) samples [B, n_steps // record_every] when
+        ``record`` is given, then with ``return_control`` the held input of every sample, ``control`` [K, B, n],
+        non-differentiable), as a torch.autograd.Function whose backward is crb_step_implicit_feedback_adjoint:
+        ``loss.backward()`` reaches whichever of ``x0_red``, ``gain`` [n, 2n], ``reference`` [B, 2n], ``impulse_amp`` [B] and
+        ``held_force`` [B, n] require grad -- tuning the gain of a 1 kHz regulator on the nonlinear rod at h = 1e-3 s
+        (examples/tune_digital_gain.py).  The forward is the checkpoint pass (the chain; it agrees with
+        step_implicit_feedback to rounding), whose checkpoints and controls backward reuses.  Leaves ``state``, ``time`` and
+        ``status`` alone.  fp64 ensembles with one free-DOF set; once differentiable."""
+        who = "rollout_implicit_feedback"
+        hold = self._implicit_feedback_args(gain, hold, record, who)
+        every = self._implicit_feedback_interval(n_steps, checkpoint_every, n_iter, hold, 1)
+        x0 = torch.as_tensor(x0_red, dtype=self.dtype, device=self.device)
+        K = torch.as_tensor(gain, dtype=self.dtype, device=self.device)
+        ref = None if reference is None else torch.as_tensor(reference, dtype=self.dtype, device=self.device)
+        amp = None if impulse_amp is None else torch.as_tensor(impulse_amp, dtype=self.dtype, device=self.device)
+        held = None if held_force is None else torch.as_tensor(held_force, dtype=self.dtype, device=self.device)
+        opts = dict(n_steps=int(n_steps), h=float(h), n_iter=int(n_iter), hold=hold, t0=float(t0),
+                    duration=float(impulse_duration), index=int(impulse_index), record=record,
+                    record_every=int(record_every), every=every)
+        xT, samples, control = _ImplicitFeedbackRollout.apply(self, opts, x0, K, ref, amp, held)
+        out = (xT,) + ((samples,) if record is not None else ()) + ((control,) if return_control else ())
+        return out if len(out) > 1 else xT
 
     def step_implicit(self, n_steps: int, h: float, n_iter: int = 2, impulse_amp=None, impulse_duration: float = 0.01,
                       impulse_index: int = -2, held_force=None, t0: Optional[float] = None, record=None,
@@ -1979,6 +2076,52 @@ _FEEDBACK = _AdjointFamily(
     unpack=lambda ens, outs, sd: tuple(outs))
 
 
+def _implicit_feedback_prepare(ens, n_steps, args, held_force, impulse_amp, record):
+    h, n_iter, hold, gain, reference, want_gain = args
+    K = ens._feedback_gain(gain, "step_implicit_feedback_adjoint")
+    ref = None if reference is None else ens._dev(reference, (ens.n_beams, 2 * ens.n))
+    n_samples = max(1, -(-int(n_steps) // int(hold)))
+    u_ckpt = torch.zeros((n_samples, ens.n_beams, ens.n_node, 4), dtype=ens.dtype, device=ens.device)
+    return (h, n_iter, hold, K, ref, u_ckpt), held_force, None, (want_gain, impulse_amp is not None)
+
+
+def _implicit_feedback_checkpoint(ens, x, ckpt, n_steps, every, t0, step, desc, sd, rec, t_end):
+    h, n_iter, hold, K, ref, u_ckpt = step
+    work = ens._work_buffer(_IMPLICIT_FEEDBACK, every, step, 1)
+    return ens._lib.crb_step_implicit_feedback_checkpoint(ens.plan.h, ens._ptr(x), t0, float(h), n_steps, int(n_iter), int(hold),
+                                                          every, ens._ptr(K), ens._ptr(ref), C.byref(desc), ens._ref(rec),
+                                                          ens._ptr(ckpt), ens._ptr(u_ckpt), ens._ptr(work), C.byref(t_end),
+                                                          ens._stream()), work
+
+
+def _implicit_feedback_outputs(ens, D, want, sd):
+    """[gain_bar [D, n, 2n] or None, ref_bar [D, B, 2n], amp_bar [D, B] or None, f_held_bar [D, B, n_node, 4]];
+    ``want`` = (the gain gradient, the amplitude's)"""
+    return _feedback_outputs(ens, D, want[0], sd) + _input_outputs(ens, D, want[1], sd)
+
+
+def _implicit_feedback_sweep(ens, ckpt, lamd, n_steps, every, t0, step, desc, sd, rec_bar, outs, work):
+    h, n_iter, hold, K, ref, u_ckpt = step
+    grad = nat.FeedbackCotangent()
+    grad.gain_bar = outs[0].data_ptr() if outs[0] is not None else None
+    grad.ref_bar = outs[1].data_ptr()
+    igrad, _ = _input_cotangent(ens, outs[2:], None)
+    return ens._lib.crb_step_implicit_feedback_adjoint(ens.plan.h, ens._ptr(ckpt), ens._ptr(u_ckpt), ens._ptr(lamd),
+                                                       int(lamd.shape[0]), t0, float(h), n_steps, int(n_iter), int(hold), every,
+                                                       ens._ptr(K), ens._ptr(ref), C.byref(desc), ens._ref(rec_bar),
+                                                       C.byref(grad), C.byref(igrad), ens._ptr(work), ens._stream())
+
+
+# step = (h, n_iter, hold, gain [n, 2n], reference [B, 2n] or None, u_ckpt [K, B, n_node, 4]) on the device: the pass fills
+# u_ckpt, the sweep's recompute reads it as its schedule; a segment's checkpoint is the implicit adjoint's
+_IMPLICIT_FEEDBACK = _AdjointFamily(
+    who="step_implicit_feedback_adjoint", prepare=_implicit_feedback_prepare, ckpt_shape=_IMPLICIT.ckpt_shape,
+    work_bytes=lambda ens, every, step, n_cot: ens._lib.crb_implicit_feedback_adjoint_work_bytes(
+        ens.plan.h, every, int(step[1]), int(step[2]), n_cot),
+    checkpoint=_implicit_feedback_checkpoint, outputs=_implicit_feedback_outputs, sweep=_implicit_feedback_sweep,
+    unpack=lambda ens, outs, sd: (outs[0], outs[1], outs[2], ens._unpack_force_dirs(outs[3])))
+
+
 def _rollout_result(ctx, ens, opts, x, samples):
     """what a rollout's forward returns: x(T) reduced and the samples (without a record an empty placeholder that takes no
     gradient)"""
@@ -2065,6 +2208,51 @@ class _FeedbackRollout(torch.autograd.Function):
         ggain = gain_bar[0] if ctx.needs_input_grad[3] else None
         gref = ref_bar[0] if (ctx.has_ref and ctx.needs_input_grad[4]) else None
         return None, None, gx0, ggain, gref
+
+
+class _ImplicitFeedbackRollout(torch.autograd.Function):
+    """BeamEnsemble.rollout_implicit_feedback: forward = crb_step_implicit_feedback_checkpoint, backward =
+    crb_step_implicit_feedback_adjoint on the saved checkpoints and controls"""
+
+    @staticmethod
+    def forward(ctx, ens, opts, x0, gain, ref, amp, held):
+        amp_d, held_d = (None if v is None else v.detach() for v in (amp, held))
+        step, _, _, _ = _implicit_feedback_prepare(ens, opts["n_steps"], (opts["h"], opts["n_iter"], opts["hold"], gain,
+                                                                          None if ref is None else ref.detach(), True),
+                                                   held_d, amp_d, opts["record"])
+        desc, keep = ens._input_desc(amp_d, opts["duration"], opts["index"], held_d)
+        x = ens.pack_state(x0.detach())
+        rec, samples = ens._record_desc(opts["record"], opts["n_steps"], opts["record_every"])
+        ckpt = ens._checkpoint_pass(_IMPLICIT_FEEDBACK, x, opts["n_steps"], opts["t0"], step, desc, opts["every"], rec)
+        ens._keep += keep + [samples]
+        ctx.ens, ctx.opts = ens, opts
+        ctx.has = tuple(v is not None for v in (ref, amp, held))
+        ctx.save_for_backward(ckpt, step[3], step[4], step[5], amp_d, held_d)
+        n_samples = -(-opts["n_steps"] // opts["hold"])
+        control = (ens._unpack_force_dirs(step[5][:n_samples]) if n_samples > 0 else
+                   torch.zeros((0, ens.n_beams, ens.n), dtype=ens.dtype, device=ens.device))
+        ctx.mark_non_differentiable(control)
+        return _rollout_result(ctx, ens, opts, x, samples) + (control,)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_x, g_samples, g_control):
+        ens, o = ctx.ens, ctx.opts
+        ckpt, K, r, u_ckpt, amp, held = ctx.saved_tensors
+        has_ref, has_amp, has_held = ctx.has
+        desc, keep = ens._input_desc(amp, o["duration"], o["index"], held)
+        lamd, rec_bar, cot = _rollout_seed(ens, o, g_x, g_samples)
+        need = ctx.needs_input_grad
+        gain_bar, ref_bar, amp_bar, f_bar = ens._sweep(_IMPLICIT_FEEDBACK, ckpt, lamd, o["n_steps"], o["t0"],
+                                                       (o["h"], o["n_iter"], o["hold"], K, r, u_ckpt), desc, o["every"],
+                                                       rec_bar, (need[3], has_amp))
+        ens._keep += keep + [cot]
+        gx0 = ens._unpack_dirs(lamd)[0] if need[2] else None
+        ggain = gain_bar[0] if need[3] else None
+        gref = ref_bar[0] if (has_ref and need[4]) else None
+        gamp = amp_bar[0] if (has_amp and need[5]) else None
+        gheld = ens._unpack_force_dirs(f_bar)[0] if (has_held and need[6]) else None
+        return None, None, gx0, ggain, gref, gamp, gheld
 
 
 class _Equilibrium(torch.autograd.Function):

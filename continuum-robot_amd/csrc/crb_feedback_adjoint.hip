@@ -28,11 +28,14 @@ hipError_t launch_feedback_gain_grad(const FeedbackAdjParams& p, hipStream_t st)
     if (p.ref) hipLaunchKernelGGL(crb_feedback_gain_grad_kernel<true>, grid, dim3(256), 0, st, q);
     else hipLaunchKernelGGL(crb_feedback_gain_grad_kernel<false>, grid, dim3(256), 0, st, q);
     if (hipError_t e = hipGetLastError()) return e;
-    if (q.slices > 1) {
-        const size_t per_cot = size_t(p.n) * size_t(p.n2), total = per_cot * size_t(n_cot);
-        hipLaunchKernelGGL(crb_feedback_gain_reduce_kernel, dim3(unsigned((total + 255) / 256)), dim3(256), 0, st, q.gain_bar, q.partial,
-                           per_cot, q.slices, total);
-    }
+    return q.slices > 1 ? launch_feedback_gain_reduce(q.gain_bar, q.partial, p.n, n_cot, q.slices, st) : hipSuccess;
+}
+
+hipError_t launch_feedback_gain_reduce(double* gain_bar, const double* partial, int n, int n_cot, int slices, hipStream_t st) {
+    if (!gain_bar || !partial || n < 1 || n_cot < 1 || slices < 1) return hipErrorInvalidValue;
+    const size_t per_cot = size_t(n) * size_t(2 * n), total = per_cot * size_t(n_cot);
+    hipLaunchKernelGGL(crb_feedback_gain_reduce_kernel, dim3(unsigned((total + 255) / 256)), dim3(256), 0, st, gain_bar, partial, per_cot,
+                       slices, total);
     return hipGetLastError();
 }
 

@@ -43,6 +43,8 @@ hipError_t launch_feedback_transpose(const FeedbackAdjParams& p, hipStream_t st)
 // crb_feedback_gain_grad_kernel on a grid of ceil(n / 32) x ceil(2n / 32) * slices x n_cot workgroups (p.rows = n_cot * p.B,
 // slices = feedback_gain_grad_slices(p.B, p.n)), then with slices > 1 crb_feedback_gain_reduce_kernel over p.partial
 hipError_t launch_feedback_gain_grad(const FeedbackAdjParams& p, hipStream_t st);
+// crb_feedback_gain_reduce_kernel alone: gain_bar [n_cot][n][2n] += partial [n_cot][slices][n][2n], the slices in ascending order
+hipError_t launch_feedback_gain_reduce(double* gain_bar, const double* partial, int n, int n_cot, int slices, hipStream_t st);
 // crb_feedback_seed_kernel over total = rows * x_stride entries
 hipError_t launch_feedback_seed(double* lam, double* seed, size_t total, size_t x_stride, double c, const double* rec_bar,
                                 size_t rec_off, int rec_n, int kr, hipStream_t st);

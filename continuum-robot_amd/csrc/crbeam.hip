@@ -23,6 +23,7 @@
 #include "crb_implicit_tangent_launch.h"
 #include "crb_implicit_feedback_launch.h"
 #include "crb_feedback_adjoint_launch.h"
+#include "crb_implicit_feedback_adjoint_launch.h"
 #include "crb_host.h"
 #include "crb_blocked.h"
 
@@ -2290,6 +2291,21 @@ int implicit_feedback_fused(const crb_plan* p, void* x, double t0, double h, int
     return CRB_OK;
 #endif
 }
+// The slice of a call's recording that the launch of one sample takes (steps s .. s + hs - 1 of the call): `every` divides hold
+// (hs / every samples) or is a multiple of it (one sample at the end of every (every / hold)-th whole sample).  plane2: doubles
+// of one whole-state snapshot.
+Recording sample_recording(const Recording& rec, int s, int hs, int hold, size_t plane2) {
+    Recording rs;
+    if (!rec.out) return rs;
+    long first = -1;
+    if (hold % rec.every == 0) {
+        if (hs / rec.every > 0) { rs = rec; first = s / rec.every; }
+    } else if (hs == hold && (s + hold) % rec.every == 0) {
+        rs = rec; rs.every = hold; first = (s + hold) / rec.every - 1;
+    }
+    if (first >= 0) rs.out = static_cast<double*>(rec.out) + size_t(first) * (rec.slot == REC_ALL_SLOTS ? plane2 : size_t(1));
+    return rs;
+}
 int implicit_feedback_chain(const crb_plan* p, void* x, double t0, double h, int n_steps, int n_iter, int hold, const void* gain,
                             const void* ref, const Forcing& f, const Recording& rec, void* u_out, void* work, hipStream_t st) {
     if (int rc = stiff_tables<double>(p, 0.25 * h * h, st)) return rc;
@@ -2312,19 +2328,7 @@ int implicit_feedback_chain(const crb_plan* p, void* x, double t0, double h, int
                                               size_t(p->n_node) * 4, st));
         Forcing fs = f;
         fs.held = u;
-        // the sample's slice of the recording: `every` divides hold (hs / every samples) or is a multiple of it (one sample at
-        // the end of every (every / hold)-th whole sample)
-        Recording rs;
-        if (rec.out) {
-            long first = -1;
-            if (hold % rec.every == 0) {
-                if (hs / rec.every > 0) { rs = rec; first = s / rec.every; }
-            } else if (hs == hold && (s + hold) % rec.every == 0) {
-                rs = rec; rs.every = hold; first = (s + hold) / rec.every - 1;
-            }
-            if (first >= 0)
-                rs.out = static_cast<double*>(rec.out) + size_t(first) * (rec.slot == REC_ALL_SLOTS ? plane2 : size_t(1));
-        }
+        const Recording rs = sample_recording(rec, s, hs, hold, plane2);
         KParams<double> k = base_params<double>(p);
         k.x = static_cast<double*>(x);
         set_io(k, fs, &rs);
@@ -3467,4 +3471,229 @@ extern "C" int crb_step_rk4_feedback_adjoint(const crb_plan* p, const void* ckpt
         }
         return CRB_OK;
     });
+}
+
+// ------------------------------------------------------------------ adjoint of the sampled-data implicit loop
+// (crb_implicit_feedback_adjoint.h): the implicit adjoint's launches per sample, the boundary products between them
+namespace {
+// CRB_EINVAL checks of the sizes both calls share, in the documented order
+int imp_fb_adjoint_arg_checks(const std::string& who, int n_cot, int n_steps, int every, int hold, int n_iter, double h) {
+    if (int rc = check_count(who, "n_cot", n_cot)) return rc;
+    if (n_steps < 0) return fail(CRB_EINVAL, who + ": n_steps must be >= 0");
+    if (every < 1) return fail(CRB_EINVAL, who + ": every must be >= 1");
+    if (hold < 1) return fail(CRB_EINVAL, who + ": hold must be >= 1");
+    if (every % hold != 0) return fail(CRB_EINVAL, who + ": every must be a multiple of hold (a checkpoint sits on a sample start)");
+    if (n_iter < 1 || n_iter > IMP_ADJ_MAX_ITER) return fail(CRB_EINVAL, who + ": n_iter must be in [1, 16]");
+    if (!(h > 0)) return fail(CRB_EINVAL, who + ": h must be positive");
+    return CRB_OK;
+}
+// the record and the input of both calls (CRB_EINVAL), then what the plan cannot do (CRB_EUNSUPPORTED), then the device
+int imp_fb_adjoint_io_checks(const crb_plan* p, const std::string& who, const crb_record_desc* rec, const crb_input_desc* in,
+                             int n_steps, int hold, bool amp_bar, Recording* r, Forcing* f) {
+    if (int rc = decode_record(p, rec, n_steps, true, who.c_str(), r)) return rc;
+    if (rec && hold % rec->every != 0 && rec->every % hold != 0)
+        return fail(CRB_EINVAL, who + ": the record stride must divide hold or be a multiple of it");
+    if (int rc = decode_input(p, in, who.c_str(), f)) return rc;
+    if (amp_bar && !f->impulse)
+        return fail(CRB_EINVAL, who + ": amp_bar needs an impulse input (its amplitude is what it differentiates)");
+    if (int rc = imp_adjoint_plan_checks(p, who)) return rc;
+    if (p->mixed_topology)
+        return fail(CRB_EUNSUPPORTED, who + ": one gain matrix for the ensemble needs one free-DOF set (the plan has mixed topology)");
+    if (rec && rec->node == CRB_RECORD_ALL)
+        return fail(CRB_EUNSUPPORTED, who + ": rec with CRB_RECORD_ALL (whole-state snapshots) is not supported in the differentiable loop");
+    return need_device(p, who.c_str());
+}
+// The work buffer (crb_implicit_feedback_adjoint_work_bytes), in doubles: the implicit adjoint's (imp_adj_work), then ubar of
+// every sample of a segment [n_cot][every / hold] force records, then the gain gradient's running partial tiles.
+struct ImpFbAdjWork {
+    ImpAdjWork imp;
+    double *ubar, *partial;
+};
+ImpFbAdjWork imp_fb_adj_work(const crb_plan* p, void* work, int every, int n_iter, int hold, int n_cot) {
+    ImpFbAdjWork w;
+    w.imp = imp_adj_work(p, work, every, n_iter);
+    w.ubar = w.imp.carry + size_t(n_cot) * force_doubles(p);
+    w.partial = w.ubar + size_t(n_cot) * size_t(every / hold) * force_doubles(p);
+    return w;
+}
+}  // namespace
+
+extern "C" size_t crb_implicit_feedback_adjoint_work_bytes(const crb_plan* p, int every, int n_iter, int hold, int n_cot) {
+    if (!p || every < 1 || hold < 1 || every % hold != 0 || n_iter < 1 || n_iter > IMP_ADJ_MAX_ITER || n_cot < 1 || n_cot > 65535)
+        return 0;
+    const size_t F = force_doubles(p);
+    return (size_t(every) * ((2 + size_t(n_iter)) * F + 1) + size_t(n_cot) * (1 + size_t(every / hold)) * F +
+            fb_adj_partial_doubles(p, n_cot)) * sizeof(double);
+}
+
+extern "C" int crb_step_implicit_feedback_checkpoint(const crb_plan* p, void* x, double t0, double h, int n_steps, int n_iter,
+                                                     int hold, int every, const void* gain, const void* ref,
+                                                     const crb_input_desc* in, const crb_record_desc* rec, void* ckpt,
+                                                     void* u_ckpt, void* work, double* t_end, void* stream) {
+    const std::string who("crb_step_implicit_feedback_checkpoint");
+    if (!p) return fail(CRB_EINVAL, who + ": null plan");
+    if (!x || !gain || !ckpt || !u_ckpt || !work) return fail(CRB_EINVAL, who + ": null x, gain, ckpt, u_ckpt or work");
+    const void* const outs[4] = {x, ckpt, u_ckpt, work};
+    const void* const ins[4] = {gain, ref, rec ? rec->out : nullptr, in ? in->f_held : nullptr};
+    for (int i = 0; i < 4; ++i) {
+        for (const void* b : ins)
+            if (b && b == outs[i]) return fail(CRB_EINVAL, who + ": x, ckpt, u_ckpt and work must not alias gain, ref, rec->out or input->f_held");
+        for (int j = i + 1; j < 4; ++j)
+            if (outs[j] == outs[i]) return fail(CRB_EINVAL, who + ": x, ckpt, u_ckpt and work must not alias each other");
+    }
+    if (int rc = imp_fb_adjoint_arg_checks(who, 1, n_steps, every, hold, n_iter, h)) return rc;
+    Recording r;
+    Forcing f;
+    if (int rc = imp_fb_adjoint_io_checks(p, who, rec, in, n_steps, hold, false, &r, &f)) return rc;
+    if (t_end) *t_end = clock_after(t0, h, n_steps);
+    if (n_steps == 0) return CRB_OK;
+    if (int rc = ensure_gadj(p, who.c_str())) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    KParams<double> base;
+    if (int rc = imp_adjoint_params(p, h, st, &base)) return rc;
+    base.x = static_cast<double*>(x);
+    const size_t F = force_doubles(p);
+    // entries of a force record that the product does not write (constrained DOFs, the padding component) read as zero
+    HIP_TRY(hipMemsetAsync(u_ckpt, 0, size_t((n_steps + hold - 1) / hold) * F * sizeof(double), st));
+    ImpAdjParams<double> iq = zeroed<ImpAdjParams<double>>();
+    iq.n_iter = n_iter;
+    double t = t0;
+    for (int s = 0, ks = 0; s < n_steps; s += hold, ++ks) {
+        const int hs = n_steps - s < hold ? n_steps - s : hold;
+        double* const u = static_cast<double*>(u_ckpt) + size_t(ks) * F;
+        if (int rc = feedback_force_impl<double>(p, x, gain, ref, u, st)) return rc;
+        if (f.held)
+            HIP_TRY(crb::launch_feedback_held(u, static_cast<const double*>(f.held), p->d_row_off, p->n_free, p->B, size_t(p->n_node) * 4, st));
+        Forcing fs = f;
+        fs.held = u;
+        const Recording rs = sample_recording(r, s, hs, hold, state_doubles(p));
+        KParams<double> k = base;
+        set_io(k, fs, &rs);
+        k.t0 = t; k.n_steps = hs;
+        // one launch per sample: it starts from a^0 = 0 and stores the state it starts from -- into the checkpoint where the
+        // sample opens a segment (every is a multiple of hold), else into the head of the work buffer, where nothing reads it
+        void* const start = s % every == 0 ? static_cast<double*>(ckpt) + size_t(s / every) * 3 * F : static_cast<double*>(work);
+        HIP_TRY(crb::launch_imp_adj_checkpoint(k, checkpoint_params(p, start, hold), iq, beam_groups(p), p->NT, st));
+        t = clock_after(t, h, hs);
+    }
+    return CRB_OK;
+}
+
+extern "C" int crb_step_implicit_feedback_adjoint(const crb_plan* p, const void* ckpt, const void* u_ckpt, void* lam, int n_cot,
+                                                  double t0, double h, int n_steps, int n_iter, int hold, int every,
+                                                  const void* gain, const void* ref, const crb_input_desc* in,
+                                                  const crb_record_desc* rec_bar, const crb_feedback_cotangent* grad,
+                                                  const crb_input_cotangent* igrad, void* work, void* stream) {
+    const std::string who("crb_step_implicit_feedback_adjoint");
+    if (!p) return fail(CRB_EINVAL, who + ": null plan");
+    if (!ckpt || !u_ckpt || !lam || !gain || !work) return fail(CRB_EINVAL, who + ": null ckpt, u_ckpt, lam, gain or work");
+    if (!grad) return fail(CRB_EINVAL, who + ": grad is null (crb_feedback_cotangent; its members may be null)");
+    void* const amp_bar = igrad ? igrad->amp_bar : nullptr;
+    void* const f_bar = igrad ? igrad->f_held_bar : nullptr;
+    const void* const outs[5] = {lam, grad->gain_bar, grad->ref_bar, amp_bar, f_bar};
+    const char* const out_names[5] = {"lam", "grad->gain_bar", "grad->ref_bar", "igrad->amp_bar", "igrad->f_held_bar"};
+    const void* const ins[7] = {ckpt, u_ckpt, work, gain, ref, rec_bar ? rec_bar->out : nullptr, in ? in->f_held : nullptr};
+    for (int i = 0; i < 5; ++i) {
+        if (!outs[i]) continue;
+        for (const void* b : ins)
+            if (b && b == outs[i])
+                return fail(CRB_EINVAL, who + ": " + out_names[i] + " must not alias ckpt, u_ckpt, work, gain, ref, rec_bar->out or input->f_held");
+        for (int j = i + 1; j < 5; ++j)
+            if (outs[j] == outs[i]) return fail(CRB_EINVAL, who + ": " + out_names[i] + " must not alias " + out_names[j]);
+    }
+    if (work == ckpt || work == u_ckpt || work == gain || work == ref || ckpt == u_ckpt)
+        return fail(CRB_EINVAL, who + ": work, ckpt and u_ckpt must not alias each other, gain or ref");
+    if (int rc = imp_fb_adjoint_arg_checks(who, n_cot, n_steps, every, hold, n_iter, h)) return rc;
+    Recording r;
+    Forcing f;
+    if (int rc = imp_fb_adjoint_io_checks(p, who, rec_bar, in, n_steps, hold, amp_bar != nullptr, &r, &f)) return rc;
+    if (n_steps == 0) return CRB_OK;
+    if (int rc = ensure_gadj(p, who.c_str())) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    KParams<double> base;
+    if (int rc = imp_adjoint_params(p, h, st, &base)) return rc;
+    Forcing fs = f;
+    fs.held = nullptr;   // (the held force is inside every u_k: the recompute reads u_ckpt as its schedule)
+    set_io(base, fs);
+    const size_t F = force_doubles(p), S = state_doubles(p);
+    const int per_seg = every / hold, slices = crb::feedback_gain_grad_slices(p->B, p->n_free);
+    const ImpFbAdjWork w = imp_fb_adj_work(p, work, every, n_iter, hold, n_cot);
+    Schedule sc;
+    sc.f = u_ckpt; sc.K = (n_steps + hold - 1) / hold; sc.hold = hold;
+    ImpAdjParams<double> iter = zeroed<ImpAdjParams<double>>();
+    iter.n_iter = n_iter;
+
+    ImpFbAdjParams q = zeroed<ImpFbAdjParams>();
+    q.cot_stride = size_t(per_seg) * F;
+    q.sample_stride = F;
+    q.col_off = p->d_col_off;
+    q.row_off = p->d_row_off;
+    q.rows = n_cot * p->B; q.B = p->B; q.n = p->n_free; q.n2 = 2 * p->n_free;
+    q.x_stride = size_t(2) * p->n_node * 4;
+    q.u_stride = size_t(p->n_node) * 4;
+    q.gain = static_cast<const double*>(gain);
+    q.lam = static_cast<double*>(lam);
+    q.ref_bar = static_cast<double*>(grad->ref_bar);
+    q.f_held_bar = static_cast<double*>(f_bar);
+    q.xs = w.imp.states;
+    q.xs_stride = size_t(hold) * S;
+    q.ref = static_cast<const double*>(ref);
+    q.gain_bar = static_cast<double*>(grad->gain_bar);
+    q.partial = w.partial;
+    if (q.gain_bar && slices > 1)   // the slices' running tiles persist across the segments of the call
+        HIP_TRY(hipMemsetAsync(w.partial, 0, fb_adj_partial_doubles(p, n_cot) * sizeof(double), st));
+
+    const int rc = for_segments_reversed(n_steps, every, t0, h, [&](int g, int k0, int n, double tg) -> int {
+        // 1. the segment's step data from its checkpoint: the scheduled recompute with f_sched = u_ckpt (every sample's first
+        //    step starts from a^0 = 0, as the pass's launch per sample did)
+        KParams<double> k = base;
+        k.t0 = tg;
+        k.n_steps = n;
+        set_sched(p, k, sc, k0);
+        AdjParams<double> qs = adj_params(p);
+        qs.states = w.imp.states;
+        qs.clocks = w.imp.clock;
+        ImpAdjParams<double> iq = iter;
+        iq.start = static_cast<const double*>(ckpt) + size_t(g) * 3 * F;
+        iq.iters_out = w.imp.iters;
+        HIP_TRY(crb::launch_imp_adj_segment(k, qs, iq, beam_groups(p), p->NT, st));
+        // 2. per sample, last first: the sweep over its steps (ubar_k into the sample's slot, which it accumulates into),
+        //    then the boundary
+        const int ns = (n + hold - 1) / hold;
+        HIP_TRY(hipMemsetAsync(w.ubar, 0, size_t(n_cot) * size_t(per_seg) * F * sizeof(double), st));
+        for (int j = ns - 1; j >= 0; --j) {
+            const int i0 = j * hold, hs = n - i0 < hold ? n - i0 : hold;
+            KParams<double> kb = base;
+            kb.n_steps = hs;
+            set_sched(p, kb, sc, k0 + i0);
+            set_record(kb, r);
+            AdjParams<double> b = adj_params(p);
+            b.work = w.imp.states + size_t(i0) * S;
+            b.work_clock = w.imp.clock + i0;
+            b.lam = static_cast<double*>(lam);
+            b.amp_bar = static_cast<double*>(amp_bar);
+            b.f_bar = w.ubar + size_t(j) * F;
+            b.fbar_cot_stride = q.cot_stride;
+            b.step0 = k0 + i0;
+            ImpAdjParams<double> ib = iter;
+            ib.iters = w.imp.iters + size_t(i0) * size_t(n_iter) * F;
+            ib.carry = w.imp.carry;
+            ib.carry_in = 0;   // (the launch ends a sample: the next sample's a^0 = 0 is a constant)
+            HIP_TRY(crb::launch_imp_adj_backward(kb, b, ib, beam_groups(p), n_cot, p->NT, st));
+            ImpFbAdjParams qb = q;
+            qb.ubar = w.ubar + size_t(j) * F;
+            HIP_TRY(crb::launch_imp_fb_boundary(qb, st));
+        }
+        // 3. the gain gradient of the segment's samples in one launch
+        if (q.gain_bar) {
+            ImpFbAdjParams qg = q;
+            qg.ubar = w.ubar;
+            qg.n_samples = ns;
+            HIP_TRY(crb::launch_imp_fb_gain_grad(qg, st));
+        }
+        return CRB_OK;
+    });
+    if (rc) return rc;
+    if (q.gain_bar && slices > 1) HIP_TRY(crb::launch_feedback_gain_reduce(q.gain_bar, w.partial, p->n_free, n_cot, slices, st));
+    return CRB_OK;
 }

@@ -747,12 +747,86 @@ int crb_step_implicit_tangent_sched(const crb_plan* plan, void* x, void* dx, int
  * plan, x, gain or work, n_steps < 0, h <= 0, n_iter < 1, hold < 1, a bad record or a record stride that neither divides hold
  * nor is a multiple of it, a bad input description; then CRB_EUNSUPPORTED for fp32 plans, beams of more than 256 thread-carried
  * nodes, ensembles of mixed topology or per-beam free-DOF sets; then CRB_ENODEV for host-only plans.  n_steps == 0 sets *t_end
- * and returns CRB_OK.  Not covered: per-beam gain groups, the damped variant, the adjoint of this map. */
+ * and returns CRB_OK.  Not covered: per-beam gain groups, the damped variant.  The adjoint of this map:
+ * crb_step_implicit_feedback_adjoint below. */
 int crb_step_implicit_feedback(const crb_plan* plan, void* x, double t0, double h, int n_steps, int n_iter, int hold,
                                const void* gain, const void* ref, const crb_input_desc* input, const crb_record_desc* rec,
                                void* u_out, void* work, double* t_end, void* stream);
 size_t crb_implicit_feedback_work_bytes(const crb_plan* plan);
 int crb_implicit_feedback_path(const crb_plan* plan);   /* 0 chain, 1 in-kernel */
+
+/* ---- Adjoint of the sampled-data implicit loop: gradients of a rollout of crb_step_implicit_feedback with respect to the start
+ * state, the gain, the reference, the impulse amplitude and the held force, in one backward sweep -- tuning the digital gain
+ * that runs at h = 1e-3 s on the nonlinear rod (examples/tune_digital_gain.py).
+ *
+ * The map, sample k over steps k * hold ... (k + 1) * hold - 1:  u_k = f_held + K (r - x_k) in reduced ordering,
+ * x_{k+1} = Phi(x_k, u_k) = the sample's implicit-midpoint steps with f_held = u_k, the first step's iteration started from
+ * a^0 = 0 (one crb_step_implicit call per sample; one interval of a crb_input_schedule).
+ * Its transpose, last sample first, with lambda = dL/dx_{k+1} plus the cotangents of the samples recorded inside the interval:
+ *   the implicit sweep over the sample's steps (crb_step_implicit_adjoint's kernel) gives lambda' = (dPhi/dx)^T lambda,
+ *   ubar_k = (dPhi/du)^T lambda and the amp_bar contributions; a^0 = 0 is a constant, so the cotangent carried through the
+ *   starting iterate is dropped at the sample's first step (the launch that ends a sample starts with carry_in = 0);
+ *   P = ubar_k,red . K            [rows x n] . [n x 2n], rows = n_cot * B
+ *   dL/dx_k = lambda' - P,   ref_bar += P,   f_held_bar += ubar_k,   gain_bar += sum_b ubar_k,b (x) (r_b - x_k,b).
+ *
+ * crb_implicit_feedback_adjoint_work_bytes: device bytes of the work buffer of the two calls.  With F = B * n_node * 4 doubles
+ * (a force record), in this order:
+ *   every * 2F, every * n_iter * F, every   a segment's step start states, iterates and clocks (crb_implicit_adjoint_work_bytes)
+ *   n_cot * F                               the cotangent of the starting iterate the sweep's launches write
+ *   n_cot * (every / hold) * F              ubar_k of every sample of a segment, [n_cot][every / hold][B][n_node][4]
+ *   n_cot * Z * n * 2n                      the gain gradient's running partial tiles, only when its beam reduction runs in Z > 1
+ *                                           slices (Z as in crb_rk4_feedback_adjoint_work_bytes)
+ * = (every ((2 + n_iter) F + 1) + n_cot (1 + every / hold) F + [Z > 1] n_cot Z n 2n) * sizeof(double).  0 for a NULL plan,
+ * every < 1, hold < 1, every not a multiple of hold, n_iter outside 1 .. 16 or n_cot outside 1 .. 65535.
+ *
+ * crb_step_implicit_feedback_checkpoint: the forward pass in the adjoint's own arithmetic, ALWAYS as the chain (whatever
+ * crb_implicit_feedback_path says): per sample crb_feedback_force plus the held force into record k of u_ckpt, then one
+ * checkpoint launch of the implicit adjoint's kernel over the sample's steps.  x agrees with crb_step_implicit_feedback to
+ * rounding, not bitwise.
+ *   every    steps per checkpoint segment, a multiple of hold: a checkpoint always sits on a sample start
+ *   ckpt     device [ceil(n_steps / every)][B][3][n_node][4]: (q, v, starting iterate) at steps 0, every, ...; the third plane
+ *            holds zeros (a sample starts from a^0 = 0)
+ *   u_ckpt   device [ceil(n_steps / hold)][B][n_node][4], required: u_k of every sample, laid out as u_out of
+ *            crb_step_implicit_feedback (zeros at constrained DOFs and padding) -- the schedule the adjoint's recompute reads
+ *   rec      one DOF, its stride a divisor or a multiple of hold (may be NULL); CRB_RECORD_ALL: CRB_EUNSUPPORTED
+ *   work     crb_implicit_feedback_adjoint_work_bytes(plan, every, n_iter, hold, 1) bytes are enough
+ * Does not write per-beam status (crb_plan_set_status).
+ *
+ * crb_step_implicit_feedback_adjoint: the adjoint of the rollout the pass ran from t0 (the same h, n_steps, n_iter, hold, every,
+ * gain, ref and input), for n_cot cotangents:
+ *   lam      device [n_cot][B][2][n_node][4], in place: dL/dx(T) on entry, dL/dx(0) on exit
+ *   rec_bar  the record of the pass with out = its cotangent [n_cot][B][n_rec], or NULL
+ *   grad     gain_bar += dL/dK (NULL skips its product; the other results are bitwise unchanged), ref_bar += dL/d ref
+ *   igrad    amp_bar += dL/d amp (needs an impulse), f_held_bar += dL/d f_held [n_cot][B][n_node][4]; either or igrad may be NULL
+ * Per segment, last to first: one scheduled recompute launch from the checkpoint (f_sched = u_ckpt, this hold); per sample,
+ * last first, one sweep launch over its steps that writes ubar_k into the sample's slot of work, and one boundary launch
+ * (P on v_mfma_f64_16x16x4_f64, lam -= P, ref_bar += P, f_held_bar += ubar_k); then ONE gain-gradient launch for all samples of the
+ * segment, each workgroup adding every sample's beam reduction to a running tile in sweep order.  The beam reduction of large
+ * ensembles runs in slices whose tiles persist in work across the segments and are summed in ascending order at the end of
+ * the call.  No floating-point atomics; every sum has a fixed order: lam and every cotangent are bitwise independent of
+ * `every`, D cotangents in one call are bitwise D calls of one, and two identical calls agree bitwise.  A non-finite cotangent
+ * of one beam stays in that beam's rows of lam, ref_bar and f_held_bar; it reaches gain_bar (a sum over beams).
+ *
+ * Refusals, all before the device is touched, crb_last_error() naming the entry point and the argument, in this order:
+ * CRB_EINVAL for a NULL plan or buffer (the pass: x, gain, ckpt, u_ckpt, work; the adjoint: ckpt, u_ckpt, lam, gain, work, grad);
+ * aliasing (the pass: x, ckpt, u_ckpt, work against each other, gain, ref, rec->out, input->f_held; the adjoint: lam, gain_bar,
+ * ref_bar, amp_bar, f_held_bar against ckpt, u_ckpt, work, gain, ref or each other); n_cot outside 1 .. 65535; n_steps < 0;
+ * every < 1; hold < 1; every % hold != 0; n_iter outside 1 .. 16; h <= 0; a bad record, or a record stride that neither divides
+ * hold nor is a multiple of it; a bad input; amp_bar without an impulse.  Then CRB_EUNSUPPORTED for fp32 plans, beams of more
+ * than 256 thread-carried nodes, ensembles of mixed topology, CRB_RECORD_ALL.  Then CRB_ENODEV for host-only plans.
+ * n_steps == 0 returns CRB_OK and, in the pass, sets *t_end.
+ * Not covered: an in-kernel sweep for gains that fit LDS (the adjoint is always the chain), per-beam gain groups, the damped
+ * variant, parameter gradients, checkpoint segments shorter than a sample. */
+size_t crb_implicit_feedback_adjoint_work_bytes(const crb_plan* plan, int every, int n_iter, int hold, int n_cot);
+int crb_step_implicit_feedback_checkpoint(const crb_plan* plan, void* x, double t0, double h, int n_steps, int n_iter, int hold,
+                                          int every, const void* gain, const void* ref, const crb_input_desc* input,
+                                          const crb_record_desc* rec, void* ckpt, void* u_ckpt, void* work, double* t_end,
+                                          void* stream);
+int crb_step_implicit_feedback_adjoint(const crb_plan* plan, const void* ckpt, const void* u_ckpt, void* lam, int n_cot,
+                                       double t0, double h, int n_steps, int n_iter, int hold, int every, const void* gain,
+                                       const void* ref, const crb_input_desc* input, const crb_record_desc* rec_bar,
+                                       const crb_feedback_cotangent* grad, const crb_input_cotangent* igrad, void* work,
+                                       void* stream);
 
 /* out[b] = x[b][plane][node][dof]  (e.g. tip displacement = plane 0, node n_elem, dof 1;
  * lqr_control.py:168) */

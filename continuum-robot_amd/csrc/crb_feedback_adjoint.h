@@ -5,34 +5,17 @@
 // kbar) at a stage state X the cotangent of the stage is
 //     s = xbar - P,   P = ubar_red . K          [rows x n] . [n x 2n]      (crb_feedback_transpose_kernel)
 //     ref_bar += P,   gain_bar += sum_b ubar_red,b (x) (r_b - X_red,b)      [n x B] . [B x 2n]  (crb_feedback_gain_grad_kernel)
-// rows = n_cot * B (cotangent c, beam b).  Both follow crb_feedback_kernel (crb_feedback.h): 256 threads, a 32 x 32 output tile,
-// each wave one 16 x 16 MFMA tile, K in steps of 32; the global loads of step s + 1 are issued before the MFMAs of step s and
-// stored to LDS after them.  ONE LDS stage (two barriers per step), not two: a K step here is 8 MFMAs per wave against a
-// gather whose latency is several times that, so what hides the latency is other workgroups -- at 21 - 25 KB of LDS six of
-// them share a CU (measured at 2048 x 128 elements: the transposed product 49 us against 73 with two stages; the gain gradient
-// 74 us in six slices against 177 with two stages and one slice -- DESIGN 10).  For the same reason the gain gradient's beam
-// reduction is split over blockIdx.y slices once the output tiles alone do not fill the chip (feedback_gain_grad_slices: a
-// function of B and n only); the slices' partial tiles are summed in ascending order by crb_feedback_gain_reduce_kernel.
-// Every load is unconditional: rows, columns and K indices out of range read a clamped address and are zeroed by a select (the
-// transposed product's A rows out of range are never stored, and its K tail is zeroed on the gain side: a non-finite value of
-// a row stays in that row).
-// LDS tiles: [row][k] with 32 + 2 doubles per row where the global operand is contiguous along k (the gathered ubar of the
-// transposed product), [k][col] with 32 + 16 doubles per row where it is contiguous along the output index (the gain, the
-// state, ubar^T): lanes 0 .. 31 of a fragment read (two k rows of 16 columns) then touch each bank once.
-// No atomics: every output element is owned by one lane of one workgroup, and the beam reduction of the gain gradient runs
-// in ascending order inside a slice and over the slices, so the results are bitwise reproducible and do not depend on n_cot.
+// rows = n_cot * B (cotangent c, beam b).  The tile, the LDS layouts, the clamped loads and why they are what they are, and the
+// loop of the transposed product: crb_feedback_adjoint_tile.h.  Here a row's ubar is record m of one [rows] array, and the
+// epilogue keeps the books of the RK4 stages.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "crb_feedback_adjoint_launch.h"
-#include "crb_feedback_adjoint_tile.h"   // FBA_T, FBA_LDK, FBA_LDM, FBA_Q, fba_acc_t, fba_mma
+#include "crb_feedback_adjoint_tile.h"
 #include "crb_generic.h"
 
 namespace crb {
-
-__host__ __device__ constexpr size_t feedback_transpose_lds_bytes(int n) {
-    return size_t(FBA_T) * (FBA_LDK + FBA_LDM) * sizeof(double) + size_t(n) * sizeof(int32_t);
-}
 
 // P = ubar_red . K; per free-DOF entry of the state layout: s = xbar - P, sum (+)= s, then seed = ca lam + cb s, or with
 // p.last lam += sum; ref_bar += P.  Grid: (ceil(rows / 32), ceil(2n / 32)).
@@ -41,58 +24,14 @@ __global__ void __launch_bounds__(256) crb_feedback_transpose_kernel(const Feedb
     double* const As = reinterpret_cast<double*>(crb_smem);            // [32][FBA_LDK]
     double* const Bs = As + FBA_T * FBA_LDK;                           // [32][FBA_LDM]
     int32_t* const roff_s = reinterpret_cast<int32_t*>(Bs + FBA_T * FBA_LDM);   // [n]
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int m0 = blockIdx.x * FBA_T, n0 = blockIdx.y * FBA_T;
-    const int wm = (wave >> 1) * 16, wn = (wave & 1) * 16;
-    for (int k = t; k < p.n; k += 256) roff_s[k] = p.row_off[k];
-    // loader: A column lc of rows lr + 8 q (contiguous along k); B column lc of K rows lr + 8 q (contiguous along j)
-    const int lc = t & (FBA_T - 1), lr = t / FBA_T;
-    const double* arow[FBA_Q];
-#pragma unroll
-    for (int q = 0; q < FBA_Q; ++q) {
-        const int m = m0 + lr + 8 * q;
-        arow[q] = p.ubar + size_t(m < p.rows ? m : p.rows - 1) * p.u_stride;
-    }
-    const bool jok = n0 + lc < p.n2;
-    const double* const bcol = p.gain + (jok ? n0 + lc : 0);
-    __syncthreads();   // roff_s
-    double ra[FBA_Q], rb[FBA_Q];
-    auto fetch = [&](int k0) {
-        const int ka = k0 + lc;
-        const int ro = roff_s[ka < p.n ? ka : 0];
-#pragma unroll
-        for (int q = 0; q < FBA_Q; ++q) ra[q] = arow[q][ro];
-#pragma unroll
-        for (int q = 0; q < FBA_Q; ++q) {
-            const int kb = k0 + lr + 8 * q;
-            const double v = bcol[size_t(kb < p.n ? kb : 0) * p.n2];
-            rb[q] = (kb < p.n && jok) ? v : 0.0;
-        }
-    };
-    auto stash = [&]() {
-#pragma unroll
-        for (int q = 0; q < FBA_Q; ++q) {
-            As[(lr + 8 * q) * FBA_LDK + lc] = ra[q];
-            Bs[(lr + 8 * q) * FBA_LDM + lc] = rb[q];
-        }
-    };
-    fba_acc_t acc = {0.0, 0.0, 0.0, 0.0};
-    const int nsteps = (p.n + FBA_T - 1) / FBA_T;
-    fetch(0);
-    for (int s = 0; s < nsteps; ++s) {
-        stash();
-        __syncthreads();
-        if (s + 1 < nsteps) fetch((s + 1) * FBA_T);   // (uniform; in flight during the MFMAs)
-        acc = fba_mma<FBA_LDK, 1>(As, Bs, wm, wn, lane, acc);
-        __syncthreads();   // (the next stash overwrites what this step read)
-    }
-    // epilogue: D row (cotangent, beam) = (lane >> 4) + 4 reg, D col (reduced state index) = lane & 15
-    const int j = n0 + wn + (lane & 15);
+    const FbaTile w = fba_product_tile();
+    const fba_acc_t acc = fba_transposed_product(p, w, As, Bs, roff_s, [&](int m) { return p.ubar + size_t(m) * p.u_stride; });
+    const int j = w.j();
     if (j >= p.n2) return;
     const int coff = p.col_off[j];
 #pragma unroll
     for (int reg = 0; reg < 4; ++reg) {
-        const int m = m0 + wm + MfmaOps<double>::row(lane, reg);
+        const int m = w.row(reg);
         if (m >= p.rows) continue;
         const size_t idx = size_t(m) * p.x_stride + coff;
         const double P = acc[reg];

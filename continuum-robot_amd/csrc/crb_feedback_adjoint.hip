@@ -3,15 +3,9 @@
 #include "crb_host.h"
 
 namespace crb {
-namespace {
-bool fba_shape_ok(const FeedbackAdjParams& p) {
-    return p.rows >= 1 && p.B >= 1 && p.n >= 1 && p.n2 == 2 * p.n && p.rows % p.B == 0 && p.rows / p.B <= 65535;
-}
-}  // namespace
-
 hipError_t launch_feedback_transpose(const FeedbackAdjParams& p, hipStream_t st) {
     if (!fba_shape_ok(p)) return hipErrorInvalidValue;
-    const size_t smem = feedback_transpose_lds_bytes(p.n);
+    const size_t smem = fba_product_lds_bytes(p.n);
     if (hipError_t e = lds_opt_in(crb_feedback_transpose_kernel, smem)) return e;
     const dim3 grid((p.rows + FBA_T - 1) / FBA_T, (p.n2 + FBA_T - 1) / FBA_T);
     hipLaunchKernelGGL(crb_feedback_transpose_kernel, grid, dim3(256), smem, st, p);

@@ -7,12 +7,11 @@
 //     P = ubar_k,red . K        [rows x n] . [n x 2n]                              crb_imp_fb_boundary_kernel, once per sample
 //     dL/dx_k = lambda' - P,   ref_bar += P,   f_held_bar += ubar_k
 //     gain_bar += sum_b ubar_k,b (x) (r_b - x_k,b)   [n x B] . [B x 2n]            crb_imp_fb_gain_grad_kernel, once per segment
-// Both follow the products of the RK4 loop's adjoint (crb_feedback_adjoint.h: tile, LDS layouts, one LDS stage, unconditional
-// clamped loads zeroed by selects; crb_feedback_adjoint_tile.h).
+// Both follow the products of the RK4 loop's adjoint (crb_feedback_adjoint_tile.h: tile, LDS layouts, one LDS stage, unconditional
+// clamped loads zeroed by selects, and the loop of the transposed product itself).
 //
 // The boundary kernel has its own epilogue on lambda in place and adds ubar_k to f_held_bar from the workgroups of the first
-// column tile, which own their 32 rows: no operand passes through a zero-filled buffer.  The K tail is zeroed on the gain side,
-// so a non-finite ubar of one row stays in that row.
+// column tile, which own their 32 rows: no operand passes through a zero-filled buffer.
 //
 // The gain gradient is batched over the samples of a checkpoint segment: at the sizes the loop is tuned at (64 beams) one
 // sample's product is two K steps and a launch per sample would be all launch cost.  A workgroup owns one output tile of one
@@ -21,7 +20,7 @@
 // slice) or from the slice's partial tile (several; zeroed at the start of the call, summed into gain_bar in ascending order
 // by crb_feedback_gain_reduce_kernel at its end) and is written back when the launch ends.  The additions and their order are
 // the same however the samples fall into segments: gain_bar does not depend on the checkpoint interval, bitwise.  r_b - x_k,b
-// is formed in the loader from the segment's recomputed step-start states.  No atomics.
+// is formed in the loader from the segment's recomputed step-start states.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -30,10 +29,6 @@
 
 namespace crb {
 
-__host__ __device__ constexpr size_t imp_fb_boundary_lds_bytes(int n) {
-    return size_t(FBA_T) * (FBA_LDK + FBA_LDM) * sizeof(double) + size_t(n) * sizeof(int32_t);
-}
-
 // P = ubar_red . K; lam -= P on the free-DOF entries of the state layout, ref_bar += P; blockIdx.y == 0: f_held_bar += ubar on
 // the free-DOF entries of the rows of this tile.  Grid: (ceil(rows / 32), ceil(2n / 32)).
 __global__ void __launch_bounds__(256) crb_imp_fb_boundary_kernel(const ImpFbAdjParams p) {
@@ -41,72 +36,28 @@ __global__ void __launch_bounds__(256) crb_imp_fb_boundary_kernel(const ImpFbAdj
     double* const As = reinterpret_cast<double*>(crb_smem);            // [32][FBA_LDK]
     double* const Bs = As + FBA_T * FBA_LDK;                           // [32][FBA_LDM]
     int32_t* const roff_s = reinterpret_cast<int32_t*>(Bs + FBA_T * FBA_LDM);   // [n]
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int m0 = blockIdx.x * FBA_T, n0 = blockIdx.y * FBA_T;
-    const int wm = (wave >> 1) * 16, wn = (wave & 1) * 16;
-    for (int k = t; k < p.n; k += 256) roff_s[k] = p.row_off[k];
+    const FbaTile w = fba_product_tile();
     // the force record of row m = (cotangent, beam) of this sample
     auto urow = [&](int m) {
         const int c = m / p.B;
         return p.ubar + size_t(c) * p.cot_stride + size_t(m - c * p.B) * p.u_stride;
     };
-    // loader: A column lc of rows lr + 8 q (contiguous along k); B column lc of K rows lr + 8 q (contiguous along j)
-    const int lc = t & (FBA_T - 1), lr = t / FBA_T;
-    const double* arow[FBA_Q];
-#pragma unroll
-    for (int q = 0; q < FBA_Q; ++q) {
-        const int m = m0 + lr + 8 * q;
-        arow[q] = urow(m < p.rows ? m : p.rows - 1);
-    }
-    const bool jok = n0 + lc < p.n2;
-    const double* const bcol = p.gain + (jok ? n0 + lc : 0);
-    __syncthreads();   // roff_s
-    double ra[FBA_Q], rb[FBA_Q];
-    auto fetch = [&](int k0) {
-        const int ka = k0 + lc;
-        const int ro = roff_s[ka < p.n ? ka : 0];
-#pragma unroll
-        for (int q = 0; q < FBA_Q; ++q) ra[q] = arow[q][ro];
-#pragma unroll
-        for (int q = 0; q < FBA_Q; ++q) {
-            const int kb = k0 + lr + 8 * q;
-            const double v = bcol[size_t(kb < p.n ? kb : 0) * p.n2];
-            rb[q] = (kb < p.n && jok) ? v : 0.0;
-        }
-    };
-    auto stash = [&]() {
-#pragma unroll
-        for (int q = 0; q < FBA_Q; ++q) {
-            As[(lr + 8 * q) * FBA_LDK + lc] = ra[q];
-            Bs[(lr + 8 * q) * FBA_LDM + lc] = rb[q];
-        }
-    };
-    fba_acc_t acc = {0.0, 0.0, 0.0, 0.0};
-    const int nsteps = (p.n + FBA_T - 1) / FBA_T;
-    fetch(0);
-    for (int s = 0; s < nsteps; ++s) {
-        stash();
-        __syncthreads();
-        if (s + 1 < nsteps) fetch((s + 1) * FBA_T);   // (uniform; in flight during the MFMAs)
-        acc = fba_mma<FBA_LDK, 1>(As, Bs, wm, wn, lane, acc);
-        __syncthreads();   // (the next stash overwrites what this step read)
-    }
+    const fba_acc_t acc = fba_transposed_product(p, w, As, Bs, roff_s, urow);
     // f_held_bar += ubar: the first column tile owns the force records of its rows (wave-uniform branch)
     if (p.f_held_bar && blockIdx.y == 0) {
-        const int mrows = min(FBA_T, p.rows - m0);
-        for (int e = t; e < mrows * p.n; e += 256) {
+        const int m0 = w.m0, mrows = min(FBA_T, p.rows - m0);
+        for (int e = w.t; e < mrows * p.n; e += 256) {
             const int r = e / p.n, off = roff_s[e - r * p.n];
             double* const d = p.f_held_bar + size_t(m0 + r) * p.u_stride + off;
             *d = *d + urow(m0 + r)[off];
         }
     }
-    // epilogue: D row (cotangent, beam) = (lane >> 4) + 4 reg, D col (reduced state index) = lane & 15
-    const int j = n0 + wn + (lane & 15);
+    const int j = w.j();
     if (j >= p.n2) return;
     const int coff = p.col_off[j];
 #pragma unroll
     for (int reg = 0; reg < 4; ++reg) {
-        const int m = m0 + wm + MfmaOps<double>::row(lane, reg);
+        const int m = w.row(reg);
         if (m >= p.rows) continue;
         const size_t idx = size_t(m) * p.x_stride + coff;
         const double P = acc[reg];

@@ -1,19 +1,12 @@
 // crb_implicit_feedback_adjoint.hip -- the sample-boundary kernels of the adjoint of the sampled-data implicit loop
 // (crb_implicit_feedback_adjoint.h), one translation unit of their own.
 #include "crb_implicit_feedback_adjoint.h"
-#include "crb_feedback_adjoint_launch.h"   // feedback_gain_grad_slices
 #include "crb_host.h"
 
 namespace crb {
-namespace {
-bool ifba_shape_ok(const ImpFbAdjParams& p) {
-    return p.ubar && p.rows >= 1 && p.B >= 1 && p.n >= 1 && p.n2 == 2 * p.n && p.rows % p.B == 0 && p.rows / p.B <= 65535;
-}
-}  // namespace
-
 hipError_t launch_imp_fb_boundary(const ImpFbAdjParams& p, hipStream_t st) {
-    if (!ifba_shape_ok(p) || !p.gain || !p.lam) return hipErrorInvalidValue;
-    const size_t smem = imp_fb_boundary_lds_bytes(p.n);
+    if (!p.ubar || !fba_shape_ok(p) || !p.gain || !p.lam) return hipErrorInvalidValue;
+    const size_t smem = fba_product_lds_bytes(p.n);
     if (hipError_t e = lds_opt_in(crb_imp_fb_boundary_kernel, smem)) return e;
     const dim3 grid((p.rows + FBA_T - 1) / FBA_T, (p.n2 + FBA_T - 1) / FBA_T);
     hipLaunchKernelGGL(crb_imp_fb_boundary_kernel, grid, dim3(256), smem, st, p);
@@ -21,7 +14,7 @@ hipError_t launch_imp_fb_boundary(const ImpFbAdjParams& p, hipStream_t st) {
 }
 
 hipError_t launch_imp_fb_gain_grad(const ImpFbAdjParams& p, hipStream_t st) {
-    if (!ifba_shape_ok(p) || !p.xs || p.n_samples < 1) return hipErrorInvalidValue;
+    if (!p.ubar || !fba_shape_ok(p) || !p.xs || p.n_samples < 1) return hipErrorInvalidValue;
     ImpFbAdjParams q = p;
     q.slices = feedback_gain_grad_slices(p.B, p.n);
     if (q.slices > 1 ? !q.partial : !q.gain_bar) return hipErrorInvalidValue;

@@ -3313,6 +3313,35 @@ int fb_adj_checks(const crb_plan* p, int n_cot, const void* gain, const crb_inpu
     return CRB_OK;
 }
 
+// no output of a differentiable closed-loop call may be one of its inputs (`ins_text` names them) or another output
+template <size_t NO, size_t NI>
+int fb_adj_alias_checks(const std::string& who, const void* const (&outs)[NO], const char* const (&out_names)[NO],
+                        const void* const (&ins)[NI], const char* ins_text) {
+    for (size_t i = 0; i < NO; ++i) {
+        if (!outs[i]) continue;
+        for (const void* b : ins)
+            if (b && b == outs[i]) return fail(CRB_EINVAL, who + ": " + out_names[i] + " must not alias " + ins_text);
+        for (size_t j = i + 1; j < NO; ++j)
+            if (outs[j] == outs[i]) return fail(CRB_EINVAL, who + ": " + out_names[i] + " must not alias " + out_names[j]);
+    }
+    return CRB_OK;
+}
+
+// what the matrix kernels of both closed-loop adjoints read of the plan and the call (ubar, xs and partial are the loop's own)
+void fba_params(FbaParams& q, const crb_plan* p, int n_cot, const void* gain, const void* ref, void* lam,
+                const crb_feedback_cotangent* grad) {
+    q.col_off = p->d_col_off;
+    q.row_off = p->d_row_off;
+    q.rows = n_cot * p->B; q.B = p->B; q.n = p->n_free; q.n2 = 2 * p->n_free;
+    q.x_stride = size_t(2) * p->n_node * 4;
+    q.u_stride = size_t(p->n_node) * 4;
+    q.gain = static_cast<const double*>(gain);
+    q.lam = static_cast<double*>(lam);
+    q.ref_bar = static_cast<double*>(grad->ref_bar);
+    q.ref = static_cast<const double*>(ref);
+    q.gain_bar = static_cast<double*>(grad->gain_bar);
+}
+
 // one RK4 step of the stage-split closed loop from xcur (advanced in place): feedback_rollout's launches (plus the held
 // disturbance, if any, added to each stage's force), the stage states
 // X_2 .. X_4 written to s1 .. s3 (stage 3's unused xs_next goes to `spare`)
@@ -3391,14 +3420,7 @@ extern "C" int crb_step_rk4_feedback_adjoint(const crb_plan* p, const void* ckpt
     const void* const outs[3] = {lam, grad->gain_bar, grad->ref_bar};
     const char* const out_names[3] = {"lam", "grad->gain_bar", "grad->ref_bar"};
     const void* const ins[6] = {ckpt, work, gain, ref, rec_bar ? rec_bar->out : nullptr, in ? in->f_held : nullptr};
-    for (int i = 0; i < 3; ++i) {
-        if (!outs[i]) continue;
-        for (const void* b : ins)
-            if (b && b == outs[i])
-                return fail(CRB_EINVAL, who + ": " + out_names[i] + " must not alias ckpt, work, gain, ref, rec_bar->out or input->f_held");
-        for (int j = i + 1; j < 3; ++j)
-            if (outs[j] == outs[i]) return fail(CRB_EINVAL, who + ": " + out_names[i] + " must not alias " + out_names[j]);
-    }
+    if (int rc = fb_adj_alias_checks(who, outs, out_names, ins, "ckpt, work, gain, ref, rec_bar->out or input->f_held")) return rc;
     if (work == ckpt || work == gain || work == ref) return fail(CRB_EINVAL, who + ": work must not alias ckpt, gain or ref");
     if (int rc = need_device(p, who.c_str())) return rc;
     Recording r;
@@ -3415,20 +3437,11 @@ extern "C" int crb_step_rk4_feedback_adjoint(const crb_plan* p, const void* ckpt
     const size_t rec_off = rec_on ? (size_t(r.comp / 3) * p->n_node + size_t(r.slot + p->off)) * 4 + size_t(r.comp % 3) : 0;
 
     FeedbackAdjParams q = zeroed<FeedbackAdjParams>();
+    fba_params(q, p, n_cot, gain, ref, lam, grad);
     q.ubar = w.ubar;
-    q.col_off = p->d_col_off;
-    q.row_off = p->d_row_off;
-    q.rows = n_cot * p->B; q.B = p->B; q.n = p->n_free; q.n2 = 2 * p->n_free;
-    q.x_stride = x_stride;
-    q.u_stride = size_t(p->n_node) * 4;
-    q.gain = static_cast<const double*>(gain);
     q.xbar = w.xbar;
-    q.lam = static_cast<double*>(lam);
     q.sum = w.sum;
     q.seed = w.seed;
-    q.ref_bar = static_cast<double*>(grad->ref_bar);
-    q.ref = static_cast<const double*>(ref);
-    q.gain_bar = static_cast<double*>(grad->gain_bar);
     q.partial = w.partial;
     // the seeds of DESIGN 10: kbar4 = dt/6 l+, kbar3 = dt/3 l+ + dt s4, kbar2 = dt/3 l+ + dt/2 s3, kbar1 = dt/6 l+ + dt/2 s2;
     // the launch after stage s forms the seed of stage s - 1
@@ -3593,14 +3606,8 @@ extern "C" int crb_step_implicit_feedback_adjoint(const crb_plan* p, const void*
     const void* const outs[5] = {lam, grad->gain_bar, grad->ref_bar, amp_bar, f_bar};
     const char* const out_names[5] = {"lam", "grad->gain_bar", "grad->ref_bar", "igrad->amp_bar", "igrad->f_held_bar"};
     const void* const ins[7] = {ckpt, u_ckpt, work, gain, ref, rec_bar ? rec_bar->out : nullptr, in ? in->f_held : nullptr};
-    for (int i = 0; i < 5; ++i) {
-        if (!outs[i]) continue;
-        for (const void* b : ins)
-            if (b && b == outs[i])
-                return fail(CRB_EINVAL, who + ": " + out_names[i] + " must not alias ckpt, u_ckpt, work, gain, ref, rec_bar->out or input->f_held");
-        for (int j = i + 1; j < 5; ++j)
-            if (outs[j] == outs[i]) return fail(CRB_EINVAL, who + ": " + out_names[i] + " must not alias " + out_names[j]);
-    }
+    if (int rc = fb_adj_alias_checks(who, outs, out_names, ins, "ckpt, u_ckpt, work, gain, ref, rec_bar->out or input->f_held"))
+        return rc;
     if (work == ckpt || work == u_ckpt || work == gain || work == ref || ckpt == u_ckpt)
         return fail(CRB_EINVAL, who + ": work, ckpt and u_ckpt must not alias each other, gain or ref");
     if (int rc = imp_fb_adjoint_arg_checks(who, n_cot, n_steps, every, hold, n_iter, h)) return rc;
@@ -3624,21 +3631,12 @@ extern "C" int crb_step_implicit_feedback_adjoint(const crb_plan* p, const void*
     iter.n_iter = n_iter;
 
     ImpFbAdjParams q = zeroed<ImpFbAdjParams>();
+    fba_params(q, p, n_cot, gain, ref, lam, grad);
     q.cot_stride = size_t(per_seg) * F;
     q.sample_stride = F;
-    q.col_off = p->d_col_off;
-    q.row_off = p->d_row_off;
-    q.rows = n_cot * p->B; q.B = p->B; q.n = p->n_free; q.n2 = 2 * p->n_free;
-    q.x_stride = size_t(2) * p->n_node * 4;
-    q.u_stride = size_t(p->n_node) * 4;
-    q.gain = static_cast<const double*>(gain);
-    q.lam = static_cast<double*>(lam);
-    q.ref_bar = static_cast<double*>(grad->ref_bar);
     q.f_held_bar = static_cast<double*>(f_bar);
     q.xs = w.imp.states;
     q.xs_stride = size_t(hold) * S;
-    q.ref = static_cast<const double*>(ref);
-    q.gain_bar = static_cast<double*>(grad->gain_bar);
     q.partial = w.partial;
     if (q.gain_bar && slices > 1)   // the slices' running tiles persist across the segments of the call
         HIP_TRY(hipMemsetAsync(w.partial, 0, fb_adj_partial_doubles(p, n_cot) * sizeof(double), st));

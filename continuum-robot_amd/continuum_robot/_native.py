@@ -89,6 +89,12 @@ class FeedbackCotangent(C.Structure):
     _fields_ = [("gain_bar", C.c_void_p), ("ref_bar", C.c_void_p)]
 
 
+class FeedbackTangent(C.Structure):
+    """crb_feedback_tangent: per-direction derivatives of the closed loop's gain ([n_dir][n][2n]) and reference ([n_dir][B][2n]
+    reduced), device pointers or None"""
+    _fields_ = [("d_gain", C.c_void_p), ("d_ref", C.c_void_p)]
+
+
 class RecordDesc(C.Structure):
     _fields_ = [("plane", C.c_int32), ("node", C.c_int32), ("dof", C.c_int32), ("every", C.c_int32), ("out", C.c_void_p)]
 
@@ -241,6 +247,11 @@ def load():
     L.crb_step_implicit_feedback_adjoint.argtypes = [vp, vp, vp, vp, i32, C.c_double, C.c_double, i32, i32, i32, i32, vp, vp,
                                                      C.POINTER(InputDesc), C.POINTER(RecordDesc), C.POINTER(FeedbackCotangent),
                                                      C.POINTER(InputCotangent), vp, vp]
+    L.crb_implicit_feedback_tangent_work_bytes.restype = C.c_size_t
+    L.crb_implicit_feedback_tangent_work_bytes.argtypes = [vp, i32]
+    L.crb_step_implicit_feedback_tangent.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, i32, i32, i32, vp, vp,
+                                                     C.POINTER(FeedbackTangent), C.POINTER(InputDesc), C.POINTER(InputTangent),
+                                                     vp, vp, vp, _dp, vp]
     _lib = L
     return L
 

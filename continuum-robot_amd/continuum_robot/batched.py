@@ -813,8 +813,8 @@ class BeamEnsemble:
         step's iteration and its tangent starting from the previous step's iterate, from 0 at the first step of a call and of
         every schedule interval -- the map whose transpose step_implicit_adjoint applies; not of the converged midpoint rule.
         The base state agrees with step_implicit to rounding, not bitwise.  fp64 ensembles only.
-        Not available: the damped variant (``rho_inf`` < 1), tangents of recorded samples, the closed loop, parameter
-        tangents."""
+        Not available: the damped variant (``rho_inf`` < 1), tangents of recorded samples, parameter tangents.  The closed
+        loop has its own call, step_implicit_feedback_tangent."""
         def launch(dxd, D, t_start, desc, tan, sd, dsd, t_end):   # (without a schedule: crb_step_implicit_tangent)
             return self._lib.crb_step_implicit_tangent_sched(self.plan.h, self._ptr(self.state), self._ptr(dxd), int(D), t_start,
                                                              float(h), int(n_steps), int(n_iter), C.byref(desc), C.byref(tan),
@@ -1294,6 +1294,136 @@ class BeamEnsemble:
         xT, samples, control = _ImplicitFeedbackRollout.apply(self, opts, x0, K, ref, amp, held)
         out = (xT,) + ((samples,) if record is not None else ()) + ((control,) if return_control else ())
         return out if len(out) > 1 else xT
+
+    # ------------------------------------------------- tangent of the sampled-data implicit loop (crb_implicit_feedback_tangent.h)
+    def step_implicit_feedback_tangent(self, n_steps: int, h: float, dx0_red, gain, reference=None, hold: int = 1,
+                                       n_iter: int = 2, d_gain=None, d_reference=None, impulse_amp=None,
+                                       impulse_duration: float = 0.01, impulse_index: int = -2, held_force=None,
+                                       d_impulse_amp=None, d_held_force=None, t0: Optional[float] = None,
+                                       return_control: bool = False):
+        """``step_implicit_feedback()`` with the tangent of the digital loop alongside (crb_step_implicit_feedback_tangent):
+        advances ``state`` and ``time`` as step_implicit_feedback does (``time`` moves only when the launch is accepted) and
+        returns dx(T) along ``dx0_red`` ([B, 2n], or D directions [D, B, 2n] in one call), ``d_gain`` ([n, 2n] / [D, n, 2n]),
+        ``d_reference`` ([B, 2n] / [D, B, 2n]), ``d_held_force`` ([B, n] / [D, B, n]) and ``d_impulse_amp`` ([B] / [D, B]);
+        None = 0, and a tangent without a direction axis is used for every direction, as in step_implicit_tangent.  At the
+        top of every sample du_k = d_held_force + K (d_reference - dx_k) + d_gain (r - x_k); the sample's steps are one
+        interval of step_implicit_tangent's scheduled form.  The derivative is the exact forward mode of the map whose
+        transpose step_implicit_feedback_adjoint applies.  With ``return_control`` also returns (control [K, B, n], d_control
+        [D, K, B, n]), K = ceil(n_steps / hold): ``step_implicit_tangent(held_force=ControlSchedule(control, hold),
+        d_held_force=d_control)`` replays ``state`` and dx(T) bitwise.  Always the chain form: ``state`` agrees with
+        step_implicit_feedback to rounding, not bitwise.  ``gain`` is one [n, 2n] gain for the ensemble (a list raises
+        NotImplementedError).  fp64 ensembles with one free-DOF set.  Not available: an in-kernel form, tangents of recorded
+        samples, gain groups, the damped variant, parameter tangents, the RK4 closed loop's tangent."""
+        who = "step_implicit_feedback_tangent"
+        K = self._feedback_gain(gain, who)
+        if int(hold) != hold or int(hold) < 1:
+            raise ValueError(f"{who}: hold must be an integer >= 1 (implicit steps per sample)")
+        hold = int(hold)
+        B, n = self.n_beams, self.n
+        dx, single = self._dirs(dx0_red, 2 * n, f"{who}: dx0_red")
+        D = dx.shape[0]
+        ref = None if reference is None else self._dev(reference, (B, 2 * n))
+        fbt = nat.FeedbackTangent()
+        dK = dr = None
+        if d_gain is not None:
+            dK = torch.as_tensor(d_gain, dtype=self.dtype, device=self.device)
+            if tuple(dK.shape) not in ((n, 2 * n), (D, n, 2 * n)):
+                raise ValueError(f"{who}: d_gain must be [{n}, {2 * n}] or [{D}, {n}, {2 * n}], got {tuple(dK.shape)}")
+            dK = dK.expand(D, n, 2 * n).contiguous()
+            fbt.d_gain = dK.data_ptr()
+        if d_reference is not None:
+            dr, _ = self._dirs(d_reference, 2 * n, f"{who}: d_reference")
+            if dr.shape[0] not in (1, D):
+                raise ValueError(f"{who}: d_reference must have the directions of dx0_red")
+            dr = dr.expand(D, B, 2 * n).contiguous()
+            fbt.d_ref = dr.data_ptr()
+        t_start = self.time if t0 is None else float(t0)   # (``time`` moves only when the launch is accepted)
+        if d_impulse_amp is not None and impulse_amp is None:
+            impulse_amp = torch.zeros((B,), dtype=self.dtype, device=self.device)
+        desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index, held_force)
+        tan = nat.InputTangent()
+        if d_impulse_amp is not None:
+            da = torch.as_tensor(d_impulse_amp, dtype=self.dtype, device=self.device)
+            if tuple(da.shape) not in ((B,), (D, B)):
+                raise ValueError(f"{who}: d_impulse_amp must be [{B}] or [{D}, {B}]")
+            da = da.expand(D, B).contiguous()
+            tan.d_amp = da.data_ptr()
+            keep.append(da)
+        if d_held_force is not None:
+            dh, _ = self._dirs(d_held_force, n, f"{who}: d_held_force")
+            if dh.shape[0] not in (1, D):
+                raise ValueError(f"{who}: d_held_force must have the directions of dx0_red")
+            dhd = self._pack_dirs(dh.expand(D, -1, -1), False)
+            tan.df_held = dhd.data_ptr()
+            keep.append(dhd)
+        dxd = self._pack_dirs(dx, True)
+        n_samples = -(-int(n_steps) // hold)
+        u_out = du_out = None
+        if return_control:
+            u_out = torch.zeros((max(n_samples, 1), B, self.n_node, 4), dtype=self.dtype, device=self.device)
+            du_out = torch.zeros((D, max(n_samples, 1), B, self.n_node, 4), dtype=self.dtype, device=self.device)
+        nbytes = int(self._lib.crb_implicit_feedback_tangent_work_bytes(self.plan.h, int(D)))
+        work = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=self.device)
+        t_end = C.c_double(0.0)
+        with self._on_device():
+            nat.check(self._lib.crb_step_implicit_feedback_tangent(
+                self.plan.h, self._ptr(self.state), self._ptr(dxd), int(D), t_start, float(h), int(n_steps), int(n_iter), hold,
+                self._ptr(K), self._ptr(ref), C.byref(fbt), C.byref(desc), C.byref(tan), self._ptr(u_out), self._ptr(du_out),
+                self._ptr(work), C.byref(t_end), self._stream()))
+        self._keep = keep + [K, ref, dK, dr, dxd, u_out, du_out, work]
+        self.time = float(t_end.value)
+        out = self._unpack_dirs(dxd)
+        out = out[0] if single else out
+        if not return_control:
+            return out
+        if n_samples > 0:
+            control = self._unpack_force_dirs(u_out[:n_samples])
+            d_control = self._unpack_sched_dirs(du_out[:, :n_samples])
+        else:
+            control = torch.zeros((0, B, n), dtype=self.dtype, device=self.device)
+            d_control = torch.zeros((D, 0, B, n), dtype=self.dtype, device=self.device)
+        return out, (control, d_control)
+
+    def linearize_implicit_feedback(self, h: float, gain, reference=None, hold: int = 1, n_samples: int = 1, n_iter: int = 2,
+                                    x_red=None, held_force=None):
+        """The sampled linearisation of the digital loop: (Phi_cl [B, 2n, 2n], G_ref [B, 2n, 2n]), the Jacobians of the state
+        after ``n_samples`` samples of ``step_implicit_feedback(n_samples * hold, h, gain, reference, hold, n_iter,
+        held_force=held_force)`` with respect to the state it starts from and to the reference -- on a linear rod
+        A_d - B_d K and B_d K of ``linearize_implicit(h, hold, n_iter)``; on the nonlinear rod, in water and under gravity,
+        the closed loop's state-transition matrix about any operating point, whose spectral radius says whether the
+        regulator designed on (A_d, B_d) is stable on the plant the stepper applies (examples/closed_loop_margin.py).  Taken
+        at (``x_red`` [B, 2n], ``held_force`` [B, n]); None = the resident state and 0.  Two calls of
+        crb_step_implicit_feedback_tangent with identity seeds (2n state, 2n reference directions) on a copy: ``state``,
+        ``time`` and ``status`` are untouched."""
+        who = "linearize_implicit_feedback"
+        if int(n_samples) != n_samples or int(n_samples) < 1:
+            raise ValueError(f"{who}: n_samples must be an integer >= 1")
+        if int(hold) != hold or int(hold) < 1:
+            raise ValueError(f"{who}: hold must be an integer >= 1 (implicit steps per sample)")
+        B, n = self.n_beams, self.n
+        n_steps = int(n_samples) * int(hold)
+        x0 = self.state.clone() if x_red is None else self.pack_state(x_red)
+        held = None if held_force is None else self._dev(held_force, (B, n))
+        eye2 = torch.eye(2 * n, dtype=self.dtype, device=self.device)[:, None, :].expand(2 * n, B, 2 * n)
+        zero = torch.zeros((2 * n, B, 2 * n), dtype=self.dtype, device=self.device)
+        saved = (self.state, self.time, getattr(self, "_status", None))
+        had_status = saved[2] is not None
+        try:
+            if had_status:   # (the launches below must not report into the ensemble's status, nor count as its steps)
+                with self._on_device():
+                    steps_done = int(self._lib.crb_plan_status_steps(self.plan.h))
+                    nat.check(self._lib.crb_plan_set_status(self.plan.h, None, 0))
+            self.state = x0.clone()
+            dP = self.step_implicit_feedback_tangent(n_steps, h, eye2, gain, reference, hold, n_iter, held_force=held, t0=0.0)
+            self.state = x0
+            dG = self.step_implicit_feedback_tangent(n_steps, h, zero, gain, reference, hold, n_iter, d_reference=eye2,
+                                                     held_force=held, t0=0.0)
+        finally:
+            self.state, self.time = saved[0], saved[1]
+            if had_status:
+                with self._on_device():
+                    nat.check(self._lib.crb_plan_set_status(self.plan.h, self._ptr(saved[2]), steps_done))
+        return dP.permute(1, 2, 0).contiguous(), dG.permute(1, 2, 0).contiguous()
 
     def step_implicit(self, n_steps: int, h: float, n_iter: int = 2, impulse_amp=None, impulse_duration: float = 0.01,
                       impulse_index: int = -2, held_force=None, t0: Optional[float] = None, record=None,

@@ -24,6 +24,7 @@
 #include "crb_implicit_feedback_launch.h"
 #include "crb_feedback_adjoint_launch.h"
 #include "crb_implicit_feedback_adjoint_launch.h"
+#include "crb_implicit_feedback_tangent_launch.h"
 #include "crb_host.h"
 #include "crb_blocked.h"
 
@@ -3693,5 +3694,110 @@ extern "C" int crb_step_implicit_feedback_adjoint(const crb_plan* p, const void*
     });
     if (rc) return rc;
     if (q.gain_bar && slices > 1) HIP_TRY(crb::launch_feedback_gain_reduce(q.gain_bar, w.partial, p->n_free, n_cot, slices, st));
+    return CRB_OK;
+}
+
+// ------------------------------------------------------------------ tangent of the sampled-data implicit loop
+// (crb_implicit_feedback_tangent.h): per sample the boundary products, then the implicit tangent's scheduled kernel over the
+// sample's steps as ONE interval of a schedule (u_k, du_k) -- a^0 = 0 and da^0 = 0 at its first step
+extern "C" size_t crb_implicit_feedback_tangent_work_bytes(const crb_plan* p, int n_dir) {
+    if (!p || n_dir < 1 || n_dir > 65535) return 0;
+    return (size_t(1) + size_t(n_dir)) * force_doubles(p) * sizeof(double);
+}
+
+extern "C" int crb_step_implicit_feedback_tangent(const crb_plan* p, void* x, void* dx, int n_dir, double t0, double h, int n_steps,
+                                                  int n_iter, int hold, const void* gain, const void* ref,
+                                                  const crb_feedback_tangent* dfb, const crb_input_desc* in,
+                                                  const crb_input_tangent* din, void* u_out, void* du_out, void* work,
+                                                  double* t_end, void* stream) {
+    const std::string who("crb_step_implicit_feedback_tangent");
+    if (!p) return fail(CRB_EINVAL, who + ": null plan");
+    if (!x || !dx || !gain || !work) return fail(CRB_EINVAL, who + ": null x, dx, gain or work");
+    const void* const d_gain = dfb ? dfb->d_gain : nullptr;
+    const void* const d_ref = dfb ? dfb->d_ref : nullptr;
+    const void* const d_amp = din ? din->d_amp : nullptr;
+    const void* const df_held = din ? din->df_held : nullptr;
+    const void* const outs[4] = {dx, u_out, du_out, work};
+    const char* const out_names[4] = {"dx", "u_out", "du_out", "work"};
+    const void* const ins[9] = {x, gain, ref, d_gain, d_ref, in ? in->f_held : nullptr, in ? in->amp : nullptr, df_held, d_amp};
+    if (int rc = fb_adj_alias_checks(who, outs, out_names, ins,
+                                     "x, gain, ref, dfb->d_gain, dfb->d_ref, input->f_held, input->amp, dinput->df_held or dinput->d_amp"))
+        return rc;
+    if (int rc = check_count(who, "n_dir", n_dir)) return rc;
+    if (n_steps < 0) return fail(CRB_EINVAL, who + ": n_steps must be >= 0");
+    if (n_iter < 1 || n_iter > IMP_ADJ_MAX_ITER) return fail(CRB_EINVAL, who + ": n_iter must be in [1, 16]");
+    if (!(h > 0)) return fail(CRB_EINVAL, who + ": h must be positive");
+    if (hold < 1) return fail(CRB_EINVAL, who + ": hold must be >= 1");
+    Forcing f;
+    if (int rc = decode_input(p, in, who.c_str(), &f)) return rc;
+    if (d_amp && !f.impulse)
+        return fail(CRB_EINVAL, who + ": d_amp needs an impulse input (its amplitude is what it differentiates)");
+    if (p->dtype != CRB_F64) return fail(CRB_EUNSUPPORTED, who + ": the tangent of the implicit stepper needs an fp64 plan");
+    if (p->NT > TANGENT_MAX_NT) return fail(CRB_EUNSUPPORTED, who + ": beams of more than 256 thread-carried nodes are not supported");
+    if (p->mixed_topology)
+        return fail(CRB_EUNSUPPORTED, who + ": one gain matrix for the ensemble needs one free-DOF set (the plan has mixed topology)");
+    if (int rc = need_device(p, who.c_str())) return rc;
+    if (t_end) *t_end = clock_after(t0, h, n_steps);
+    if (n_steps == 0) return CRB_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    KParams<double> base;
+    if (int rc = imp_adjoint_params(p, h, st, &base)) return rc;   // (A's tables where M's are, base.dt = h)
+    base.x = static_cast<double*>(x);
+    Forcing fs = f;
+    fs.held = nullptr;   // (the held force is inside every u_k)
+    set_io(base, fs);
+    // a beam that goes non-finite is marked with the step count at the end of the CALL, as crb_step_implicit_feedback does
+    arm_status(p, base, n_steps);
+    const size_t F = force_doubles(p), S = state_doubles(p);
+    const int n_samples = (n_steps + hold - 1) / hold;
+    // the held input of a sample and its tangents: record k of u_out / du_out, else the one record (per direction) of work.
+    // Entries the boundary kernel does not write (constrained DOFs, the padding component) read as zero
+    double* const u0 = u_out ? static_cast<double*>(u_out) : static_cast<double*>(work);
+    double* const du0 = du_out ? static_cast<double*>(du_out) : static_cast<double*>(work) + F;
+    const size_t u_step = u_out ? F : 0, du_step = du_out ? F : 0, du_dir = du_out ? size_t(n_samples) * F : F;
+    HIP_TRY(hipMemsetAsync(u0, 0, (u_out ? size_t(n_samples) : size_t(1)) * F * sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(du0, 0, size_t(n_dir) * du_dir * sizeof(double), st));
+
+    crb::ImpFbTanParams b = zeroed<crb::ImpFbTanParams>();
+    b.col_off = p->d_col_off;
+    b.row_off = p->d_row_off;
+    b.B = p->B; b.n = p->n_free; b.n2 = 2 * p->n_free; b.n_dir = n_dir;
+    b.x_stride = size_t(2) * p->n_node * 4;
+    b.u_stride = size_t(p->n_node) * 4;
+    b.gain = static_cast<const double*>(gain);
+    b.d_gain = static_cast<const double*>(d_gain);
+    b.ref = static_cast<const double*>(ref);
+    b.d_ref = static_cast<const double*>(d_ref);
+    b.x = static_cast<const double*>(x);
+    b.dx = static_cast<const double*>(dx);
+    b.f_held = static_cast<const double*>(f.held);
+    b.df_held = static_cast<const double*>(df_held);
+    b.du_dir_stride = du_dir;
+
+    TangentParams<double> q{};
+    q.x0 = base.x;
+    if (n_dir > 1) {   // (instance d = 0 writes the base back while the others may still be loading it: they read a copy)
+        if (!p->d_tan_x0) HIP_TRY(hipMalloc(&p->d_tan_x0, S * sizeof(double)));
+        q.x0 = static_cast<const double*>(p->d_tan_x0);
+    }
+    q.dx = static_cast<double*>(dx);
+    q.d_amp = static_cast<const double*>(d_amp);
+    q.du_dir_stride = du_dir;
+    double t = t0;
+    for (int s = 0, ks = 0; s < n_steps; s += hold, ++ks) {
+        const int hs = n_steps - s < hold ? n_steps - s : hold;
+        b.u = u0 + size_t(ks) * u_step;
+        b.du = du0 + size_t(ks) * du_step;
+        HIP_TRY(crb::launch_imp_fb_tangent_boundary(b, st));
+        if (n_dir > 1) HIP_TRY(hipMemcpyAsync(p->d_tan_x0, x, S * sizeof(double), hipMemcpyDeviceToDevice, st));
+        KParams<double> k = base;
+        k.t0 = t; k.n_steps = hs;
+        Schedule sc;   // the sample as the one interval of a schedule: the kernel never switches (hs <= hold)
+        sc.f = b.u; sc.K = 1; sc.hold = hold;
+        set_sched(p, k, sc, 0);
+        q.du_held = b.du;
+        HIP_TRY(crb::launch_imp_jvp_step(k, q, n_iter, true, beam_groups(p), n_dir, p->NT, st));
+        t = clock_after(t, h, hs);
+    }
     return CRB_OK;
 }

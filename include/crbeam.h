@@ -715,7 +715,8 @@ int crb_step_implicit_adjoint_sched(const crb_plan* plan, const void* ckpt, void
  * n_steps > n_intervals * hold, a schedule together with input->f_held or dinput->df_held, d_sched without a schedule); then
  * CRB_EUNSUPPORTED for fp32 plans and beams of more than 256 thread-carried nodes; then CRB_ENODEV for host-only plans.
  * *t_end is written only by a call that is not refused; n_steps == 0 returns CRB_OK and touches nothing else.
- * Not covered: the damped variant (rho_inf < 1), tangents of recorded samples, the closed loop, parameter tangents. */
+ * Not covered: the damped variant (rho_inf < 1), tangents of recorded samples, parameter tangents.  The closed loop
+ * u_k = f_held + K (r - x_k) has its own entry point, crb_step_implicit_feedback_tangent below. */
 int crb_step_implicit_tangent(const crb_plan* plan, void* x, void* dx, int n_dir, double t0, double h, int n_steps, int n_iter,
                               const crb_input_desc* input, const crb_input_tangent* dinput, double* t_end, void* stream);
 int crb_step_implicit_tangent_sched(const crb_plan* plan, void* x, void* dx, int n_dir, double t0, double h, int n_steps,
@@ -827,6 +828,60 @@ int crb_step_implicit_feedback_adjoint(const crb_plan* plan, const void* ckpt, c
                                        const void* ref, const crb_input_desc* input, const crb_record_desc* rec_bar,
                                        const crb_feedback_cotangent* grad, const crb_input_cotangent* igrad, void* work,
                                        void* stream);
+
+/* ---- Tangent of the sampled-data implicit loop: forward-mode derivatives of a rollout of crb_step_implicit_feedback with
+ * respect to the start state, the gain, the reference, the held force and the impulse amplitude, n_dir directions in one call
+ * (csrc/crb_implicit_feedback_tangent.h).  With identity seeds it gives the closed loop's sampled state-transition matrix
+ * d x_{k+N} / d x_k on the nonlinear rod -- whether the regulator of control/linear_quadratic_regulator.py:84-191, designed on
+ * crb_step_implicit_tangent's (A_d, B_d) and applied as control/full_state_linear.py:81 applies it, is stable on the plant the
+ * stepper runs -- and the Gauss-Newton columns of gain tuning and reference shaping.
+ *
+ * The map is crb_step_implicit_feedback_adjoint's.  Sample k covers steps k * hold ... (k + 1) * hold - 1 (the last sample may
+ * be cut short by n_steps); at its top, in reduced ordering,
+ *     u_k  = f_held  + K (r - x_k)
+ *     du_k = df_held + K (dr - dx_k) + dK (r - x_k)          per direction
+ * and the sample's steps are one interval of crb_step_implicit_tangent_sched with the held input u_k and its tangent du_k:
+ * a^0 = 0 and da^0 = 0 at the sample's first step, the impulse and d_amp added on the impulse DOF while the midpoint clock
+ * __dadd_rn(tc, 0.5 h) < duration, the clock advanced by __dadd_rn.
+ *   x        device [B][2][n_node][4], advances in place; per-beam status (crb_plan_set_status) is written by direction 0 with
+ *            the ensemble's step count at the end of the call
+ *   dx       device [n_dir][B][2][n_node][4], in place: the seeds on entry, dx(T) on exit
+ *   gain     device [n][2n] row-major; ref device [B][2n] or NULL (= 0)
+ *   dfb      d_gain [n_dir][n][2n] row-major, d_ref [n_dir][B][2n]; either or dfb may be NULL (= 0).  With d_gain NULL the
+ *            product dK (r - x_k) is skipped entirely (no loads, no MFMAs) and every other result is bitwise unchanged
+ *   input    impulse and f_held as crb_step_implicit_feedback; dinput: d_amp [n_dir][B] (needs an impulse) and df_held
+ *            [n_dir][B][n_node][4] as crb_step_implicit_tangent; either or dinput may be NULL (= 0)
+ *   u_out    device [K][B][n_node][4], du_out device [n_dir][K][B][n_node][4], K = ceil(n_steps / hold), either may be NULL: the
+ *            held input of every sample and its tangent, zeros at constrained DOFs and padding; du_out in the layout
+ *            crb_step_implicit_tangent_sched takes as d_sched (with f_sched = u_out and this hold it replays x and dx bitwise)
+ *   work     device, crb_implicit_feedback_tangent_work_bytes(plan, n_dir) = (1 + n_dir) * B * n_node * 4 * sizeof(double) bytes:
+ *            one force record for u_k and one per direction for du_k, used where u_out / du_out is NULL (never NULL itself).
+ *            0 for a NULL plan or n_dir outside 1 .. 65535
+ * The call always runs the chain form, as the adjoint does: per sample one boundary launch (both products on
+ * v_mfma_f64_16x16x4_f64, straight from the state layout and to the force layout) and one launch of the implicit tangent's
+ * scheduled kernel over the sample's steps.  A workgroup of the boundary kernel owns 32 beams x 32 force DOFs of ONE direction
+ * (or of u) and sums K (dr - dx) and then dK (r - x) over 2n in ascending order: no floating-point atomics, every output
+ * element has one owner; D directions in one call are bitwise D calls of one, two identical calls agree bitwise, and u does
+ * not depend on n_dir.  A non-finite seed stays in its beam and direction.  x agrees with crb_step_implicit_feedback to
+ * rounding, not bitwise (the products sum in another order).
+ *
+ * Refusals, all before the device is touched, crb_last_error() naming the entry point and the argument, in this order:
+ * CRB_EINVAL for a NULL plan, x, dx, gain or work; dx, u_out, du_out or work aliasing each other, x, gain, ref, d_gain, d_ref,
+ * f_held, amp, df_held or d_amp; n_dir outside 1 .. 65535; n_steps < 0; n_iter outside 1 .. 16; h <= 0; hold < 1; a bad input
+ * description; d_amp without an impulse.  Then CRB_EUNSUPPORTED for fp32 plans, beams of more than 256 thread-carried nodes,
+ * ensembles of mixed topology or per-beam free-DOF sets.  Then CRB_ENODEV for host-only plans.  n_steps == 0 sets *t_end,
+ * returns CRB_OK and touches nothing else.
+ * Not covered: an in-kernel (one-launch) form, tangents of recorded samples, per-beam gain groups, the damped variant, fp32,
+ * parameter tangents, the tangent of the RK4 closed loop (crb_step_rk4_feedback). */
+typedef struct crb_feedback_tangent {
+    const void* d_gain;   /* [n_dir][n][2n] row-major, or NULL */
+    const void* d_ref;    /* [n_dir][B][2n] reduced, or NULL */
+} crb_feedback_tangent;
+size_t crb_implicit_feedback_tangent_work_bytes(const crb_plan* plan, int n_dir);
+int crb_step_implicit_feedback_tangent(const crb_plan* plan, void* x, void* dx, int n_dir, double t0, double h, int n_steps,
+                                       int n_iter, int hold, const void* gain, const void* ref, const crb_feedback_tangent* dfb,
+                                       const crb_input_desc* input, const crb_input_tangent* dinput, void* u_out, void* du_out,
+                                       void* work, double* t_end, void* stream);
 
 /* out[b] = x[b][plane][node][dof]  (e.g. tip displacement = plane 0, node n_elem, dof 1;
  * lqr_control.py:168) */

@@ -754,17 +754,26 @@ class BeamEnsemble:
 
     def _rollout_tangent(self, who, unit, launch, n_steps, dx0_red, impulse_amp, impulse_duration, impulse_index, held_force,
                          d_impulse_amp, d_held_force, t0):
-        """The body step_tangent and step_implicit_tangent share: decodes the seeds and the input tangents, runs
-        ``launch(dxd, D, t_start, desc, tan, sd, dsd, t_end)`` (the library call on the resident state) and returns the
-        tangent in the shape of ``dx0_red``.  ``who`` / ``unit``: the caller's name and what a schedule's hold counts."""
+        """The body step_tangent and step_implicit_tangent share: _tangent_inputs, then _tangent_launch of
+        ``launch(dxd, D, t_start, desc, tan, sd, dsd, t_end)`` (the library call on the resident state).  ``who`` / ``unit``:
+        the caller's name and what a schedule's hold counts."""
+        held_force, sch = self._control(held_force, None, None, n_steps, who, unit)
+        dx, single, D, desc, tan, keep, sd, dsd = self._tangent_inputs(who, dx0_red, impulse_amp, impulse_duration, impulse_index,
+                                                                       held_force, sch, d_impulse_amp, d_held_force)
+        return self._tangent_launch(lambda dxd, t_start, t_end: launch(dxd, D, t_start, desc, tan, sd, dsd, t_end), dx, single, t0,
+                                    keep)
+
+    def _tangent_inputs(self, who, dx0_red, impulse_amp, impulse_duration, impulse_index, held_force, sch, d_impulse_amp,
+                        d_held_force):
+        """What every tangent rollout decodes alike: the seeds dx [D, B, 2n] (and whether ``dx0_red`` had no direction axis), the
+        input's descriptor, the crb_input_tangent of ``d_impulse_amp`` and ``d_held_force`` and, with a schedule ``sch`` (of
+        _control), its descriptor and its packed tangent -- (dx, single, D, desc, tan, keep, sd, dsd), ``keep`` the device
+        buffers these point to."""
         dx, single = self._dirs(dx0_red, 2 * self.n, f"{who}: dx0_red")
         D = dx.shape[0]
-        held_force, sch = self._control(held_force, None, None, n_steps, who, unit)
-        t_start = self.time if t0 is None else float(t0)   # (``time`` moves only when the launch is accepted)
         if d_impulse_amp is not None and impulse_amp is None:
             impulse_amp = torch.zeros((self.n_beams,), dtype=self.dtype, device=self.device)
         desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index, held_force)
-        dxd = self._pack_dirs(dx, True)
         tan = nat.InputTangent()
         if d_impulse_amp is not None:
             da = torch.as_tensor(d_impulse_amp, dtype=self.dtype, device=self.device)
@@ -791,13 +800,19 @@ class BeamEnsemble:
             dhd = self._pack_dirs(dh.expand(D, -1, -1), False)
             tan.df_held = dhd.data_ptr()
             keep.append(dhd)
-        t_end = C.c_double(0.0)
         sd, packed = self._sched_desc(sch)
         keep.append(packed)
+        return dx, single, D, desc, tan, keep, sd, dsd
+
+    def _tangent_launch(self, call, dx, single, t0, keep):
+        """``call(dxd, t_start, t_end)``, the library call of a tangent rollout on the resident state with the seeds packed, from
+        the clock ``t0`` (None: ``time``, which moves only when the launch is accepted); the tangent in the seeds' shape"""
+        dxd = self._pack_dirs(dx, True)
+        t_end = C.c_double(0.0)
         with self._on_device():
-            nat.check(launch(dxd, D, t_start, desc, tan, sd, dsd, t_end))
+            nat.check(call(dxd, self.time if t0 is None else float(t0), t_end))
         self._keep = keep + [dxd]
-        self.time = t_end.value
+        self.time = float(t_end.value)
         out = self._unpack_dirs(dxd)
         return out[0] if single else out
 
@@ -835,6 +850,18 @@ class BeamEnsemble:
         held = None if held_force is None else self._dev(held_force, (B, n))
         eye2 = torch.eye(2 * n, dtype=self.dtype, device=self.device)
         eye1 = torch.eye(n, dtype=self.dtype, device=self.device)
+        return self._jacobians_on_a_copy(
+            x0,
+            lambda: self.step_implicit_tangent(n_steps, h, eye2[:, None, :].expand(2 * n, B, 2 * n), n_iter=n_iter,
+                                               held_force=held, t0=0.0),
+            lambda: self.step_implicit_tangent(n_steps, h, torch.zeros((n, B, 2 * n), dtype=self.dtype, device=self.device),
+                                               n_iter=n_iter, held_force=held, d_held_force=eye1[:, None, :].expand(n, B, n),
+                                               t0=0.0))
+
+    def _jacobians_on_a_copy(self, x0, first, second):
+        """The Jacobians [B, 2n, D] of two tangent calls with identity seeds (each returns [D, B, 2n]), ``first`` on a copy of
+        the device-layout state ``x0`` and ``second`` on ``x0`` itself: ``state``, ``time`` and the status -- the plan's
+        pointer and step count -- are put back, whatever the calls raise."""
         saved = (self.state, self.time, getattr(self, "_status", None))
         had_status = saved[2] is not None
         try:
@@ -843,17 +870,15 @@ class BeamEnsemble:
                     steps_done = int(self._lib.crb_plan_status_steps(self.plan.h))
                     nat.check(self._lib.crb_plan_set_status(self.plan.h, None, 0))
             self.state = x0.clone()
-            dA = self.step_implicit_tangent(n_steps, h, eye2[:, None, :].expand(2 * n, B, 2 * n), n_iter=n_iter, held_force=held,
-                                            t0=0.0)
+            d1 = first()
             self.state = x0
-            dB = self.step_implicit_tangent(n_steps, h, torch.zeros((n, B, 2 * n), dtype=self.dtype, device=self.device),
-                                            n_iter=n_iter, held_force=held, d_held_force=eye1[:, None, :].expand(n, B, n), t0=0.0)
+            d2 = second()
         finally:
             self.state, self.time = saved[0], saved[1]
             if had_status:
                 with self._on_device():
                     nat.check(self._lib.crb_plan_set_status(self.plan.h, self._ptr(saved[2]), steps_done))
-        return dA.permute(1, 2, 0).contiguous(), dB.permute(1, 2, 0).contiguous()
+        return d1.permute(1, 2, 0).contiguous(), d2.permute(1, 2, 0).contiguous()
 
     # ------------------------------------------------------------------ adjoint (reverse mode, crb_adjoint.h)
     ADJOINT_WORK_BUDGET = 1 << 30   # bytes the default checkpoint interval keeps crb_step_rk4_adjoint's work buffer under
@@ -1228,15 +1253,34 @@ class BeamEnsemble:
                              f"({nbytes(every)} bytes at hold = {hold}) exceeds ADJOINT_WORK_BUDGET = {self.ADJOINT_WORK_BUDGET}")
         return every
 
+    @staticmethod
+    def _hold(hold, who) -> int:
+        """``hold`` of a sampled-data loop, as an int"""
+        if int(hold) != hold or int(hold) < 1:
+            raise ValueError(f"{who}: hold must be an integer >= 1 (implicit steps per sample)")
+        return int(hold)
+
+    def _control_records(self, n_steps, hold, D=None) -> torch.Tensor:
+        """zeroed device records for the held input of every sample, [K, B, n_node, 4] (with ``D`` directions [D, K, ...]),
+        K = ceil(n_steps / hold) but at least one (the library is given an address)"""
+        K = max(-(-int(n_steps) // int(hold)), 1)
+        return torch.zeros(((K,) if D is None else (D, K)) + (self.n_beams, self.n_node, 4), dtype=self.dtype, device=self.device)
+
+    def _unpack_controls(self, u: torch.Tensor, n_steps, hold) -> torch.Tensor:
+        """_control_records -> reduced [K, B, n] / [D, K, B, n], K = ceil(n_steps / hold), none included"""
+        K = -(-int(n_steps) // int(hold))
+        if K == 0:
+            return torch.zeros(tuple(u.shape[:-4]) + (0, self.n_beams, self.n), dtype=self.dtype, device=self.device)
+        return self._unpack_force_dirs(u[:K]) if u.dim() == 4 else self._unpack_sched_dirs(u[:, :K])
+
     def _implicit_feedback_args(self, gain, hold, record, who):
         """the argument errors step_implicit_feedback_adjoint and rollout_implicit_feedback share; returns hold as an int"""
         if isinstance(gain, (list, tuple)):
             self._feedback_gain(gain, who)
-        if int(hold) != hold or int(hold) < 1:
-            raise ValueError(f"{who}: hold must be an integer >= 1 (implicit steps per sample)")
+        hold = self._hold(hold, who)
         if record is not None and isinstance(record, str):
             raise NotImplementedError(f"{who}: whole-state snapshots (record='all') are not available in the differentiable loop")
-        return int(hold)
+        return hold
 
     def step_implicit_feedback_adjoint(self, n_steps: int, h: float, lam_red, gain, reference=None, hold: int = 1,
                                        n_iter: int = 2, x0_red=None, impulse_amp=None, impulse_duration: float = 0.01,
@@ -1316,12 +1360,10 @@ class BeamEnsemble:
         samples, gain groups, the damped variant, parameter tangents, the RK4 closed loop's tangent."""
         who = "step_implicit_feedback_tangent"
         K = self._feedback_gain(gain, who)
-        if int(hold) != hold or int(hold) < 1:
-            raise ValueError(f"{who}: hold must be an integer >= 1 (implicit steps per sample)")
-        hold = int(hold)
+        hold = self._hold(hold, who)
         B, n = self.n_beams, self.n
-        dx, single = self._dirs(dx0_red, 2 * n, f"{who}: dx0_red")
-        D = dx.shape[0]
+        dx, single, D, desc, tan, keep, _, _ = self._tangent_inputs(who, dx0_red, impulse_amp, impulse_duration, impulse_index,
+                                                                    held_force, None, d_impulse_amp, d_held_force)
         ref = None if reference is None else self._dev(reference, (B, 2 * n))
         fbt = nat.FeedbackTangent()
         dK = dr = None
@@ -1337,52 +1379,21 @@ class BeamEnsemble:
                 raise ValueError(f"{who}: d_reference must have the directions of dx0_red")
             dr = dr.expand(D, B, 2 * n).contiguous()
             fbt.d_ref = dr.data_ptr()
-        t_start = self.time if t0 is None else float(t0)   # (``time`` moves only when the launch is accepted)
-        if d_impulse_amp is not None and impulse_amp is None:
-            impulse_amp = torch.zeros((B,), dtype=self.dtype, device=self.device)
-        desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index, held_force)
-        tan = nat.InputTangent()
-        if d_impulse_amp is not None:
-            da = torch.as_tensor(d_impulse_amp, dtype=self.dtype, device=self.device)
-            if tuple(da.shape) not in ((B,), (D, B)):
-                raise ValueError(f"{who}: d_impulse_amp must be [{B}] or [{D}, {B}]")
-            da = da.expand(D, B).contiguous()
-            tan.d_amp = da.data_ptr()
-            keep.append(da)
-        if d_held_force is not None:
-            dh, _ = self._dirs(d_held_force, n, f"{who}: d_held_force")
-            if dh.shape[0] not in (1, D):
-                raise ValueError(f"{who}: d_held_force must have the directions of dx0_red")
-            dhd = self._pack_dirs(dh.expand(D, -1, -1), False)
-            tan.df_held = dhd.data_ptr()
-            keep.append(dhd)
-        dxd = self._pack_dirs(dx, True)
-        n_samples = -(-int(n_steps) // hold)
-        u_out = du_out = None
-        if return_control:
-            u_out = torch.zeros((max(n_samples, 1), B, self.n_node, 4), dtype=self.dtype, device=self.device)
-            du_out = torch.zeros((D, max(n_samples, 1), B, self.n_node, 4), dtype=self.dtype, device=self.device)
+        u_out = self._control_records(n_steps, hold) if return_control else None
+        du_out = self._control_records(n_steps, hold, D) if return_control else None
         nbytes = int(self._lib.crb_implicit_feedback_tangent_work_bytes(self.plan.h, int(D)))
         work = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=self.device)
-        t_end = C.c_double(0.0)
-        with self._on_device():
-            nat.check(self._lib.crb_step_implicit_feedback_tangent(
+
+        def call(dxd, t_start, t_end):
+            return self._lib.crb_step_implicit_feedback_tangent(
                 self.plan.h, self._ptr(self.state), self._ptr(dxd), int(D), t_start, float(h), int(n_steps), int(n_iter), hold,
                 self._ptr(K), self._ptr(ref), C.byref(fbt), C.byref(desc), C.byref(tan), self._ptr(u_out), self._ptr(du_out),
-                self._ptr(work), C.byref(t_end), self._stream()))
-        self._keep = keep + [K, ref, dK, dr, dxd, u_out, du_out, work]
-        self.time = float(t_end.value)
-        out = self._unpack_dirs(dxd)
-        out = out[0] if single else out
+                self._ptr(work), C.byref(t_end), self._stream())
+        out = self._tangent_launch(call, dx, single, t0, keep + [K, ref, dK, dr])
+        self._keep += [u_out, du_out, work]
         if not return_control:
             return out
-        if n_samples > 0:
-            control = self._unpack_force_dirs(u_out[:n_samples])
-            d_control = self._unpack_sched_dirs(du_out[:, :n_samples])
-        else:
-            control = torch.zeros((0, B, n), dtype=self.dtype, device=self.device)
-            d_control = torch.zeros((D, 0, B, n), dtype=self.dtype, device=self.device)
-        return out, (control, d_control)
+        return out, (self._unpack_controls(u_out, n_steps, hold), self._unpack_controls(du_out, n_steps, hold))
 
     def linearize_implicit_feedback(self, h: float, gain, reference=None, hold: int = 1, n_samples: int = 1, n_iter: int = 2,
                                     x_red=None, held_force=None):
@@ -1398,32 +1409,18 @@ class BeamEnsemble:
         who = "linearize_implicit_feedback"
         if int(n_samples) != n_samples or int(n_samples) < 1:
             raise ValueError(f"{who}: n_samples must be an integer >= 1")
-        if int(hold) != hold or int(hold) < 1:
-            raise ValueError(f"{who}: hold must be an integer >= 1 (implicit steps per sample)")
+        hold = self._hold(hold, who)
         B, n = self.n_beams, self.n
-        n_steps = int(n_samples) * int(hold)
+        n_steps = int(n_samples) * hold
         x0 = self.state.clone() if x_red is None else self.pack_state(x_red)
         held = None if held_force is None else self._dev(held_force, (B, n))
         eye2 = torch.eye(2 * n, dtype=self.dtype, device=self.device)[:, None, :].expand(2 * n, B, 2 * n)
         zero = torch.zeros((2 * n, B, 2 * n), dtype=self.dtype, device=self.device)
-        saved = (self.state, self.time, getattr(self, "_status", None))
-        had_status = saved[2] is not None
-        try:
-            if had_status:   # (the launches below must not report into the ensemble's status, nor count as its steps)
-                with self._on_device():
-                    steps_done = int(self._lib.crb_plan_status_steps(self.plan.h))
-                    nat.check(self._lib.crb_plan_set_status(self.plan.h, None, 0))
-            self.state = x0.clone()
-            dP = self.step_implicit_feedback_tangent(n_steps, h, eye2, gain, reference, hold, n_iter, held_force=held, t0=0.0)
-            self.state = x0
-            dG = self.step_implicit_feedback_tangent(n_steps, h, zero, gain, reference, hold, n_iter, d_reference=eye2,
-                                                     held_force=held, t0=0.0)
-        finally:
-            self.state, self.time = saved[0], saved[1]
-            if had_status:
-                with self._on_device():
-                    nat.check(self._lib.crb_plan_set_status(self.plan.h, self._ptr(saved[2]), steps_done))
-        return dP.permute(1, 2, 0).contiguous(), dG.permute(1, 2, 0).contiguous()
+        return self._jacobians_on_a_copy(
+            x0,
+            lambda: self.step_implicit_feedback_tangent(n_steps, h, eye2, gain, reference, hold, n_iter, held_force=held, t0=0.0),
+            lambda: self.step_implicit_feedback_tangent(n_steps, h, zero, gain, reference, hold, n_iter, d_reference=eye2,
+                                                        held_force=held, t0=0.0))
 
     def step_implicit(self, n_steps: int, h: float, n_iter: int = 2, impulse_amp=None, impulse_duration: float = 0.01,
                       impulse_index: int = -2, held_force=None, t0: Optional[float] = None, record=None,
@@ -1494,9 +1491,7 @@ class BeamEnsemble:
         if isinstance(gain, (list, tuple)):
             raise NotImplementedError(f"{who}: a list of gains (per-beam or grouped gains) is not available in the implicit closed "
                                       f"loop; pass one [{self.n}, {2 * self.n}] gain for the whole ensemble")
-        if int(hold) != hold or int(hold) < 1:
-            raise ValueError(f"{who}: hold must be an integer >= 1 (implicit steps per sample)")
-        hold = int(hold)
+        hold = self._hold(hold, who)
         K = torch.as_tensor(gain, dtype=self.dtype, device=self.device).contiguous()
         if tuple(K.shape) != (self.n, 2 * self.n):
             raise ValueError(f"{who}: gain must be [{self.n}, {2 * self.n}], got {tuple(K.shape)}")
@@ -1509,10 +1504,7 @@ class BeamEnsemble:
             self.time = float(t0)
         desc, keep = self._input_desc(impulse_amp, impulse_duration, impulse_index, held_force)
         rec, samples = self._record_desc(record, n_steps, record_every)
-        n_samples = -(-int(n_steps) // hold)
-        u_out = None
-        if return_control:
-            u_out = torch.zeros((max(n_samples, 1), self.n_beams, self.n_node, 4), dtype=self.dtype, device=self.device)
+        u_out = self._control_records(n_steps, hold) if return_control else None
         nbytes = int(self._lib.crb_implicit_feedback_work_bytes(self.plan.h))
         work = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=self.device)
         t_end = C.c_double(0.0)
@@ -1527,8 +1519,7 @@ class BeamEnsemble:
         if record is not None:
             out += (samples,)
         if return_control:
-            out += (self._unpack_force_dirs(u_out[:n_samples]) if n_samples > 0 else
-                    torch.zeros((0, self.n_beams, self.n), dtype=self.dtype, device=self.device),)
+            out += (self._unpack_controls(u_out, n_steps, hold),)
         return out if len(out) > 1 else self.time
 
     def implicit_feedback_path(self) -> str:
@@ -2210,9 +2201,7 @@ def _implicit_feedback_prepare(ens, n_steps, args, held_force, impulse_amp, reco
     h, n_iter, hold, gain, reference, want_gain = args
     K = ens._feedback_gain(gain, "step_implicit_feedback_adjoint")
     ref = None if reference is None else ens._dev(reference, (ens.n_beams, 2 * ens.n))
-    n_samples = max(1, -(-int(n_steps) // int(hold)))
-    u_ckpt = torch.zeros((n_samples, ens.n_beams, ens.n_node, 4), dtype=ens.dtype, device=ens.device)
-    return (h, n_iter, hold, K, ref, u_ckpt), held_force, None, (want_gain, impulse_amp is not None)
+    return (h, n_iter, hold, K, ref, ens._control_records(n_steps, hold)), held_force, None, (want_gain, impulse_amp is not None)
 
 
 def _implicit_feedback_checkpoint(ens, x, ckpt, n_steps, every, t0, step, desc, sd, rec, t_end):
@@ -2358,9 +2347,7 @@ class _ImplicitFeedbackRollout(torch.autograd.Function):
         ctx.ens, ctx.opts = ens, opts
         ctx.has = tuple(v is not None for v in (ref, amp, held))
         ctx.save_for_backward(ckpt, step[3], step[4], step[5], amp_d, held_d)
-        n_samples = -(-opts["n_steps"] // opts["hold"])
-        control = (ens._unpack_force_dirs(step[5][:n_samples]) if n_samples > 0 else
-                   torch.zeros((0, ens.n_beams, ens.n), dtype=ens.dtype, device=ens.device))
+        control = ens._unpack_controls(step[5], opts["n_steps"], opts["hold"])
         ctx.mark_non_differentiable(control)
         return _rollout_result(ctx, ens, opts, x, samples) + (control,)
 

@@ -1025,6 +1025,18 @@ int for_segments_reversed(int n_steps, int every, double t0, double dt, F&& body
     }
     return CRB_OK;
 }
+// body(ks, s, hs, t) for sample ks of a sampled-data rollout -- steps s .. s + hs - 1 of the call (hs < hold where the call
+// ends inside the sample), from the clock t that the samples before it leave -- in order, until one returns non-zero
+template <typename F>
+int for_samples(int n_steps, int hold, double t0, double h, F&& body) {
+    double t = t0;
+    for (int s = 0, ks = 0; s < n_steps; s += hold, ++ks) {
+        const int hs = n_steps - s < hold ? n_steps - s : hold;
+        if (int rc = body(ks, s, hs, t)) return rc;
+        t = clock_after(t, h, hs);
+    }
+    return CRB_OK;
+}
 // the decoded recording, and the decoded forcing (and recording), in a launch's parameter block
 template <typename T>
 void set_record(KParams<T>& k, const Recording& r) {
@@ -2307,38 +2319,42 @@ Recording sample_recording(const Recording& rec, int s, int hs, int hold, size_t
     if (first >= 0) rs.out = static_cast<double*>(rec.out) + size_t(first) * (rec.slot == REC_ALL_SLOTS ? plane2 : size_t(1));
     return rs;
 }
+// The controls of a sampled-data loop: record ks of the caller's u_out (one per sample), else the one record of the work buffer.
+// Zeroed first: entries of a force record that the product does not write (constrained DOFs, the padding component) read as zero
+double* control_record(const crb_plan* p, void* u_out, void* work, int ks) {
+    return u_out ? static_cast<double*>(u_out) + size_t(ks) * force_doubles(p) : static_cast<double*>(work);
+}
+hipError_t zero_controls(const crb_plan* p, void* u_out, void* work, int n_steps, int hold, hipStream_t st) {
+    const size_t records = u_out ? size_t((n_steps + hold - 1) / hold) : 1;
+    return hipMemsetAsync(u_out ? u_out : work, 0, records * force_doubles(p) * sizeof(double), st);
+}
+// u_k = f_held + K (r - x) into the force record u (the product, then the held force), and in k the sample's launch: the call's
+// forcing with u as its held input, the sample's slice of the recording
+int sample_control(const crb_plan* p, KParams<double>& k, const void* x, const void* gain, const void* ref, const Forcing& f,
+                   const Recording& rec, double* u, int s, int hs, int hold, hipStream_t st) {
+    if (int rc = feedback_force_impl<double>(p, x, gain, ref, u, st)) return rc;
+    if (f.held)
+        HIP_TRY(crb::launch_feedback_held(u, static_cast<const double*>(f.held), p->d_row_off, p->n_free, p->B, size_t(p->n_node) * 4, st));
+    const Recording rs = sample_recording(rec, s, hs, hold, state_doubles(p));
+    set_io(k, f, &rs);
+    k.u_held = u;
+    return CRB_OK;
+}
 int implicit_feedback_chain(const crb_plan* p, void* x, double t0, double h, int n_steps, int n_iter, int hold, const void* gain,
                             const void* ref, const Forcing& f, const Recording& rec, void* u_out, void* work, hipStream_t st) {
     if (int rc = stiff_tables<double>(p, 0.25 * h * h, st)) return rc;
     const StiffParams<double> q = stiff_params(p, h, n_iter);
-    const size_t force = force_doubles(p), plane2 = state_doubles(p);
-    const int n_samples = (n_steps + hold - 1) / hold;
-    // entries of a force record that the GEMM does not write (constrained DOFs, the padding component) read as zero
-    if (u_out) HIP_TRY(hipMemsetAsync(u_out, 0, size_t(n_samples) * force * sizeof(double), st));
-    else HIP_TRY(hipMemsetAsync(work, 0, force * sizeof(double), st));
+    HIP_TRY(zero_controls(p, u_out, work, n_steps, hold, st));
     // a beam that goes non-finite is marked with the step count at the end of the CALL, as the one launch of the other form does
-    KParams<double> armed = base_params<double>(p);
-    arm_status(p, armed, n_steps);
-    double t = t0;
-    for (int s = 0, ks = 0; s < n_steps; s += hold, ++ks) {
-        const int hs = n_steps - s < hold ? n_steps - s : hold;
-        double* const u = u_out ? static_cast<double*>(u_out) + size_t(ks) * force : static_cast<double*>(work);
-        if (int rc = feedback_force_impl<double>(p, x, gain, ref, u, st)) return rc;
-        if (f.held)
-            HIP_TRY(crb::launch_feedback_held(u, static_cast<const double*>(f.held), p->d_row_off, p->n_free, p->B,
-                                              size_t(p->n_node) * 4, st));
-        Forcing fs = f;
-        fs.held = u;
-        const Recording rs = sample_recording(rec, s, hs, hold, plane2);
-        KParams<double> k = base_params<double>(p);
-        k.x = static_cast<double*>(x);
-        set_io(k, fs, &rs);
-        k.t0 = t; k.dt = h; k.n_steps = hs;
-        k.status = armed.status; k.status_value = armed.status_value;
-        if (int rc = launch_implicit<double>(p, k, q, st)) return rc;
-        t = clock_after(t, h, hs);
-    }
-    return CRB_OK;
+    KParams<double> base = base_params<double>(p);
+    arm_status(p, base, n_steps);
+    base.x = static_cast<double*>(x); base.dt = h;
+    return for_samples(n_steps, hold, t0, h, [&](int ks, int s, int hs, double t) -> int {
+        KParams<double> k = base;
+        if (int rc = sample_control(p, k, x, gain, ref, f, rec, control_record(p, u_out, work, ks), s, hs, hold, st)) return rc;
+        k.t0 = t; k.n_steps = hs;
+        return launch_implicit<double>(p, k, q, st);
+    });
 }
 }  // namespace
 
@@ -2597,9 +2613,32 @@ int tangent_checks(const crb_plan* p, int n_dir, const char* who) {
         return fail(CRB_EUNSUPPORTED, std::string(who) + ": beams of more than 256 thread-carried nodes are not supported");
     return check_count(who, "n_dir", n_dir);
 }
+// the input of a tangent rollout (CRB_EINVAL): the forcing, and the rule of its amplitude tangent
+int tangent_input(const crb_plan* p, const crb_input_desc* in, const crb_input_tangent* din, const std::string& who, Forcing* f) {
+    if (int rc = decode_input(p, in, who.c_str(), f)) return rc;
+    if (din && din->d_amp && !f->impulse)
+        return fail(CRB_EINVAL, who + ": d_amp needs an impulse input (its amplitude is what it differentiates)");
+    return CRB_OK;
+}
+// The base of a tangent launch from the state x as it stands on the stream: the seeds dx, the amplitude tangents and x -- for
+// more than one direction a copy of x, made here (instance d = 0 writes the base back while the others may still be loading it)
+int tangent_base(const crb_plan* p, const void* x, void* dx, int n_dir, const crb_input_tangent* din, hipStream_t st,
+                 TangentParams<double>* q) {
+    *q = TangentParams<double>{};
+    q->x0 = static_cast<const double*>(x);
+    if (n_dir > 1) {
+        const size_t bytes = state_doubles(p) * sizeof(double);
+        if (!p->d_tan_x0) HIP_TRY(hipMalloc(&p->d_tan_x0, bytes));
+        HIP_TRY(hipMemcpyAsync(p->d_tan_x0, x, bytes, hipMemcpyDeviceToDevice, st));
+        q->x0 = static_cast<const double*>(p->d_tan_x0);
+    }
+    q->dx = static_cast<double*>(dx);
+    if (din) q->d_amp = static_cast<const double*>(din->d_amp);
+    return CRB_OK;
+}
 // What the two tangent rollouts share once the caller has put its family's tables and step size into k: the state, forcing,
-// clock and status in k, the TangentParams -- the seeds dx, the input tangents (with a schedule its tangent d_sched in
-// df_held's place) and, for more than one direction, a copy of the base state -- and the family's launch(k, q).
+// clock and status in k, the TangentParams -- tangent_base and the held force's tangents (with a schedule its tangent d_sched
+// in df_held's place) -- and the family's launch(k, q).
 template <typename L>
 int tangent_rollout(const crb_plan* p, KParams<double> k, void* x, void* dx, int n_dir, double t0, int n_steps, const Forcing& f,
                     const crb_input_tangent* din, const Schedule& sc, const void* d_sched, hipStream_t st, L&& launch) {
@@ -2607,19 +2646,9 @@ int tangent_rollout(const crb_plan* p, KParams<double> k, void* x, void* dx, int
     set_io(k, f);
     k.t0 = t0; k.n_steps = n_steps;
     arm_status(p, k, n_steps);
-    TangentParams<double> q{};
-    q.x0 = k.x;
-    if (n_dir > 1) {   // (instance d = 0 writes the base back while the others may still be loading it: they read a copy)
-        const size_t bytes = state_doubles(p) * sizeof(double);
-        if (!p->d_tan_x0) HIP_TRY(hipMalloc(&p->d_tan_x0, bytes));
-        HIP_TRY(hipMemcpyAsync(p->d_tan_x0, x, bytes, hipMemcpyDeviceToDevice, st));
-        q.x0 = static_cast<const double*>(p->d_tan_x0);
-    }
-    q.dx = static_cast<double*>(dx);
-    if (din) {
-        q.du_held = static_cast<const double*>(din->df_held);
-        q.d_amp = static_cast<const double*>(din->d_amp);
-    }
+    TangentParams<double> q;
+    if (int rc = tangent_base(p, x, dx, n_dir, din, st, &q)) return rc;
+    if (din) q.du_held = static_cast<const double*>(din->df_held);
     if (sc.f) {
         set_sched(p, k, sc, 0);
         q.du_held = static_cast<const double*>(d_sched);
@@ -2669,9 +2698,7 @@ extern "C" int crb_step_rk4_tangent_sched(const crb_plan* p, void* x, void* dx, 
     if (n_steps < 0) return fail(CRB_EINVAL, "crb_step_rk4_tangent: n_steps must be >= 0");
     if (!(dt > 0)) return fail(CRB_EINVAL, "crb_step_rk4_tangent: dt must be positive");
     Forcing f;
-    if (int rc = decode_input(p, in, "crb_step_rk4_tangent", &f)) return rc;
-    if (din && din->d_amp && !f.impulse)
-        return fail(CRB_EINVAL, "crb_step_rk4_tangent: d_amp needs an impulse input (its amplitude is what it differentiates)");
+    if (int rc = tangent_input(p, in, din, "crb_step_rk4_tangent", &f)) return rc;
     if (t_end) *t_end = clock_after(t0, dt, n_steps);
     if (n_steps == 0) return CRB_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -3016,6 +3043,19 @@ int imp_adjoint_plan_checks(const crb_plan* p, const std::string& who) {
     if (p->NT > ADJ_MAX_NT) return fail(CRB_EUNSUPPORTED, who + ": beams of more than 256 thread-carried nodes are not supported");
     return CRB_OK;
 }
+// their siblings of the two implicit-tangent entry points: the caller's own CRB_EINVAL cases and tangent_input lie between them
+int imp_tangent_arg_checks(const std::string& who, int n_dir, int n_steps, int n_iter, double h) {
+    if (int rc = check_count(who, "n_dir", n_dir)) return rc;
+    if (n_steps < 0) return fail(CRB_EINVAL, who + ": n_steps must be >= 0");
+    if (n_iter < 1 || n_iter > IMP_ADJ_MAX_ITER) return fail(CRB_EINVAL, who + ": n_iter must be in [1, 16]");
+    if (!(h > 0)) return fail(CRB_EINVAL, who + ": h must be positive");
+    return CRB_OK;
+}
+int imp_tangent_plan_checks(const crb_plan* p, const std::string& who) {
+    if (p->dtype != CRB_F64) return fail(CRB_EUNSUPPORTED, who + ": the tangent of the implicit stepper needs an fp64 plan");
+    if (p->NT > TANGENT_MAX_NT) return fail(CRB_EUNSUPPORTED, who + ": beams of more than 256 thread-carried nodes are not supported");
+    return CRB_OK;
+}
 // the launch parameters of the implicit adjoint kernels: A's tables (stiff_tables, for alpha = h^2 / 4) where M's are
 int imp_adjoint_params(const crb_plan* p, double h, hipStream_t st, KParams<double>* k) {
     if (int rc = stiff_tables<double>(p, 0.25 * h * h, st)) return rc;
@@ -3174,20 +3214,14 @@ extern "C" int crb_step_implicit_tangent_sched(const crb_plan* p, void* x, void*
     const std::string who(sched || d_sched ? "crb_step_implicit_tangent_sched" : "crb_step_implicit_tangent");
     if (!p) return fail(CRB_EINVAL, who + ": null plan");
     if (!x || !dx) return fail(CRB_EINVAL, who + ": null state or tangent");
-    if (int rc = check_count(who, "n_dir", n_dir)) return rc;
-    if (n_steps < 0) return fail(CRB_EINVAL, who + ": n_steps must be >= 0");
-    if (n_iter < 1 || n_iter > IMP_ADJ_MAX_ITER) return fail(CRB_EINVAL, who + ": n_iter must be in [1, 16]");
-    if (!(h > 0)) return fail(CRB_EINVAL, who + ": h must be positive");
+    if (int rc = imp_tangent_arg_checks(who, n_dir, n_steps, n_iter, h)) return rc;
     Forcing f;
-    if (int rc = decode_input(p, in, who.c_str(), &f)) return rc;
-    if (din && din->d_amp && !f.impulse)
-        return fail(CRB_EINVAL, who + ": d_amp needs an impulse input (its amplitude is what it differentiates)");
+    if (int rc = tangent_input(p, in, din, who, &f)) return rc;
     if (d_sched && !sched) return fail(CRB_EINVAL, who + ": d_sched needs a schedule (sched is null)");
     Schedule sc;
     if (int rc = decode_schedule(sched, in, n_steps, who.c_str(), &sc)) return rc;
     if (sc.f && din && din->df_held) return fail(CRB_EINVAL, who + ": a schedule and dinput->df_held are given together");
-    if (p->dtype != CRB_F64) return fail(CRB_EUNSUPPORTED, who + ": the tangent of the implicit stepper needs an fp64 plan");
-    if (p->NT > TANGENT_MAX_NT) return fail(CRB_EUNSUPPORTED, who + ": beams of more than 256 thread-carried nodes are not supported");
+    if (int rc = imp_tangent_plan_checks(p, who)) return rc;
     if (int rc = need_device(p, who.c_str())) return rc;
     if (t_end) *t_end = clock_after(t0, h, n_steps);
     if (n_steps == 0) return CRB_OK;
@@ -3566,31 +3600,19 @@ extern "C" int crb_step_implicit_feedback_checkpoint(const crb_plan* p, void* x,
     KParams<double> base;
     if (int rc = imp_adjoint_params(p, h, st, &base)) return rc;
     base.x = static_cast<double*>(x);
-    const size_t F = force_doubles(p);
-    // entries of a force record that the product does not write (constrained DOFs, the padding component) read as zero
-    HIP_TRY(hipMemsetAsync(u_ckpt, 0, size_t((n_steps + hold - 1) / hold) * F * sizeof(double), st));
+    HIP_TRY(zero_controls(p, u_ckpt, nullptr, n_steps, hold, st));
     ImpAdjParams<double> iq = zeroed<ImpAdjParams<double>>();
     iq.n_iter = n_iter;
-    double t = t0;
-    for (int s = 0, ks = 0; s < n_steps; s += hold, ++ks) {
-        const int hs = n_steps - s < hold ? n_steps - s : hold;
-        double* const u = static_cast<double*>(u_ckpt) + size_t(ks) * F;
-        if (int rc = feedback_force_impl<double>(p, x, gain, ref, u, st)) return rc;
-        if (f.held)
-            HIP_TRY(crb::launch_feedback_held(u, static_cast<const double*>(f.held), p->d_row_off, p->n_free, p->B, size_t(p->n_node) * 4, st));
-        Forcing fs = f;
-        fs.held = u;
-        const Recording rs = sample_recording(r, s, hs, hold, state_doubles(p));
+    return for_samples(n_steps, hold, t0, h, [&](int ks, int s, int hs, double t) -> int {
         KParams<double> k = base;
-        set_io(k, fs, &rs);
+        if (int rc = sample_control(p, k, x, gain, ref, f, r, control_record(p, u_ckpt, nullptr, ks), s, hs, hold, st)) return rc;
         k.t0 = t; k.n_steps = hs;
         // one launch per sample: it starts from a^0 = 0 and stores the state it starts from -- into the checkpoint where the
         // sample opens a segment (every is a multiple of hold), else into the head of the work buffer, where nothing reads it
-        void* const start = s % every == 0 ? static_cast<double*>(ckpt) + size_t(s / every) * 3 * F : static_cast<double*>(work);
+        void* const start = s % every == 0 ? static_cast<double*>(ckpt) + size_t(s / every) * 3 * force_doubles(p) : static_cast<double*>(work);
         HIP_TRY(crb::launch_imp_adj_checkpoint(k, checkpoint_params(p, start, hold), iq, beam_groups(p), p->NT, st));
-        t = clock_after(t, h, hs);
-    }
-    return CRB_OK;
+        return CRB_OK;
+    });
 }
 
 extern "C" int crb_step_implicit_feedback_adjoint(const crb_plan* p, const void* ckpt, const void* u_ckpt, void* lam, int n_cot,
@@ -3620,14 +3642,12 @@ extern "C" int crb_step_implicit_feedback_adjoint(const crb_plan* p, const void*
     hipStream_t st = static_cast<hipStream_t>(stream);
     KParams<double> base;
     if (int rc = imp_adjoint_params(p, h, st, &base)) return rc;
-    Forcing fs = f;
-    fs.held = nullptr;   // (the held force is inside every u_k: the recompute reads u_ckpt as its schedule)
-    set_io(base, fs);
+    set_io(base, f);
+    base.u_held = nullptr;   // (the held force is inside every u_k: the recompute reads u_ckpt as its schedule)
     const size_t F = force_doubles(p), S = state_doubles(p);
     const int per_seg = every / hold, slices = crb::feedback_gain_grad_slices(p->B, p->n_free);
     const ImpFbAdjWork w = imp_fb_adj_work(p, work, every, n_iter, hold, n_cot);
-    Schedule sc;
-    sc.f = u_ckpt; sc.K = (n_steps + hold - 1) / hold; sc.hold = hold;
+    const Schedule sc{u_ckpt, (n_steps + hold - 1) / hold, hold};
     ImpAdjParams<double> iter = zeroed<ImpAdjParams<double>>();
     iter.n_iter = n_iter;
 
@@ -3723,17 +3743,11 @@ extern "C" int crb_step_implicit_feedback_tangent(const crb_plan* p, void* x, vo
     if (int rc = fb_adj_alias_checks(who, outs, out_names, ins,
                                      "x, gain, ref, dfb->d_gain, dfb->d_ref, input->f_held, input->amp, dinput->df_held or dinput->d_amp"))
         return rc;
-    if (int rc = check_count(who, "n_dir", n_dir)) return rc;
-    if (n_steps < 0) return fail(CRB_EINVAL, who + ": n_steps must be >= 0");
-    if (n_iter < 1 || n_iter > IMP_ADJ_MAX_ITER) return fail(CRB_EINVAL, who + ": n_iter must be in [1, 16]");
-    if (!(h > 0)) return fail(CRB_EINVAL, who + ": h must be positive");
+    if (int rc = imp_tangent_arg_checks(who, n_dir, n_steps, n_iter, h)) return rc;
     if (hold < 1) return fail(CRB_EINVAL, who + ": hold must be >= 1");
     Forcing f;
-    if (int rc = decode_input(p, in, who.c_str(), &f)) return rc;
-    if (d_amp && !f.impulse)
-        return fail(CRB_EINVAL, who + ": d_amp needs an impulse input (its amplitude is what it differentiates)");
-    if (p->dtype != CRB_F64) return fail(CRB_EUNSUPPORTED, who + ": the tangent of the implicit stepper needs an fp64 plan");
-    if (p->NT > TANGENT_MAX_NT) return fail(CRB_EUNSUPPORTED, who + ": beams of more than 256 thread-carried nodes are not supported");
+    if (int rc = tangent_input(p, in, din, who, &f)) return rc;
+    if (int rc = imp_tangent_plan_checks(p, who)) return rc;
     if (p->mixed_topology)
         return fail(CRB_EUNSUPPORTED, who + ": one gain matrix for the ensemble needs one free-DOF set (the plan has mixed topology)");
     if (int rc = need_device(p, who.c_str())) return rc;
@@ -3743,19 +3757,15 @@ extern "C" int crb_step_implicit_feedback_tangent(const crb_plan* p, void* x, vo
     KParams<double> base;
     if (int rc = imp_adjoint_params(p, h, st, &base)) return rc;   // (A's tables where M's are, base.dt = h)
     base.x = static_cast<double*>(x);
-    Forcing fs = f;
-    fs.held = nullptr;   // (the held force is inside every u_k)
-    set_io(base, fs);
+    set_io(base, f);
+    base.u_held = nullptr;   // (the held force is inside every u_k)
     // a beam that goes non-finite is marked with the step count at the end of the CALL, as crb_step_implicit_feedback does
     arm_status(p, base, n_steps);
-    const size_t F = force_doubles(p), S = state_doubles(p);
-    const int n_samples = (n_steps + hold - 1) / hold;
-    // the held input of a sample and its tangents: record k of u_out / du_out, else the one record (per direction) of work.
-    // Entries the boundary kernel does not write (constrained DOFs, the padding component) read as zero
-    double* const u0 = u_out ? static_cast<double*>(u_out) : static_cast<double*>(work);
+    const size_t F = force_doubles(p);
+    // a sample's du_k beside its u_k: record k of du_out, else one record per direction behind work's; zeroed as the controls are
     double* const du0 = du_out ? static_cast<double*>(du_out) : static_cast<double*>(work) + F;
-    const size_t u_step = u_out ? F : 0, du_step = du_out ? F : 0, du_dir = du_out ? size_t(n_samples) * F : F;
-    HIP_TRY(hipMemsetAsync(u0, 0, (u_out ? size_t(n_samples) : size_t(1)) * F * sizeof(double), st));
+    const size_t du_step = du_out ? F : 0, du_dir = du_out ? size_t((n_steps + hold - 1) / hold) * F : F;
+    HIP_TRY(zero_controls(p, u_out, work, n_steps, hold, st));
     HIP_TRY(hipMemsetAsync(du0, 0, size_t(n_dir) * du_dir * sizeof(double), st));
 
     crb::ImpFbTanParams b = zeroed<crb::ImpFbTanParams>();
@@ -3774,30 +3784,18 @@ extern "C" int crb_step_implicit_feedback_tangent(const crb_plan* p, void* x, vo
     b.df_held = static_cast<const double*>(df_held);
     b.du_dir_stride = du_dir;
 
-    TangentParams<double> q{};
-    q.x0 = base.x;
-    if (n_dir > 1) {   // (instance d = 0 writes the base back while the others may still be loading it: they read a copy)
-        if (!p->d_tan_x0) HIP_TRY(hipMalloc(&p->d_tan_x0, S * sizeof(double)));
-        q.x0 = static_cast<const double*>(p->d_tan_x0);
-    }
-    q.dx = static_cast<double*>(dx);
-    q.d_amp = static_cast<const double*>(d_amp);
-    q.du_dir_stride = du_dir;
-    double t = t0;
-    for (int s = 0, ks = 0; s < n_steps; s += hold, ++ks) {
-        const int hs = n_steps - s < hold ? n_steps - s : hold;
-        b.u = u0 + size_t(ks) * u_step;
+    return for_samples(n_steps, hold, t0, h, [&](int ks, int, int hs, double t) -> int {
+        b.u = control_record(p, u_out, work, ks);
         b.du = du0 + size_t(ks) * du_step;
         HIP_TRY(crb::launch_imp_fb_tangent_boundary(b, st));
-        if (n_dir > 1) HIP_TRY(hipMemcpyAsync(p->d_tan_x0, x, S * sizeof(double), hipMemcpyDeviceToDevice, st));
+        TangentParams<double> q;   // (the base as the boundary kernel read it: the sample's steps advance x)
+        if (int rc = tangent_base(p, x, dx, n_dir, din, st, &q)) return rc;
+        q.du_held = b.du; q.du_dir_stride = du_dir;
         KParams<double> k = base;
         k.t0 = t; k.n_steps = hs;
-        Schedule sc;   // the sample as the one interval of a schedule: the kernel never switches (hs <= hold)
-        sc.f = b.u; sc.K = 1; sc.hold = hold;
-        set_sched(p, k, sc, 0);
-        q.du_held = b.du;
+        // the sample as the one interval of a schedule: the kernel never switches (hs <= hold)
+        set_sched(p, k, Schedule{b.u, 1, hold}, 0);
         HIP_TRY(crb::launch_imp_jvp_step(k, q, n_iter, true, beam_groups(p), n_dir, p->NT, st));
-        t = clock_after(t, h, hs);
-    }
-    return CRB_OK;
+        return CRB_OK;
+    });
 }

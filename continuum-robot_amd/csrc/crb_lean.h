@@ -214,7 +214,10 @@ __device__ __forceinline__ void lean_rhs(const ElemCoef<T>& ec, T dragc, bool co
 //   separator level (stride 4) through the wave's own LDS strip [3][4 + 64 + 4] (3 ds_write_b64 + 6 ds_read_b64 at immediate
 //   offsets instead of 24 DPP moves; the pads, zeroed once, are the 0 that a bound_ctrl shift brings in past the root and the
 //   tip, so the results are bitwise those of the shifts).  No barrier in the step loop: a wave's LDS accesses execute in order.
-//   A workgroup is four independent beam walkers.
+//   A workgroup is four independent beam walkers.  The first two rounds are off the stage's dependent chain, and were still
+//   slower through strips of their own (3 ds_write_b64 + 3 ds_read_b64 each, at -1 / +1 column, reads behind the writes;
+//   measured, DESIGN.md §4, three rounds: +0.15 .. 0.18 us per step for the q round alone, +0.12 .. 0.24 for the left half
+//   alone, +0.36 .. 0.46 for both, with 24 / 24 / 48 v_mov_b32_dpp fewer per step): not taken.
 // The solve's 75 wave-uniform constants (the interior's factors, W_L / W_R, A_s / C_s) sit in five fp64 registers per lane,
 // loaded once per launch: constant k in lane k % 16 of every 16-lane row of register k / 16 (crb_blocked.h: BLK_TAB_*).  The 66
 // multiply-adds per stage that use one take it as the DPP row-broadcast source of v_fmac_f64 (blk_bc_fma / blk_bc_fnma: no
@@ -283,6 +286,24 @@ __device__ __forceinline__ void lean_rhs(const ElemCoef<T>& ec, T dragc, bool co
 // has the timings of the four variants, of this build and of its parent, and the counters.  CRB_BLK_SHARE /
 // CRB_BLK_CONST_AHEAD / CRB_BLK_HOLD_PARAMS (=0 in the tuning build) switch each off; with all three off the unit's
 // code is the parent's line for line.
+// Two pieces of the stage's vector work that is no arithmetic are gone, neither changing a computed value.
+// CRB_BLK_F3_PLUS: the right transverse half is carried as +f3 through the impulse block (its dof-1 line adds amp; (f3 + amp)
+// is exactly -(-f3 - amp)) instead of being stored as -f3 -- an in/out operand of the block, so the negation was materialised
+// as a v_xor_b32 and a v_mov_b32 per node -- and negated again in the right-hand side; node k's transverse right-hand side
+// stands directly behind its block, as the last reader of the f3 that the next block takes in/out, so that no copy is made
+// either.  CRB_BLK_SEP_ADDR: the separator tables are read at immediate offsets from this lane's LDS byte address, formed once
+// per launch and laundered in place per level, instead of through a laundered lane index that was scaled again at every level.
+// Step loop of the tuning build, per step (parent / F3_PLUS alone / SEP_ADDR alone / both): VALU 1634 / 1602 / 1614 / 1582,
+// v_xor_b32 16 / 0 / 16 / 0, v_mov_b32_e32 20 / 4 / 16 / 0, v_lshl_add_u32 16 / 16 / 0 / 0, fp64 1322 and v_mov_b32_dpp 240 in
+// each; VGPRs 256 / 252 / 256 / 252, 103 SGPRs as the assembler totals them, no spill, no scratch.  The linear instance: VALU 1198
+// -> 1146 (v_xor_b32 20 -> 4, v_mov_b32_e32 24 -> 4, v_lshl_add_u32 16 -> 0), fp64 893 and its mix unchanged, 238 -> 236 VGPRs.
+// Measured (tuning builds, one box, alternating, three rounds): 12.121 / 12.125 / 12.106 us per step with neither,
+// 12.083 / 12.116 / 12.071 and 12.092 / 12.089 / 12.078 with one, 12.032 / 12.041 / 12.023 with both: -0.7 % for the pair, which
+// is more than three round-to-round spreads; either item alone is not.  The whole library against its parent's on another
+// box: 12.167 / 12.187 / 12.191 against 12.263 / 12.301 / 12.260 (-0.8 %, below in every round, short of three of the parent's
+// spreads there), 13.55 against 13.79 at 20 steps per launch, 1.206 against 1.222 ms per 100-step launch in the kernel trace:
+// about a fifth of what 52 of 1634 issue slots project.  Outputs are bitwise the parent's, config 3 (state and
+// clock) and the linear instance.  With both switches off (=0 in the tuning build) the unit's code is the parent's line for line.
 // The next beam's state is not prefetched as in the one-node-per-lane
 // form: four nodes' records are 48 more registers than the budget of two waves per SIMD holds.
 #ifndef CRB_BLK_CHORD
@@ -302,6 +323,12 @@ __device__ __forceinline__ void lean_rhs(const ElemCoef<T>& ec, T dragc, bool co
 #endif
 #ifndef CRB_BLK_RK4_POS
 #define CRB_BLK_RK4_POS 1
+#endif
+#ifndef CRB_BLK_F3_PLUS
+#define CRB_BLK_F3_PLUS 1
+#endif
+#ifndef CRB_BLK_SEP_ADDR
+#define CRB_BLK_SEP_ADDR 1
 #endif
 constexpr int BLK_STRIP_PAD = 4;   // the stride of the separator level that goes through the wave's LDS strip (the third)
 constexpr int BLK_STRIP_W = BLK_STRIP_PAD + BLK_LANES + BLK_STRIP_PAD;
@@ -337,6 +364,12 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
     // with the constants arriving under the solve these seven registers no longer push anything out of the scalar file
     // (needs CRB_BLK_CONST_AHEAD)
     constexpr bool HOLD = AHEAD && CRB_BLK_HOLD_PARAMS;
+    // the stage's vector work that is no arithmetic (neither item changes a computed value):
+    // +f3 carried through the impulse block as the right transverse half, instead of -f3 negated again in the right-hand side
+    constexpr bool F3PLUS = CRB_BLK_F3_PLUS && (REGROUP || EM == EM_LINEAR);
+    // the separator tables read at immediate offsets from this lane's LDS byte address, laundered per level in place,
+    // instead of through the laundered lane index (a new index every time, scaled again every time)
+    constexpr bool SEPADDR = CRB_BLK_SEP_ADDR;
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef const __attribute__((address_space(4))) SlotConst<T>* CS;
     typedef const __attribute__((address_space(4))) T* CK;
@@ -374,6 +407,13 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
     typedef volatile T* SP;
 #endif
     const SP strip = (SP)(strips + wave * 3 * BLK_STRIP_W + BLK_STRIP_PAD + lane);
+    // SEPADDR: this lane's column of the separator tables, value pair v at sepc[v * 64]
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const __attribute__((address_space(3))) pair2* SEPC;
+#else
+    typedef const pair2* SEPC;
+#endif
+    [[maybe_unused]] SEPC sepc = (SEPC)(sepL + lane);
     // the wave-uniform table, once per launch: constant k in lane k % 16 of every row of tab[k / 16] (crb_blocked.h), and
     // broadcast copies of the nine constants that multiply without adding (the first product of each blk_mul sum)
     T tab[BLK_TAB_REGS];
@@ -513,14 +553,17 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                         if constexpr (SHARE) e = elem_force_nonlinear_shared<T, const T*>(fk, k ? sq[k - 1] : qL, sq[k]);
                         else e = elem_force_nonlinear_folded<T, const T*>(fk, k ? sq[k - 1] : qL, sq[k]);
                         f2[k] = e.f2; cW[k] = e.W;   // (W carries cA1)
-                        fl[k][1] = e.f3; fr[k][1] = -e.f3; fl[k][2] = e.m_left; fr[k][2] = e.m_right;
+                        fl[k][1] = e.f3; fr[k][1] = F3PLUS ? e.f3 : -e.f3; fl[k][2] = e.m_left; fr[k][2] = e.m_right;
                     } else if constexpr (REGROUP) {
                         const ElemForceRegrouped<T> e = CHORD ? elem_force_nonlinear_chord<T>(ec, k ? sq[k - 1] : qL, sq[k])
                                                               : elem_force_nonlinear_regrouped<T>(ec, k ? sq[k - 1] : qL, sq[k]);
                         f2[k] = e.f2; cW[k] = ec[1] * e.W;
-                        fl[k][1] = e.f3; fr[k][1] = -e.f3; fl[k][2] = e.m_left; fr[k][2] = e.m_right;
+                        fl[k][1] = e.f3; fr[k][1] = F3PLUS ? e.f3 : -e.f3; fl[k][2] = e.m_left; fr[k][2] = e.m_right;
                     } else if (EM == EM_NONLINEAR) elem_force_nonlinear<T>(ec, k ? sq[k - 1] : qL, sq[k], false, fl[k], fr[k]);
-                    else elem_force_linear<T>(ec, k ? sq[k - 1] : qL, sq[k], fl[k], fr[k]);
+                    else {
+                        elem_force_linear<T>(ec, k ? sq[k - 1] : qL, sq[k], fl[k], fr[k]);
+                        if constexpr (F3PLUS) fr[k][1] = fl[k][1];   // (the linear element's right transverse half is -fl[1])
+                    }
                 }
                 if constexpr (REGROUP) {
                     // the axial right-hand side less its last product, negated: fr[k][0] enters r as -fr[k][0] below, as the
@@ -538,34 +581,56 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                 //    written as an opaque block per node because a C++ branch here splits the stage's straight-line code, which
                 //    the scheduler then no longer interleaves with the solve (measured: 50 spilled VGPRs).  No lane shift inside.
                 //    After a compiler upgrade re-check with `make resource-usage`: this kernel at 0 SGPR spills, <= 256 VGPRs
-                //    (256 with the folded forces and the RK4 positions on the accelerations, 97 SGPRs with the constants a stage ahead: the ceiling of two waves per SIMD, with no register of headroom left -- a compiler that needs one more spills), no scratch.  The block can go back to the C++ form of the host branch below once that no longer splits the
+                //    (252 with +f3 carried through this block, CRB_BLK_F3_PLUS; 256 without it, the ceiling of two waves per SIMD, where
+                //    a compiler that needs one more register spills; 97 SGPRs allocated with the constants a stage ahead, 103 as the
+                //    tool totals them), no scratch.  The block can go back to the C++ form of the host branch below once that no longer splits the
                 //    schedule (same resource figures, same step time).
                 {
                     const int kon = imp_on ? kimp : -1, dof = HOLD ? dof_held : q.imp_dof;
+                    // (F3PLUS: the transverse left half of lane+1's first element, for the last node's right-hand side below)
+                    [[maybe_unused]] T flR1 = T(0);
+                    if constexpr (F3PLUS) flR1 = dpp_from_higher(fl[0][1]);
 #if defined(__HIP_DEVICE_COMPILE__)
+                    // (SGN1: the sign of amp on the transverse dof -- "-" on fr[k][1] = -f3, "" on +f3 carried through, F3PLUS)
+#define CRB_BLK_IMPULSE(SGN1)                                                                  \
+                        asm volatile(                                                          \
+                            "s_cmp_lg_u32 %[kon], %[k]\n\t"                                    \
+                            "s_cbranch_scc1 2f\n\t"                                            \
+                            "s_cmp_lg_u32 %[dof], 0\n\t"                                       \
+                            "s_cbranch_scc1 0f\n\t"                                            \
+                            "v_add_f64 %[f0], %[f0], -%[amp]\n"                                \
+                            "0:\n\t"                                                           \
+                            "s_cmp_lg_u32 %[dof], 1\n\t"                                       \
+                            "s_cbranch_scc1 1f\n\t"                                            \
+                            "v_add_f64 %[f1], %[f1], " SGN1 "%[amp]\n"                         \
+                            "1:\n\t"                                                           \
+                            "s_cmp_lg_u32 %[dof], 2\n\t"                                       \
+                            "s_cbranch_scc1 2f\n\t"                                            \
+                            "v_add_f64 %[f2], %[f2], -%[amp]\n"                                \
+                            "2:"                                                               \
+                            : [f0] "+v"(fr[k][0]), [f1] "+v"(fr[k][1]), [f2] "+v"(fr[k][2])    \
+                            : [kon] "s"(kon), [dof] "s"(dof), [amp] "v"(amp), [k] "n"(k)       \
+                            : "scc")
 #pragma unroll
-                    for (int k = 0; k < NP; ++k)
-                        asm volatile(
-                            "s_cmp_lg_u32 %[kon], %[k]\n\t"
-                            "s_cbranch_scc1 2f\n\t"
-                            "s_cmp_lg_u32 %[dof], 0\n\t"
-                            "s_cbranch_scc1 0f\n\t"
-                            "v_add_f64 %[f0], %[f0], -%[amp]\n"
-                            "0:\n\t"
-                            "s_cmp_lg_u32 %[dof], 1\n\t"
-                            "s_cbranch_scc1 1f\n\t"
-                            "v_add_f64 %[f1], %[f1], -%[amp]\n"
-                            "1:\n\t"
-                            "s_cmp_lg_u32 %[dof], 2\n\t"
-                            "s_cbranch_scc1 2f\n\t"
-                            "v_add_f64 %[f2], %[f2], -%[amp]\n"
-                            "2:"
-                            : [f0] "+v"(fr[k][0]), [f1] "+v"(fr[k][1]), [f2] "+v"(fr[k][2])
-                            : [kon] "s"(kon), [dof] "s"(dof), [amp] "v"(amp), [k] "n"(k)
-                            : "scc");
+                    for (int k = 0; k < NP; ++k) {
+                        if constexpr (F3PLUS) {
+                            // (node k's transverse right-hand side directly behind its block: it is the last reader of
+                            //  fl[k + 1][1], the very f3 that the next block takes in/out -- dead by then, it needs no copy)
+                            CRB_BLK_IMPULSE("");
+                            r[k][1] = (fr[k][1] + drag_force<T>(dragc, sv[k][1])) - ((k + 1 < NP) ? fl[k + 1][1] : flR1);
+                        } else CRB_BLK_IMPULSE("-");
+                    }
+#undef CRB_BLK_IMPULSE
 #else
                     for (int k = 0; k < NP; ++k)
-                        for (int c = 0; c < 3; ++c) fr[k][c] -= (kon == k && c == dof) ? amp : T(0);
+                        for (int c = 0; c < 3; ++c) {
+                            const T ac = (kon == k && c == dof) ? amp : T(0);
+                            if (F3PLUS && c == 1) fr[k][c] += ac;
+                            else fr[k][c] -= ac;
+                        }
+                    if constexpr (F3PLUS)
+                        for (int k = 0; k < NP; ++k)
+                            r[k][1] = (fr[k][1] + drag_force<T>(dragc, sv[k][1])) - ((k + 1 < NP) ? fl[k + 1][1] : flR1);
 #endif
                 }
                 CRB_SETPRIO(P_TAIL);
@@ -577,6 +642,7 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                         for (int k = 0; k < NP; ++k) r[k][0] = (k + 1 < NP) ? (-fr[k][0] - cW[k + 1]) : (-f2[k] - fr[k][0]);
                         continue;
                     }
+                    if (F3PLUS && c == 1) continue;   // (formed behind the impulse blocks, above)
                     const T flR = dpp_from_higher(fl[0][c]);
 #pragma unroll
                     for (int k = 0; k < NP; ++k) {
@@ -603,13 +669,20 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                 //    row is fma(m1, v1, m2 v2), and the axial row of a blk_mul / blk_sub_mul pair is fma(d, v, -(u w))
                 T y[3][3], z1[3], z2[3], g[3], y0R[3];
                 // (the first separator level's table is requested here, under the interior solve, which has no wait of its own:
-                //  the lane index is laundered through the right-hand side, so that the reads are issued where the solve starts)
-                int li = lane;
+                //  what the reads are addressed by is laundered through the right-hand side, so that they are issued where the solve
+                //  starts.  SEPADDR: that is the lane's table address, laundered in place -- the old value is dead, so nothing is
+                //  copied or scaled again -- with every read at an immediate offset from it; otherwise the lane index)
+                [[maybe_unused]] int li = lane;
                 T cf0[PCR_LEVEL_VALS];
-                asm volatile("" : "+v"(li) : "v"(r[0][0]));
+                auto sep_pair = [&](int v2) -> pair2 {
+                    if constexpr (SEPADDR) return sepc[v2 * 64];
+                    else return sepL[v2 * 64 + li];
+                };
+                if constexpr (SEPADDR) asm volatile("" : "+v"(sepc) : "v"(r[0][0]));
+                else asm volatile("" : "+v"(li) : "v"(r[0][0]));
 #pragma unroll
                 for (int i = 0; i < PCR_LEVEL_VALS; i += 2) {
-                    const pair2 e = sepL[(i / 2) * 64 + li];
+                    const pair2 e = sep_pair(i / 2);
                     cf0[i] = e[0]; cf0[i + 1] = e[1];
                 }
 #pragma unroll
@@ -635,15 +708,17 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                 blk_bc_sub_mul<BU_CS>(tab, y0R, g);
 #pragma unroll
                 for (int l = 0; l < LS; ++l) {
-                    // (the lane index is laundered through this level's input, so that the table loads of the later levels are
-                    //  issued when they start instead of all at the top of the loop: the tables would otherwise take 70 registers)
-                    asm volatile("" : "+v"(li) : "v"(g[0]));
+                    // (the table address -- without SEPADDR the lane index -- is laundered through this level's input, so that
+                    //  the table loads of the later levels are issued when they start instead of all at the top of the loop: the
+                    //  tables would otherwise take 70 registers)
+                    if constexpr (SEPADDR) asm volatile("" : "+v"(sepc) : "v"(g[0]));
+                    else asm volatile("" : "+v"(li) : "v"(g[0]));
                     T cf[PCR_LEVEL_VALS];
 #pragma unroll
                     for (int i = 0; i < PCR_LEVEL_VALS; i += 2) {
                         const int v = l * PCR_LEVEL_VALS + i;   // (even: PCR_LEVEL_VALS is)
                         if (l == 0) { cf[i] = cf0[i]; cf[i + 1] = cf0[i + 1]; continue; }
-                        const pair2 e = sepL[(v / 2) * 64 + li];
+                        const pair2 e = sep_pair(v / 2);
                         cf[i] = e[0]; cf[i + 1] = e[1];
                     }
                     T glo[3], ghi[3];
@@ -661,12 +736,13 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                     }
                     pcr_apply_level<T>(cf, glo, ghi, g);
                 }
-                asm volatile("" : "+v"(li) : "v"(g[0]));
+                if constexpr (SEPADDR) asm volatile("" : "+v"(sepc) : "v"(g[0]));
+                else asm volatile("" : "+v"(li) : "v"(g[0]));
                 T fin[6], xs[3], xsL[3];
 #pragma unroll
                 for (int i = 0; i < 6; i += 2) {
                     const int v = LS * PCR_LEVEL_VALS + i;
-                    const pair2 e = sepL[(v / 2) * 64 + li];
+                    const pair2 e = sep_pair(v / 2);
                     fin[i] = e[0]; fin[i + 1] = e[1];
                 }
                 pcr_apply_final<T>(fin, g, xs);

@@ -231,6 +231,15 @@ def load():
                                                      C.POINTER(RecordDesc), vp, _dp, vp]
     L.crb_step_implicit_adjoint_sched.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, i32, i32, i32, C.POINTER(InputDesc),
                                                   C.POINTER(RecordDesc), C.POINTER(InputCotangent), sched, vp, vp, vp]
+    L.crb_implicit_adjoint_params_work_bytes.restype = C.c_size_t
+    L.crb_implicit_adjoint_params_work_bytes.argtypes = [vp, i32, i32, i32]
+    L.crb_step_implicit_adjoint_params.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, i32, i32, i32,
+                                                   C.POINTER(InputDesc), C.POINTER(RecordDesc), C.POINTER(InputCotangent),
+                                                   C.POINTER(ParamCotangent), vp, vp]
+    L.crb_step_implicit_adjoint_params_sched.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, i32, i32, i32,
+                                                         C.POINTER(InputDesc), C.POINTER(RecordDesc),
+                                                         C.POINTER(InputCotangent), C.POINTER(ParamCotangent), sched, vp, vp,
+                                                         vp]
     L.crb_step_implicit_tangent.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, i32, i32, C.POINTER(InputDesc),
                                             C.POINTER(InputTangent), _dp, vp]
     L.crb_step_implicit_tangent_sched.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, i32, i32, C.POINTER(InputDesc),

@@ -917,7 +917,8 @@ class BeamEnsemble:
     def checkpoint_interval(self, n_steps: int, checkpoint_every: Optional[int] = None,
                             param_cotangents: Optional[int] = None, feedback_cotangents: Optional[int] = None,
                             implicit: Optional[Tuple[int, int]] = None,
-                            implicit_feedback: Optional[Tuple[int, int, int]] = None) -> int:
+                            implicit_feedback: Optional[Tuple[int, int, int]] = None,
+                            implicit_params: Optional[Tuple[int, int]] = None) -> int:
         """Steps per checkpoint segment of an adjoint rollout: ``checkpoint_every``, or ceil(sqrt(n_steps)) lowered until the
         work buffer of crb_step_rk4_adjoint (crb_rk4_adjoint_work_bytes) fits ADJOINT_WORK_BUDGET.  ``param_cotangents``: the
         number of cotangents of a ``step_adjoint_params`` call, whose work buffer
@@ -926,7 +927,13 @@ class BeamEnsemble:
         (crb_implicit_adjoint_work_bytes); ``implicit_feedback`` = (n_iter, hold, n_cot): that of a
         ``step_implicit_feedback_adjoint`` call (crb_implicit_feedback_adjoint_work_bytes), whose segments are whole samples:
         ceil(sqrt(n_steps)) rounded up to a multiple of ``hold`` and lowered by ``hold`` while the buffer exceeds the budget
-        (ValueError if one sample per segment does not fit); a given ``checkpoint_every`` must be a multiple of ``hold``."""
+        (ValueError if one sample per segment does not fit); a given ``checkpoint_every`` must be a multiple of ``hold``;
+        ``implicit_params`` = (n_iter, n_cot): that of a ``step_implicit_adjoint_params`` call
+        (crb_implicit_adjoint_params_work_bytes)."""
+        if implicit_params is not None:
+            if any(a is not None for a in (implicit, implicit_feedback, param_cotangents, feedback_cotangents)):
+                raise ValueError("checkpoint_interval: implicit_params and another family's argument are given together")
+            return self._interval(_IMPLICIT_PARAMS, n_steps, checkpoint_every, (None, implicit_params[0]), implicit_params[1])
         if implicit_feedback is not None:
             if implicit is not None or param_cotangents is not None or feedback_cotangents is not None:
                 raise ValueError("checkpoint_interval: implicit_feedback and another family's argument are given together")
@@ -1152,10 +1159,29 @@ class BeamEnsemble:
         ([D, K, B, n]); intervals the rollout does not reach, and entries past a beam's own DOF count in mixed-topology
         ensembles, are exact zeros.  The scheduled rollout is the chain of one call per interval, so every interval's first step
         starts its iteration from 0 and the cotangent carried through the starting iterate is dropped there.
-        Not available: the damped variant (``rho_inf`` < 1), the closed loop, and gradients with respect to the rod's own
-        parameters (E and I enter the iteration matrix)."""
-        return self._rollout_adjoint(_IMPLICIT, n_steps, (h, n_iter), lam_red, x0_red, impulse_amp, impulse_duration,
+        Not available: the damped variant (``rho_inf`` < 1) and the closed loop.  ``step_implicit_adjoint_params`` also gives
+        the gradient with respect to the rod's own parameters."""
+        return self._rollout_adjoint(_IMPLICIT, n_steps, (h, n_iter, None, None), lam_red, x0_red, impulse_amp, impulse_duration,
                                      impulse_index, held_force, t0, record, record_every, lam_record, checkpoint_every)
+
+    def step_implicit_adjoint_params(self, n_steps: int, h: float, lam_red, n_iter: int = 2, x0_red=None, impulse_amp=None,
+                                     impulse_duration: float = 0.01, impulse_index: int = -2, held_force=None,
+                                     t0: Optional[float] = None, record=None, record_every: int = 1, lam_record=None,
+                                     checkpoint_every: Optional[int] = None, control=None, control_hold: Optional[int] = None):
+        """``step_implicit_adjoint`` (the same arguments, ``control`` [K, B, n] / ``control_hold`` for
+        ``held_force=ControlSchedule(control, control_hold)``; the first three returns are bitwise its returns) with a fourth
+        return: ``step_adjoint_params``' dict of gradients with respect to the rod itself -- EA_scale, EI_scale,
+        elastic_modulus, moment_inertia, drag_scale, drag_coef, fluid_density, gravity, with the shapes and meanings given
+        there -- through the stepper that takes h = 1e-4 ... 1e-3 s (crb_step_implicit_adjoint_params: the same sweep, storing
+        gbar = A^-T abar of every iteration, and one reduction launch per segment).  E and I enter the iteration matrix
+        A = M + h^2/4 K0 as well as the force, so every iteration adds gbar^T dF/dtheta at its (q_m, v_m) AND
+        h^2/4 gbar^T (dK0/dtheta) (a^i - a^{i+1}), the part a fixed iteration count leaves; the gradient is that of the map
+        step_implicit computes with ``n_iter`` iterations, and does not depend on ``checkpoint_every``, bitwise.
+        Not available: gradients with respect to length, cross_area and density (they enter the mass matrix), the damped
+        variant, the sampled-data loop, parameters as autograd inputs of ``rollout_implicit``."""
+        return self._rollout_adjoint(_IMPLICIT_PARAMS, n_steps, (h, n_iter, control, control_hold), lam_red, x0_red, impulse_amp,
+                                     impulse_duration, impulse_index, held_force, t0, record, record_every, lam_record,
+                                     checkpoint_every)
 
     def rollout_implicit(self, x0_red, n_steps: int, h: float, n_iter: int = 2, impulse_amp=None, held_force=None,
                          impulse_duration: float = 0.01, impulse_index: int = -2, t0: float = 0.0, record=None,
@@ -2131,8 +2157,9 @@ _RK4_PARAMS = _RK4._replace(
 
 
 def _implicit_prepare(ens, n_steps, args, held_force, impulse_amp, record):
-    held_force, sch = ens._control(held_force, None, None, n_steps, "step_implicit_adjoint", "implicit steps")
-    return args, held_force, sch, impulse_amp is not None
+    h, n_iter, control, control_hold = args
+    held_force, sch = ens._control(held_force, control, control_hold, n_steps, "step_implicit_adjoint", "implicit steps")
+    return (h, n_iter), held_force, sch, impulse_amp is not None
 
 
 def _implicit_checkpoint(ens, x, ckpt, n_steps, every, t0, step, desc, sd, rec, t_end):
@@ -2154,6 +2181,23 @@ _IMPLICIT = _AdjointFamily(
     who="step_implicit_adjoint", prepare=_implicit_prepare, ckpt_shape=lambda ens: (ens.n_beams, 3, ens.n_node, 4),
     work_bytes=lambda ens, every, step, n_cot: ens._lib.crb_implicit_adjoint_work_bytes(ens.plan.h, every, int(step[1]), n_cot),
     checkpoint=_implicit_checkpoint, outputs=_input_outputs, sweep=_implicit_sweep, unpack=_input_unpack)
+
+
+def _implicit_params_sweep(ens, ckpt, lamd, n_steps, every, t0, step, desc, sd, rec_bar, outs, work):
+    grad, sched_bar = _input_cotangent(ens, outs, sd)
+    pgrad = nat.ParamCotangent()
+    pgrad.param_bar = outs[2].data_ptr()
+    return ens._lib.crb_step_implicit_adjoint_params_sched(ens.plan.h, ens._ptr(ckpt), ens._ptr(lamd), int(lamd.shape[0]), t0,
+                                                           float(step[0]), n_steps, int(step[1]), every, C.byref(desc),
+                                                           ens._ref(rec_bar), C.byref(grad), C.byref(pgrad), ens._ref(sd),
+                                                           sched_bar, ens._ptr(work), ens._stream())
+
+
+# step_implicit_adjoint_params: the same pass, the storing sweep, and _RK4_PARAMS' third buffer and dict
+_IMPLICIT_PARAMS = _IMPLICIT._replace(
+    work_bytes=lambda ens, every, step, n_cot: ens._lib.crb_implicit_adjoint_params_work_bytes(ens.plan.h, every, int(step[1]),
+                                                                                               n_cot),
+    outputs=_RK4_PARAMS.outputs, sweep=_implicit_params_sweep, unpack=_RK4_PARAMS.unpack)
 
 
 def _feedback_prepare(ens, n_steps, args, held_force, impulse_amp, record):

@@ -26,6 +26,9 @@
 // every cotangent (grid y); lambda, cbar and the input cotangents stay in registers across the segment, cbar passes from one
 // segment's launch to the next through `carry`.  The sums are the same additions in the same order for any segment length
 // and any number of cotangents: the gradient does not depend on either, bitwise.  No floating-point atomics.
+// The parameter path (crb_implicit_paramgrad.h) runs two variants compiled in by the mode, so that the three modes above stay the
+// code they were: IADJ_SEG_FIN, the recompute that also keeps the final iterate of the segment's last step, and IADJ_BWD_STORE,
+// the sweep that also stores every iteration's masked gbar (one store per iteration, the lane address formed once).
 // Mapping, LDS and constrained DOFs: those of crb_adjoint.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -34,7 +37,9 @@
 
 namespace crb {
 
-enum : int { IADJ_CKPT = 0, IADJ_SEG = 1, IADJ_BWD = 2 };
+// IADJ_BWD_STORE: IADJ_BWD that also writes every iteration's masked gbar for crb_imp_param_grad_kernel (crb_implicit_paramgrad.h)
+// IADJ_SEG_FIN: IADJ_SEG that also writes the final iterate of the segment's last step, which the same kernel needs
+enum : int { IADJ_CKPT = 0, IADJ_SEG = 1, IADJ_BWD = 2, IADJ_BWD_STORE = 3, IADJ_SEG_FIN = 4 };
 
 // The implicit launches' own fields, next to KParams<T> (A's tables in pcr_levels / pcr_final, p.dt = h) and AdjParams<T>
 // (gadj, states / clocks / store_every / write_back, work / work_clock, lam / amp_bar / f_bar, step0 with their meanings there;
@@ -47,7 +52,23 @@ struct ImpAdjParams {
     T* carry;         // IADJ_BWD: [n_cot][B][n_node][4] cbar at the segment's first step, written; read when carry_in
     int carry_in;     // IADJ_BWD: 0 for the call's last segment (cbar = 0)
     int n_iter;
+    // the parameter path (last, so that the fields above keep their kernel-argument offsets)
+    T* gbar;          // IADJ_BWD_STORE: [n_steps][n_iter][n_cot][B][n_node][4] the masked gbar = Ainv^T abar of every iteration
+    T* fin_out;       // IADJ_SEG_FIN: [B][n_node][4] the final iterate a^{n_iter} of the segment's last step.  With a schedule
+                      //  the mode also moves the final iterate of every step an interval ends on INSIDE the segment into the
+                      //  slot of the next step's a^0 (a constant 0, which IADJ_BWD_STORE and the reduction put back); the
+                      //  reduction reads the record
 };
+
+// (kl, kr) = the left-node and right-node halves of K0's element block on (zl, a): elem_force_linear on the element's linear
+// coefficient pack, with the axial block [[c0, -s c0], [-c0, c0]] (s = 0 for the shipped nonlinear element, whose f1 has no u2 term)
+template <typename T>
+__device__ __forceinline__ void imp_k0_elem(const ElemCoef<T>& e, bool corrected, const T zl[3], const T a[3], T kl[3], T kr[3]) {
+    T lin[5] = {T(0), T(0), T(0), T(0), T(0)};
+    elem_linear_coefs<T>(e.c, e.kind, lin);
+    elem_force_linear<T>(lin, zl, a, kl, kr);
+    if (e.kind == KIND_NONLINEAR && !corrected) kl[0] = lin[0] * zl[0];   // tangent of the shipped f1: no u2 term
+}
 
 // out = K0 a of this thread's node: the element left of the node on (a_{j-1}, a_j) by elem_force_linear (its right-node half
 // stays, its left-node half goes left through LDS).  Whole workgroup; uses the reduction exchange rows of AdjLds.
@@ -60,12 +81,10 @@ __device__ __forceinline__ void imp_k0(const AdjLds<T>& L, const Topo& tp, const
 #pragma unroll
     for (int c = 0; c < 3; ++c) L.r[c * NT + tp.t] = a[c];
     __syncthreads();
-    T zl[3], lin[5] = {T(0), T(0), T(0), T(0), T(0)}, kl[3], kr[3];
+    T zl[3], kl[3], kr[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) zl[c] = has_l ? L.r[c * NT + tl] : T(0);
-    elem_linear_coefs<T>(k.sc.elem.c, k.sc.elem.kind, lin);
-    elem_force_linear<T>(lin, zl, a, kl, kr);
-    if (k.sc.elem.kind == KIND_NONLINEAR && !k.corrected) kl[0] = lin[0] * zl[0];   // tangent of the shipped f1: no u2 term
+    imp_k0_elem<T>(k.sc.elem, k.corrected, zl, a, kl, kr);
 #pragma unroll
     for (int c = 0; c < 3; ++c) L.r[(3 + c) * NT + tp.t] = kl[c];
     __syncthreads();
@@ -141,10 +160,11 @@ __global__ void __launch_bounds__(ADJ_MAX_NT) crb_imp_adj_kernel(const KParams<T
     }
     const T h = T(p.dt), hh = T(0.5 * p.dt), alpha = T(0.25 * p.dt * p.dt), alpha2 = T(0.5 * p.dt * p.dt);
 
-    if (MODE == IADJ_CKPT || MODE == IADJ_SEG) {
+    constexpr bool SEG = MODE == IADJ_SEG || MODE == IADJ_SEG_FIN;
+    if (MODE == IADJ_CKPT || SEG) {
         T x[6] = {T(0), T(0), T(0), T(0), T(0), T(0)}, am[3] = {T(0), T(0), T(0)};
         if (valid) {
-            if (MODE == IADJ_SEG) {
+            if (SEG) {
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     x[c] = iq.start[coff + c] * sc.mask[c];
@@ -162,10 +182,19 @@ __global__ void __launch_bounds__(ADJ_MAX_NT) crb_imp_adj_kernel(const KParams<T
         int sched_left = SCHED ? p.sched_first : -1;
         const T* sched_u = p.u_held + uoff;
         for (int step = 0; step < p.n_steps; ++step) {
+            bool moved = false;   // (IADJ_SEG_FIN: the slot of this step's a^0 holds the previous step's final iterate)
             if constexpr (SCHED) {
                 if (sched_left == 0) {   // (wave-uniform)
                     sched_left = p.sched_hold;
                     sched_u += p.sched_stride;
+                    if (MODE == IADJ_SEG_FIN) {
+                        moved = true;
+                        if (valid) {
+                            T* const io = iq.iters_out + size_t(step) * size_t(iq.n_iter) * force_sz + uoff;
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) io[c] = am[c];
+                        }
+                    }
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
                         if (valid) uh[c] = sched_u[c];
@@ -174,7 +203,7 @@ __global__ void __launch_bounds__(ADJ_MAX_NT) crb_imp_adj_kernel(const KParams<T
                 }
                 --sched_left;
             }
-            if (MODE == IADJ_SEG) {   // the step's start state and clock
+            if (SEG) {   // the step's start state and clock
                 if (valid) {
                     T* const so = aq.states + size_t(step) * state_sz + xoff;
 #pragma unroll
@@ -202,7 +231,7 @@ __global__ void __launch_bounds__(ADJ_MAX_NT) crb_imp_adj_kernel(const KParams<T
             }
 #pragma unroll 1
             for (int it = 0; it < iq.n_iter; ++it) {
-                if (MODE == IADJ_SEG && valid) {
+                if (SEG && valid && !(moved && it == 0)) {
                     T* const io = iq.iters_out + (size_t(step) * size_t(iq.n_iter) + size_t(it)) * force_sz + uoff;
 #pragma unroll
                     for (int c = 0; c < 3; ++c) io[c] = am[c];
@@ -243,10 +272,16 @@ __global__ void __launch_bounds__(ADJ_MAX_NT) crb_imp_adj_kernel(const KParams<T
         if (MODE == IADJ_CKPT && aq.write_back && valid)
 #pragma unroll
             for (int c = 0; c < 3; ++c) { p.x[xoff + c] = x[c]; p.x[xoff + plane + c] = x[3 + c]; }
+        if (MODE == IADJ_SEG_FIN && valid) {
+            T* const fo = iq.fin_out + uoff;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) fo[c] = am[c];
+            fo[3] = T(0);
+        }
         return;
     }
 
-    // ---- IADJ_BWD
+    // ---- IADJ_BWD, IADJ_BWD_STORE
     T lam[6] = {T(0), T(0), T(0), T(0), T(0), T(0)}, fb[3] = {T(0), T(0), T(0)}, cb[3] = {T(0), T(0), T(0)};
     T ab = T(0);
     if (valid) {
@@ -270,6 +305,12 @@ __global__ void __launch_bounds__(ADJ_MAX_NT) crb_imp_adj_kernel(const KParams<T
         rec_p = p.rec_slot == REC_ALL_SLOTS ? p.rec_out + d * size_t(p.rec_n) * state_sz + xoff
                                             : p.rec_out + (d * size_t(p.B) + tp.beam) * size_t(p.rec_n);
     asm volatile("" : "+v"(lam_p), "+v"(fb_p), "+v"(ab_p), "+v"(rec_p), "+v"(cb_p), "+v"(it_p));
+    T* gb_p = nullptr;                                         // (IADJ_BWD_STORE: this lane's gbar record of iteration 0 of step 0)
+    const size_t gb_stride = size_t(gridDim.y) * force_sz;     //  and the stride from one iteration to the next
+    if (MODE == IADJ_BWD_STORE) {
+        gb_p = iq.gbar + luoff;
+        asm volatile("" : "+v"(gb_p));
+    }
 #pragma unroll 1
     for (int i = p.n_steps - 1; i >= 0; --i) {
         const int kstep = aq.step0 + i;
@@ -317,6 +358,13 @@ __global__ void __launch_bounds__(ADJ_MAX_NT) crb_imp_adj_kernel(const KParams<T
 #pragma unroll
                 for (int c = 0; c < 3; ++c) a[c] = ai[c] * sc.mask[c];
             }
+            if constexpr (SCHED && MODE == IADJ_BWD_STORE) {   // an interval's a^0 is 0, whatever its slot holds (iq.fin_out)
+                int hold = p.sched_hold;
+                asm volatile("" : "+s"(hold));
+                if (it == 0 && kstep % hold == 0)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) a[c] = T(0);
+            }
 #pragma unroll
             for (int c = 0; c < 3; ++c) { qm[c] = qp[c] + alpha * a[c]; vm[c] = x0[3 + c] + hh * a[c]; }
             const T zero3[3] = {T(0), T(0), T(0)};
@@ -324,6 +372,12 @@ __global__ void __launch_bounds__(ADJ_MAX_NT) crb_imp_adj_kernel(const KParams<T
             adj_vjp<T>(p, L, tp, kk, ixx, qm, vm, zero3, abar, qb, vb, gb);
 #pragma unroll
             for (int c = 0; c < 3; ++c) { qb[c] = qb[c] * sc.mask[c]; vb[c] = vb[c] * sc.mask[c]; gb[c] = gb[c] * sc.mask[c]; }
+            if (MODE == IADJ_BWD_STORE && valid) {
+                T* const go = gb_p + (size_t(i) * size_t(iq.n_iter) + size_t(it)) * gb_stride;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) go[c] = gb[c];
+                go[3] = T(0);
+            }
             imp_k0t<T>(L, tp, kk, gb, kt);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {

@@ -42,26 +42,15 @@ __device__ __forceinline__ ElemCoef<T> stiffness_part(const ElemCoef<T>& e, bool
     return o;
 }
 
-// One stage point of the sums above: the state record `w` (positions at w[c], velocities a `plane` further) and the masked
-// rbar record `r` of this thread's node, both null-safe only through `valid`; the left neighbour's records lie one node
-// (4 values) before.  Adds into acc = (sA, sI, sD, gx, gy) in the order the rollout kernel has always used.  Whole workgroup
-// when grav_on (two barriers); drag_on false leaves sD alone (a static equilibrium has v = 0).
+// The sums above at one point, from values in registers: this node's and its left neighbour's position (q, ql; masked), this
+// node's transverse velocity vw and the masked cotangents (rb, rl) of the two nodes.  Adds into acc = (sA, sI, sD, gx, gy) in
+// the order the rollout kernel has always used.  Whole workgroup when grav_on (two barriers); drag_on false leaves sD alone.
 template <typename T>
-__device__ __forceinline__ void param_stage_point(const AdjLds<T>& L, const Topo& tp, const SlotConst<T>& sc, const T (&ml)[3],
-                                                  const ElemCoef<T>& eA, const ElemCoef<T>& eI, const AdjIdx<T>& ix, bool valid,
-                                                  bool has_l, const T* w, const T* r, size_t plane, bool drag_on, bool grav_on,
-                                                  bool corrected, T (&acc)[5]) {
+__device__ __forceinline__ void param_point_sums(const AdjLds<T>& L, const Topo& tp, const SlotConst<T>& sc, const ElemCoef<T>& eA,
+                                                 const ElemCoef<T>& eI, const AdjIdx<T>& ix, const T (&q)[3], const T (&ql)[3], T vw,
+                                                 const T (&rb)[3], const T (&rl)[3], bool drag_on, bool grav_on, bool corrected,
+                                                 T (&acc)[5]) {
     const int NT = L.NT;
-    T q[3] = {T(0), T(0), T(0)}, ql[3] = {T(0), T(0), T(0)}, rb[3] = {T(0), T(0), T(0)}, rl[3] = {T(0), T(0), T(0)};
-    T vw = T(0);
-    if (valid) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { q[c] = w[c] * sc.mask[c]; rb[c] = r[c]; }
-        if (drag_on) vw = w[plane + 1] * sc.mask[1];
-        if (has_l)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { ql[c] = w[c - 4] * ml[c]; rl[c] = r[c - 4]; }
-    }
     T fl[3], fr[3];
     elem_force<T>(eA, ql, q, corrected, fl, fr);
     acc[0] = acc[0] - (rl[0] * fl[0] + rl[1] * fl[1] + rl[2] * fl[2] + rb[0] * fr[0] + rb[1] * fr[1] + rb[2] * fr[2]);
@@ -82,6 +71,27 @@ __device__ __forceinline__ void param_stage_point(const AdjLds<T>& L, const Topo
         acc[3] = acc[3] + sc.half_mass * (cs * gb[0] - sn * gb[1]);
         acc[4] = acc[4] + sc.half_mass * (sn * gb[0] + cs * gb[1]);
     }
+}
+
+// One stage point of the sums above: the state record `w` (positions at w[c], velocities a `plane` further) and the masked
+// rbar record `r` of this thread's node, both null-safe only through `valid`; the left neighbour's records lie one node
+// (4 values) before.  Loads them and adds param_point_sums.
+template <typename T>
+__device__ __forceinline__ void param_stage_point(const AdjLds<T>& L, const Topo& tp, const SlotConst<T>& sc, const T (&ml)[3],
+                                                  const ElemCoef<T>& eA, const ElemCoef<T>& eI, const AdjIdx<T>& ix, bool valid,
+                                                  bool has_l, const T* w, const T* r, size_t plane, bool drag_on, bool grav_on,
+                                                  bool corrected, T (&acc)[5]) {
+    T q[3] = {T(0), T(0), T(0)}, ql[3] = {T(0), T(0), T(0)}, rb[3] = {T(0), T(0), T(0)}, rl[3] = {T(0), T(0), T(0)};
+    T vw = T(0);
+    if (valid) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { q[c] = w[c] * sc.mask[c]; rb[c] = r[c]; }
+        if (drag_on) vw = w[plane + 1] * sc.mask[1];
+        if (has_l)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { ql[c] = w[c - 4] * ml[c]; rl[c] = r[c - 4]; }
+    }
+    param_point_sums<T>(L, tp, sc, eA, eI, ix, q, ql, vw, rb, rl, drag_on, grav_on, corrected, acc);
 }
 
 // crb_static_vjp's parameter records: one "stage point", the equilibrium itself.  aq.work = the state whose plane 0 holds q,

@@ -3071,13 +3071,19 @@ int imp_adjoint_params(const crb_plan* p, double h, hipStream_t st, KParams<doub
 }
 // The work buffer of the implicit adjoint, in doubles: a segment's step start states [every], iterates [every][n_iter] force
 // records and clocks [every], and the cotangent carried through the starting iterate from one segment to the one before it,
-// [n_cot] force records.
-struct ImpAdjWork { double *states, *iters, *clock, *carry; };
-ImpAdjWork imp_adj_work(const crb_plan* p, void* work, int every, int n_iter) {
+// [n_cot] force records.  With parameter gradients (crb_implicit_adjoint_params_work_bytes) the sweep's per-iteration gbar,
+// [every][n_iter][n_cot] force records, and the final iterate of the segment's last step, one force record.
+struct ImpAdjWork { double *states, *iters, *clock, *carry, *gbar, *fin; };
+ImpAdjWork imp_adj_work(const crb_plan* p, void* work, int every, int n_iter, int n_cot) {
     double* const states = static_cast<double*>(work), * const iters = states + size_t(every) * state_doubles(p);
     double* const clock = iters + size_t(every) * size_t(n_iter) * force_doubles(p);
-    return {states, iters, clock, clock + size_t(every)};
+    double* const carry = clock + size_t(every), * const gbar = carry + size_t(n_cot) * force_doubles(p);
+    return {states, iters, clock, carry, gbar, gbar + size_t(every) * size_t(n_iter) * size_t(n_cot) * force_doubles(p)};
 }
+int imp_adjoint_rollout(const std::string& who, const crb_plan* p, const void* ckpt, void* lam, int n_cot, double t0, double h,
+                        int n_steps, int n_iter, int every, const crb_input_desc* in, const crb_record_desc* rec_bar,
+                        const crb_input_cotangent* grad, bool want_params, const crb_param_cotangent* pgrad,
+                        const crb_input_schedule* sched, void* sched_bar, void* work, void* stream);
 }  // namespace
 
 extern "C" size_t crb_implicit_adjoint_work_bytes(const crb_plan* p, int every, int n_iter, int n_cot) {
@@ -3135,10 +3141,47 @@ extern "C" int crb_step_implicit_adjoint_sched(const crb_plan* p, const void* ck
                                                int n_steps, int n_iter, int every, const crb_input_desc* in,
                                                const crb_record_desc* rec_bar, const crb_input_cotangent* grad,
                                                const crb_input_schedule* sched, void* sched_bar, void* work, void* stream) {
-    const std::string who(sched ? "crb_step_implicit_adjoint_sched" : "crb_step_implicit_adjoint");
+    return imp_adjoint_rollout(sched ? "crb_step_implicit_adjoint_sched" : "crb_step_implicit_adjoint", p, ckpt, lam, n_cot, t0, h,
+                               n_steps, n_iter, every, in, rec_bar, grad, false, nullptr, sched, sched_bar, work, stream);
+}
+
+extern "C" size_t crb_implicit_adjoint_params_work_bytes(const crb_plan* p, int every, int n_iter, int n_cot) {
+    const size_t plain = crb_implicit_adjoint_work_bytes(p, every, n_iter, n_cot);
+    if (!plain) return 0;
+    return plain + (size_t(every) * size_t(n_iter) * size_t(n_cot) + 1) * force_doubles(p) * sizeof(double);
+}
+
+extern "C" int crb_step_implicit_adjoint_params(const crb_plan* p, const void* ckpt, void* lam, int n_cot, double t0, double h,
+                                                int n_steps, int n_iter, int every, const crb_input_desc* in,
+                                                const crb_record_desc* rec_bar, const crb_input_cotangent* grad,
+                                                const crb_param_cotangent* pgrad, void* work, void* stream) {
+    return imp_adjoint_rollout("crb_step_implicit_adjoint_params", p, ckpt, lam, n_cot, t0, h, n_steps, n_iter, every, in, rec_bar,
+                               grad, true, pgrad, nullptr, nullptr, work, stream);
+}
+
+extern "C" int crb_step_implicit_adjoint_params_sched(const crb_plan* p, const void* ckpt, void* lam, int n_cot, double t0, double h,
+                                                      int n_steps, int n_iter, int every, const crb_input_desc* in,
+                                                      const crb_record_desc* rec_bar, const crb_input_cotangent* grad,
+                                                      const crb_param_cotangent* pgrad, const crb_input_schedule* sched,
+                                                      void* sched_bar, void* work, void* stream) {
+    return imp_adjoint_rollout(sched ? "crb_step_implicit_adjoint_params_sched" : "crb_step_implicit_adjoint_params", p, ckpt, lam,
+                               n_cot, t0, h, n_steps, n_iter, every, in, rec_bar, grad, true, pgrad, sched, sched_bar, work, stream);
+}
+
+namespace {
+// crb_step_implicit_adjoint(_sched) and crb_step_implicit_adjoint_params(_sched) (want_params): the same segments and launches,
+// the latter with the recompute that keeps the last final iterate, the storing sweep and crb_imp_param_grad_kernel after each
+int imp_adjoint_rollout(const std::string& who, const crb_plan* p, const void* ckpt, void* lam, int n_cot, double t0, double h,
+                        int n_steps, int n_iter, int every, const crb_input_desc* in, const crb_record_desc* rec_bar,
+                        const crb_input_cotangent* grad, bool want_params, const crb_param_cotangent* pgrad,
+                        const crb_input_schedule* sched, void* sched_bar, void* work, void* stream) {
     if (!p) return fail(CRB_EINVAL, who + ": null plan");
     if (!ckpt || !lam) return fail(CRB_EINVAL, who + ": null checkpoint buffer or cotangent");
-    if (!work) return fail(CRB_EINVAL, who + ": null work buffer (crb_implicit_adjoint_work_bytes)");
+    if (want_params && (!pgrad || !pgrad->param_bar))
+        return fail(CRB_EINVAL, who + ": null parameter cotangent (crb_param_cotangent.param_bar)");
+    if (!work) return fail(CRB_EINVAL, who + (want_params ? ": null work buffer (crb_implicit_adjoint_params_work_bytes)"
+                                                             : ": null work buffer (crb_implicit_adjoint_work_bytes)"));
+    void* const param_bar = want_params ? pgrad->param_bar : nullptr;
     void* const amp_bar = grad ? grad->amp_bar : nullptr;
     void* f_bar = grad ? grad->f_held_bar : nullptr;
     const void* const rec_out = rec_bar ? rec_bar->out : nullptr;
@@ -3146,8 +3189,11 @@ extern "C" int crb_step_implicit_adjoint_sched(const crb_plan* p, const void* ck
     const void* bufs[6] = {ckpt, work, amp_bar, f_bar, rec_out, held};
     for (const void* b : bufs)
         if (b && b == lam) return fail(CRB_EINVAL, who + ": lam must not alias another buffer of the call");
+    if (param_bar && (param_bar == lam || param_bar == work || param_bar == ckpt))
+        return fail(CRB_EINVAL, who + ": param_bar must not alias lam, the work buffer or the checkpoints");
     if (work == ckpt || (amp_bar && (amp_bar == work || amp_bar == ckpt || amp_bar == f_bar)) ||
-        (f_bar && (f_bar == work || f_bar == ckpt)))
+        (f_bar && (f_bar == work || f_bar == ckpt)) ||
+        (param_bar && (param_bar == amp_bar || param_bar == f_bar || param_bar == rec_out || param_bar == held)))
         return fail(CRB_EINVAL, who + ": the output and work buffers must not alias each other or the checkpoints");
     if (int rc = imp_adjoint_arg_checks(who, n_cot, n_steps, every, n_iter, h)) return rc;
     Recording r;
@@ -3163,6 +3209,8 @@ extern "C" int crb_step_implicit_adjoint_sched(const crb_plan* p, const void* ck
     if (sched_bar && !sc.f) return fail(CRB_EINVAL, who + ": sched_bar needs a schedule (sched is null)");
     if (sched_bar && (sched_bar == lam || sched_bar == work || sched_bar == ckpt || sched_bar == sc.f || sched_bar == amp_bar))
         return fail(CRB_EINVAL, who + ": sched_bar must not alias lam, the work buffer, the checkpoints, f_sched or amp_bar");
+    if (param_bar && (param_bar == sched_bar || param_bar == sc.f))
+        return fail(CRB_EINVAL, who + ": param_bar must not alias the schedule or its cotangent");
     if (sc.f) f_bar = sched_bar;   // (one accumulator in the sweep: the interval's record)
     if (int rc = imp_adjoint_plan_checks(p, who)) return rc;
     if (int rc = need_device(p, who.c_str())) return rc;
@@ -3172,9 +3220,10 @@ extern "C" int crb_step_implicit_adjoint_sched(const crb_plan* p, const void* ck
     KParams<double> base;
     if (int rc = imp_adjoint_params(p, h, st, &base)) return rc;
     set_io(base, f);
-    const ImpAdjWork w = imp_adj_work(p, work, every, n_iter);
+    const ImpAdjWork w = imp_adj_work(p, work, every, n_iter, n_cot);
     ImpAdjParams<double> iter = zeroed<ImpAdjParams<double>>();
     iter.n_iter = n_iter;
+    const int groups = beam_groups(p);
     return for_segments_reversed(n_steps, every, t0, h, [&](int g, int k0, int n, double tg) -> int {
         KParams<double> k = base;
         k.t0 = tg;
@@ -3187,18 +3236,33 @@ extern "C" int crb_step_implicit_adjoint_sched(const crb_plan* p, const void* ck
         ImpAdjParams<double> iq = iter;
         iq.start = static_cast<const double*>(ckpt) + size_t(g) * 3 * force_doubles(p);
         iq.iters_out = w.iters;
-        HIP_TRY(crb::launch_imp_adj_segment(k, q, iq, beam_groups(p), p->NT, st));
+        if (want_params) {
+            iq.fin_out = w.fin;
+            HIP_TRY(crb::launch_imp_adj_segment_final(k, q, iq, groups, p->NT, st));
+        } else {
+            HIP_TRY(crb::launch_imp_adj_segment(k, q, iq, groups, p->NT, st));
+        }
         // 2. the sweep back over it, every cotangent
         set_record(k, r);
         ImpAdjParams<double> ib = iter;
         ib.iters = w.iters;
         ib.carry = w.carry;
         ib.carry_in = k0 + n < n_steps ? 1 : 0;   // (every segment but the one that ends the rollout)
-        HIP_TRY(crb::launch_imp_adj_backward(k, sweep_params(p, w.states, w.clock, lam, amp_bar, f_bar, sc, k0, n), ib, beam_groups(p),
-                                             n_cot, p->NT, st));
+        AdjParams<double> b = sweep_params(p, w.states, w.clock, lam, amp_bar, f_bar, sc, k0, n);
+        if (!want_params) {
+            HIP_TRY(crb::launch_imp_adj_backward(k, b, ib, groups, n_cot, p->NT, st));
+            return CRB_OK;
+        }
+        ib.gbar = w.gbar;
+        ib.fin_out = w.fin;
+        b.param_bar = static_cast<double*>(param_bar);
+        HIP_TRY(crb::launch_imp_adj_backward_store(k, b, ib, groups, n_cot, p->NT, st));
+        // 3. the parameter sums of the segment, from its step data and the sweep's gbar
+        HIP_TRY(crb::launch_imp_param_grad(k, b, ib, groups, n_cot, p->NT, st));
         return CRB_OK;
     });
 }
+}  // namespace
 
 // ---- tangent of the implicit stepper (crb_implicit_tangent.h)
 extern "C" int crb_step_implicit_tangent(const crb_plan* p, void* x, void* dx, int n_dir, double t0, double h, int n_steps, int n_iter,
@@ -3559,7 +3623,7 @@ struct ImpFbAdjWork {
 };
 ImpFbAdjWork imp_fb_adj_work(const crb_plan* p, void* work, int every, int n_iter, int hold, int n_cot) {
     ImpFbAdjWork w;
-    w.imp = imp_adj_work(p, work, every, n_iter);
+    w.imp = imp_adj_work(p, work, every, n_iter, n_cot);
     w.ubar = w.imp.carry + size_t(n_cot) * force_doubles(p);
     w.partial = w.ubar + size_t(n_cot) * size_t(every / hold) * force_doubles(p);
     return w;

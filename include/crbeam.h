@@ -653,9 +653,8 @@ int crb_step_rk4_adjoint_params_sched(const crb_plan* plan, const void* ckpt, vo
  * plan or buffer, aliasing buffers, n_cot outside 1 ... 65535, n_steps < 0, every < 1, n_iter outside 1 ... 16, h <= 0, a bad
  * input or record description, amp_bar without an impulse input; CRB_EUNSUPPORTED for fp32 plans and beams of more than 256
  * thread-carried nodes; CRB_ENODEV for host-only plans.  *t_end is written only by a call that is not refused.
- * Not covered: the damped variant (rho_inf < 1), the closed loop, and parameter gradients (E and I enter A and K0, so with a
- * fixed iteration count the dependence is not the linear sum crb_step_rk4_adjoint_params computes).  Control schedules: the
- * *_sched calls below. */
+ * Not covered: the damped variant (rho_inf < 1) and the closed loop.  Parameter gradients: crb_step_implicit_adjoint_params
+ * below.  Control schedules: the *_sched calls below. */
 size_t crb_implicit_adjoint_work_bytes(const crb_plan* plan, int every, int n_iter, int n_cot);
 int crb_step_implicit_checkpoint(const crb_plan* plan, void* x, double t0, double h, int n_steps, int n_iter, int every,
                                  const crb_input_desc* input, const crb_record_desc* rec, void* ckpt, double* t_end, void* stream);
@@ -696,6 +695,44 @@ int crb_step_implicit_adjoint_sched(const crb_plan* plan, const void* ckpt, void
                                     int n_steps, int n_iter, int every, const crb_input_desc* input,
                                     const crb_record_desc* rec_bar, const crb_input_cotangent* grad,
                                     const crb_input_schedule* sched, void* sched_bar, void* work, void* stream);
+
+/* ---- Parameter gradients of the implicit adjoint: stiffness, drag and gravity, the iteration matrix included
+ * (csrc/crb_implicit_paramgrad.h).  crb_step_implicit_adjoint(_sched) with one more output, the crb_param_cotangent of
+ * crb_step_rk4_adjoint_params: the same struct, the same record [n_cot][B][n_node][8] = (sA, sI, sD, gx, gy, 0, 0, 0) per node
+ * (sA, sI of node j: the element left of it), param_bar ACCUMULATED.  lam, grad and sched_bar come out bitwise as from the
+ * plain call.
+ * E and I enter the iteration matrix A = M + alpha K0(theta), alpha = h^2 / 4, as well as the force.  With iteration i of a step
+ *     q_m = qp + alpha a^i,  v_m = v0 + h/2 a^i,  a^{i+1} = A^-1 (F(q_m, v_m; theta) + u + alpha K0(theta) a^i)
+ * and gbar = A^-T abar of that iteration (what the sweep forms), dA^-1 = -A^-1 (alpha dK0) A^-1 gives its contribution
+ *     theta_bar += gbar^T dF/dtheta (q_m, v_m)  +  alpha gbar^T (dK0/dtheta) (a^i - a^{i+1})
+ * The first term is crb_step_rk4_adjoint_params' sum with gbar in the place of rbar; the second exists for sA and sI only (drag
+ * and gravity are not in K0): dK0/dsA is the element's linear stiffness with the EI entries zeroed, dK0/dsI with the EA entries
+ * zeroed, the axial block [[c0, -s c0], [-c0, c0]] with s = 0 for the shipped nonlinear element.  It vanishes as the iteration
+ * converges and is what a fixed iteration count leaves; a^0 = 0 at the first step of a call and of every schedule interval.
+ * Per segment, last to first: the recompute (which also keeps the final iterate of the segment's last step), the storing sweep
+ * (gbar of every iteration to the work buffer) and one reduction launch; fixed summation order, no atomics: param_bar is
+ * bitwise independent of `every`, and D cotangents in one call are bitwise D calls of one.
+ *
+ * crb_implicit_adjoint_params_work_bytes:
+ *     crb_implicit_adjoint_work_bytes(plan, every, n_iter, n_cot) + (every * n_iter * n_cot + 1) * B * n_node * 4 * sizeof(double)
+ * -- after the plain buffer gbar [every][n_iter][n_cot][B][n_node][4], then the final iterate [B][n_node][4].  0 where the
+ * plain call returns 0.
+ *
+ * Refusals, all before the device is touched, in this order: CRB_EINVAL for a NULL plan, ckpt or lam, a NULL pgrad or
+ * pgrad->param_bar, a NULL work buffer (each named in crb_last_error()), lam aliasing another buffer, param_bar aliasing lam,
+ * work or ckpt, other aliasing buffers, n_cot, n_steps, every, n_iter or h out of range; then every further check of
+ * crb_step_implicit_adjoint(_sched) in its order, param_bar aliasing the schedule or sched_bar with the schedule's cases;
+ * CRB_EUNSUPPORTED for fp32 plans and beams of more than 256 thread-carried nodes; CRB_ENODEV for host-only plans.
+ * Not covered: length, cross-section area and density (they enter M), the damped variant, the sampled-data loop. */
+size_t crb_implicit_adjoint_params_work_bytes(const crb_plan* plan, int every, int n_iter, int n_cot);
+int crb_step_implicit_adjoint_params(const crb_plan* plan, const void* ckpt, void* lam, int n_cot, double t0, double h, int n_steps,
+                                     int n_iter, int every, const crb_input_desc* input, const crb_record_desc* rec_bar,
+                                     const crb_input_cotangent* grad, const crb_param_cotangent* pgrad, void* work, void* stream);
+int crb_step_implicit_adjoint_params_sched(const crb_plan* plan, const void* ckpt, void* lam, int n_cot, double t0, double h,
+                                           int n_steps, int n_iter, int every, const crb_input_desc* input,
+                                           const crb_record_desc* rec_bar, const crb_input_cotangent* grad,
+                                           const crb_param_cotangent* pgrad, const crb_input_schedule* sched, void* sched_bar,
+                                           void* work, void* stream);
 
 /* ---- Tangent of the implicit stepper: forward-mode derivatives of stiff rollouts (csrc/crb_implicit_tangent.h).
  * crb_step_implicit with the tangent of its discrete map alongside: the exact derivative of what crb_step_implicit computes

@@ -147,6 +147,8 @@ def load():
     L.crb_plan_get_slot_tables.argtypes = [vp, _dp, _dp, _dp, C.POINTER(C.c_int16), C.POINTER(C.c_int32)]
     L.crb_plan_get_mass.argtypes = [vp, _dp]
     L.crb_blocked_solve_host.argtypes = [_dp, C.c_double, _dp, _dp, C.POINTER(C.c_int32), _dp]
+    L.crb_plan_get_blocked_form.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.crb_blocked_twist_solve_host.argtypes = [_dp, C.c_double, _dp, _dp, C.POINTER(C.c_int32), _dp]
     L.crb_plan_get_stiffness.argtypes = [vp, _dp]
     for name in ("crb_pack_state", "crb_unpack_state", "crb_pack_vec", "crb_unpack_vec", "crb_internal_force"):
         getattr(L, name).argtypes = [vp, vp, vp, vp]
@@ -424,6 +426,12 @@ class Plan:
         M = np.empty((self.n_free0, self.n_free0))
         check(load().crb_plan_get_mass(self.h, M.ctypes.data_as(_dp)))
         return M
+
+    def blocked_form(self):
+        """(form, separator levels) of the register-blocked stepper's tables: 0 none, 1 block Thomas, 2 twisted interior"""
+        form, lv = C.c_int32(0), C.c_int32(0)
+        check(load().crb_plan_get_blocked_form(self.h, C.byref(form), C.byref(lv)))
+        return form.value, lv.value
 
     def stiffness(self):
         K = np.empty((self.n_free0, self.n_free0))

@@ -10,12 +10,24 @@
 // the fixed root's x_s = 0, lane 63's C_s the 0 shifted in past the wave's end), so they are ONE table of wave-uniform
 // constants; only the separator system's multipliers differ near the beam's ends and are stored per lane.
 // blocked_factor builds both in fp64 and refuses a beam whose interior constants are not bitwise uniform.
+// CRB_BLK_TWIST: step 1 twisted about the lane's centre node.  The blocked stepper only takes beams of equal elements, and
+// their consistent mass matrix is mirror symmetric: every interior diagonal block B is diagonal (the +-22L terms of the two
+// adjoining elements cancel) and C = J A J with J = diag(1, -1) on (w, phi).  Then the centre pivot
+// Dc = B1 - A1 B0^-1 C0 - C1 B2^-1 A2 is diagonal too (the off-diagonal parts of its two products are mirror images), and
+//   t0 = B^-1 r0, t2 = B^-1 r2;  z1 = r1 - (A1 B^-1) r0 - (C1 B^-1) r2;  y1 = Dc^-1 z1;  y0 = t0 - (B^-1 C0) y1;  y2 = t2 - (B^-1 A2) y1
+// is 29 multiplies and multiply-adds of depth three against block Thomas's 35 of depth five (blk_twist_interior_solve).
+// blocked_mirrored checks the structure bitwise; blocked_factor builds this form's constants for node blocks that have it, and a
+// plan whose blocks lack it runs the block-Thomas instance.
 #pragma once
 #include <cmath>
 #include <cstring>
 #include <vector>
 
 #include "crb_math.h"
+
+#ifndef CRB_BLK_TWIST
+#define CRB_BLK_TWIST 1
+#endif
 
 namespace crb {
 
@@ -40,11 +52,22 @@ __host__ __device__ constexpr int blk_fold_offset(int levels) { return BU_N + bl
 // ... and behind them the constants of the form that shares the membrane combinations (elem_share_build, SK_N values)
 __host__ __device__ constexpr int blk_share_offset(int levels) { return blk_fold_offset(levels) + FK_N; }
 
+// The twisted form's wave-uniform table (CRB_BLK_TWIST), behind the constants of the shared form whatever the element kind:
+// P = A1 B^-1, Q = C1 B^-1 (into z1), U = B^-1 C0, V = B^-1 A2 (back into y0, y2), the diagonals of B^-1 and Dc^-1
+// [axial, w, phi], then W_L, W_R, A_s, C_s as in the table above.  It is stored as the kernel's registers read it: entry k
+// at [k], BT_TAB = BLK_TAB_REGS * BLK_TAB_ROW values, zero behind BT_N.
+enum : int {
+    BT_P = 0, BT_Q = 5, BT_U = 10, BT_V = 15, BT_BI = 20, BT_DI = 23, BT_WL = 26, BT_WR = 41, BT_AS = 56, BT_CS = 61, BT_N = 66,
+    BT_TAB = 80
+};
+__host__ __device__ constexpr int blk_twist_offset(int levels) { return blk_share_offset(levels) + SK_N; }
+
 // The wave-uniform table as the kernel holds it: BLK_TAB_REGS fp64 registers per lane, constant k in lane k % BLK_TAB_ROW of
 // EVERY 16-lane row of register k / BLK_TAB_ROW (a DPP row broadcast reads inside the reader's own row, so each of the four
 // rows of a wave carries the whole table); the slots past the table repeat its zero pad.
 constexpr int BLK_TAB_ROW = 16;
 constexpr int BLK_TAB_REGS = (BU_N + BLK_TAB_ROW - 1) / BLK_TAB_ROW;   // 5
+static_assert(BT_N <= BU_N && BT_TAB == BLK_TAB_REGS * BLK_TAB_ROW, "the twisted table fills the same registers");
 __host__ __device__ constexpr int blk_tab_index(int reg, int lane) {   // the table entry that `lane` holds in register `reg`
     return BLK_TAB_ROW * reg + (lane & (BLK_TAB_ROW - 1)) < BU_N - 1 ? BLK_TAB_ROW * reg + (lane & (BLK_TAB_ROW - 1)) : BU_N - 1;
 }
@@ -98,6 +121,15 @@ __device__ __forceinline__ void blk_bc_sub_mul(const T (&tab)[BLK_TAB_REGS], con
     blk_bc_fnma<OFF + 3>(tab, v[1], o[2]);
     blk_bc_fnma<OFF + 4>(tab, v[2], o[2]);
 }
+// o += u[OFF .. OFF+4] v
+template <int OFF, typename T>
+__device__ __forceinline__ void blk_bc_add_mul(const T (&tab)[BLK_TAB_REGS], const T v[3], T o[3]) {
+    blk_bc_fma<OFF + 0>(tab, v[0], o[0]);
+    blk_bc_fma<OFF + 1>(tab, v[1], o[1]);
+    blk_bc_fma<OFF + 2>(tab, v[2], o[1]);
+    blk_bc_fma<OFF + 3>(tab, v[1], o[2]);
+    blk_bc_fma<OFF + 4>(tab, v[2], o[2]);
+}
 #endif
 
 // ---- apply a 5-pack to a 3-vector [u, w, phi]
@@ -126,6 +158,20 @@ __host__ __device__ __forceinline__ void blk_interior_solve(P u, const T r[][3],
     blk_sub_mul<T, P>(u + BU_U1, y[2], y[1]);
     blk_mul<T, P>(u + BU_D0, r[0], y[0]);
     blk_sub_mul<T, P>(u + BU_U0, y[1], y[0]);
+}
+// the same about the lane's centre node (w: the twisted table; needs the mirror structure, blocked_factor)
+template <typename T, typename P = const T*>
+__host__ __device__ __forceinline__ void blk_twist_interior_solve(P w, const T r[][3], T y[3][3]) {
+    T z1[3] = {r[1][0], r[1][1], r[1][2]};
+    blk_sub_mul<T, P>(w + BT_P, r[0], z1);
+    blk_sub_mul<T, P>(w + BT_Q, r[2], z1);
+    for (int c = 0; c < 3; ++c) {
+        y[0][c] = w[BT_BI + c] * r[0][c];
+        y[2][c] = w[BT_BI + c] * r[2][c];
+        y[1][c] = w[BT_DI + c] * z1[c];
+    }
+    blk_sub_mul<T, P>(w + BT_U, y[1], y[0]);
+    blk_sub_mul<T, P>(w + BT_V, y[1], y[2]);
 }
 
 // ---- host-side factorisation (plan time, fp64)
@@ -188,11 +234,53 @@ inline void blocked_lane_constants(const NodeBlocks* blk, int l, double* u) {
     b2_store(b2_right(n[3]), u + BU_CS);
 }
 
+// The mirror structure of lane `l`'s interior, bitwise: every B diagonal, every C = J A J, and the blocks that the twisted
+// form takes as one (B0 = B2, A1 = A2, C0 = C1) equal.
+inline bool blocked_lane_mirrored(const NodeBlocks* blk, int l) {
+    const NodeBlocks* n = blk + BLK_NPL * l;
+    for (int k = 0; k < 3; ++k) {
+        const double jaj[4] = {n[k].A[0], -n[k].A[1], -n[k].A[2], n[k].A[3]};
+        if (n[k].B[1] != 0.0 || n[k].B[2] != 0.0) return false;
+        if (l == 0 && k == 0) continue;   // (the node at the fixed root has no left coupling; the form takes none of it)
+        if (n[k].c_ax != n[k].a_ax) return false;
+        for (int i = 0; i < 4; ++i)
+            if (n[k].C[i] != jaj[i]) return false;
+    }
+    return n[0].b_ax == n[2].b_ax && n[0].B[0] == n[2].B[0] && n[0].B[3] == n[2].B[3] && n[1].a_ax == n[2].a_ax &&
+           std::memcmp(n[1].A, n[2].A, sizeof(n[1].A)) == 0 && std::memcmp(n[0].C, n[1].C, sizeof(n[0].C)) == 0;
+}
+inline bool blocked_mirrored(const NodeBlocks* blk) {   // every lane of the 256 node rows
+    for (int l = 0; l < BLK_LANES; ++l)
+        if (!blocked_lane_mirrored(blk, l)) return false;
+    return true;
+}
+// The twisted table of lane `l` (mirrored, above) into w[BT_TAB]; u: the lane's constants of blocked_lane_constants, whose
+// W_L, W_R, A_s, C_s it carries over.
+inline void blocked_twist_constants(const NodeBlocks* blk, int l, const double* u, double* w) {
+    const NodeBlocks* n = blk + BLK_NPL * l;
+    Blk2 Bi;   // B^-1, a diagonal's reciprocals
+    Bi.ax = 1.0 / n[0].b_ax; Bi.m[0] = 1.0 / n[0].B[0]; Bi.m[3] = 1.0 / n[0].B[3];
+    const Blk2 C0 = b2_right(n[0]), A1 = b2_left(n[1]), B1 = b2_diag(n[1]), C1 = b2_right(n[1]), A2 = b2_left(n[2]);
+    const Blk2 Pm = b2_mul(A1, Bi), Qm = b2_mul(C1, Bi);
+    // the off-diagonals of the two products are mirror images: they cancel, exactly so in Dc
+    const Blk2 Dc = b2_sub(b2_sub(B1, b2_mul(Pm, C0)), b2_mul(Qm, A2));
+    std::memset(w, 0, sizeof(double) * BT_TAB);
+    b2_store(Pm, w + BT_P); b2_store(Qm, w + BT_Q);
+    b2_store(b2_mul(Bi, C0), w + BT_U); b2_store(b2_mul(Bi, A2), w + BT_V);
+    w[BT_BI] = Bi.ax; w[BT_BI + 1] = Bi.m[0]; w[BT_BI + 2] = Bi.m[3];
+    w[BT_DI] = 1.0 / Dc.ax; w[BT_DI + 1] = 1.0 / Dc.m[0]; w[BT_DI + 2] = 1.0 / Dc.m[3];
+    std::memcpy(w + BT_WL, u + BU_WL, sizeof(double) * 15);
+    std::memcpy(w + BT_WR, u + BU_WR, sizeof(double) * 15);
+    std::memcpy(w + BT_AS, u + BU_AS, sizeof(double) * BLK_PACK);
+    std::memcpy(w + BT_CS, u + BU_CS, sizeof(double) * BLK_PACK);
+}
+
 // Builds the blocked solve's tables from the 256 node rows of M (Lc: the length that scales rotations in the level norms,
 // as pick_levels uses).  u[BU_N]: the wave-uniform constants; sep[blk_sep_vals(BLK_MAX_LV)][64]: the separator tables of the
 // returned level count (levels past it are left 0); norms[BLK_MAX_LV]: each level's largest multiplier.  Returns the
 // separator levels the solve needs in fp64, or -1 when the interior constants are not bitwise uniform over the lanes.
-inline int blocked_factor(const NodeBlocks* blk, double Lc, double* u, double* sep, double* norms) {
+// tw (optional): the twisted table [BT_TAB], for node blocks that are mirrored (blocked_mirrored).
+inline int blocked_factor(const NodeBlocks* blk, double Lc, double* u, double* sep, double* norms, double* tw = nullptr) {
     blocked_lane_constants(blk, 1, u);
     double v[BU_N];
     for (int l = 0; l < BLK_LANES; ++l) {
@@ -203,6 +291,14 @@ inline int blocked_factor(const NodeBlocks* blk, double Lc, double* u, double* s
             const bool skip = (l == 0 && k >= BU_WL && k < BU_WL + 15) || (l == BLK_LANES - 1 && k >= BU_CS && k < BU_CS + 5);
             if (!skip && std::memcmp(&v[k], &u[k], sizeof(double)) != 0) return -1;
             if (l == BLK_LANES - 1 && k >= BU_CS && k < BU_CS + 5 && v[k] != 0.0) return -1;
+        }
+    }
+    if (tw) {
+        blocked_twist_constants(blk, 1, u, tw);
+        double x[BT_TAB];
+        for (int l = 0; l < BLK_LANES; ++l) {   // (the interior blocks themselves, as the constants above)
+            blocked_twist_constants(blk, l, u, x);
+            if (std::memcmp(x, tw, sizeof(double) * BT_WL) != 0) return -1;
         }
     }
     // the separator Schur system, one row per lane:  -A_s W_L2 x_s(l-1) + (B_s - A_s W_R2 - C_s W_L0) x_s(l) - C_s W_R0 x_s(l+1)
@@ -258,13 +354,15 @@ inline int blocked_factor(const NodeBlocks* blk, double Lc, double* u, double* s
 
 // Host restatement of the kernel's solve (fp64, lanes run one after another; a lane shift past the wave's end reads 0, as
 // the DPP moves with bound_ctrl do): x = M^-1 r for r, x of [256][3].  The test suite checks it against a dense solve.
-inline void blocked_solve_host(const double* u, const double* sep, int levels, const double* r, double* x) {
+// tw: the twisted table, for the interiors solved about their centre nodes (CRB_BLK_TWIST) instead of by block Thomas.
+inline void blocked_solve_host(const double* u, const double* sep, int levels, const double* r, double* x, const double* tw = nullptr) {
     double y[BLK_LANES][3][3], g[BLK_LANES][3];
     for (int l = 0; l < BLK_LANES; ++l) {
         double ri[3][3];
         for (int k = 0; k < 3; ++k)
             for (int c = 0; c < 3; ++c) ri[k][c] = r[(BLK_NPL * l + k) * 3 + c];
-        blk_interior_solve<double>(u, ri, y[l]);
+        if (tw) blk_twist_interior_solve<double>(tw, ri, y[l]);
+        else blk_interior_solve<double>(u, ri, y[l]);
     }
     for (int l = 0; l < BLK_LANES; ++l) {
         const double zero[3] = {0.0, 0.0, 0.0};

@@ -304,6 +304,28 @@ __device__ __forceinline__ void lean_rhs(const ElemCoef<T>& ec, T dragc, bool co
 // spreads there), 13.55 against 13.79 at 20 steps per launch, 1.206 against 1.222 ms per 100-step launch in the kernel trace:
 // about a fifth of what 52 of 1634 issue slots project.  Outputs are bitwise the parent's, config 3 (state and
 // clock) and the linear instance.  With both switches off (=0 in the tuning build) the unit's code is the parent's line for line.
+// Two changes that rest on the mirror symmetry of a mass matrix of equal elements and on the linearity of the separator's
+// right-hand side; both change roundings, neither the number of fp64 operations outside the interior solve.
+// CRB_BLK_TWIST (crb_blocked.h): a lane's nodes 0 and 2 are eliminated into its centre node instead of swept 0 -> 1 -> 2 and back:
+// every interior B is diagonal, C = J A J, so the centre pivot is diagonal too and the solve is 29 fp64 instructions of depth
+// three against 35 of depth five, with six broadcast copies (B^-1, Dc^-1) against nine.  It is the instance TW = true
+// (crb_step_lean_twist_kernel), which a plan runs when its node blocks have the structure bitwise; the device assembly leaves a
+// rounding residue in B's off-diagonals at some element lengths (0.3 / 256 and 0.0731 / 256 among the suite's; 0.25 / 256 and
+// 1 / 256 have none), and those plans run TW = false.  crb_plan_get_blocked_form reports the choice.
+// CRB_BLK_ONE_RIGHT: the left halves of lane+1's first element enter nothing but the separator's right-hand side g, as C_s y_0 of
+// lane+1 does, so lane+1 forms h = fl[0] + C_s y_0 (the same five multiply-adds, on fl[0] instead of on g) and ONE shift brings
+// hR: g = (-fr[3] [+ drag]) - A_s y_2 - hR.  The impulse on the axial dof of a lane's last node lands on the local f2(3); the
+// axial and moment components of g's local part are carried negated until the subtraction of hR, where the sign is a source
+// modifier (formed as -fr they cost a v_xor_b32 each).  Lane 63 is shifted a 0, as before.
+// Step loop of the tuning build, per step (neither / TWIST alone / ONE_RIGHT alone / both): VALU 1582 / 1558 / 1562 / 1538, fp64
+// 1322 / 1298 / 1322 / 1298 (v_fmac_f64_dpp 264 / 240 / 264 / 240, every other fp64 opcode unchanged), v_mov_b32_dpp 240 / 240 /
+// 216 / 216, v_mov_b64 17 / 17 / 21 / 21, s_waitcnt 52 / 50 / 51 / 48, s_nop 25 / 27 / 30 / 29, LDS and scalar loads unchanged;
+// VGPRs 252 / 246 / 252 / 246, 103 SGPRs, no spill, no scratch, two waves per SIMD.  (Counted from the step loop's header label
+// to its backward branch, which gives the s_waitcnt 52 and s_nop 25 that DESIGN.md §4 records for the parent; "neither" is the
+// parent's assembly byte for byte.)
+// The linear instance takes neither (taken, it has VALU 1146 -> 1102, fp64 893 -> 869, 236 -> 228 VGPRs): its output is held to
+// its parent's bit for bit by the suite (tests/test_blocked_folded_forces.py), so its code stays line for line.  With both
+// switches off (=0 in the tuning build) the unit's code is the parent's line for line.  DESIGN.md §4 has the timings.
 // The next beam's state is not prefetched as in the one-node-per-lane
 // form: four nodes' records are 48 more registers than the budget of two waves per SIMD holds.
 #ifndef CRB_BLK_CHORD
@@ -330,13 +352,18 @@ __device__ __forceinline__ void lean_rhs(const ElemCoef<T>& ec, T dragc, bool co
 #ifndef CRB_BLK_SEP_ADDR
 #define CRB_BLK_SEP_ADDR 1
 #endif
+#ifndef CRB_BLK_ONE_RIGHT
+#define CRB_BLK_ONE_RIGHT 1
+#endif
 constexpr int BLK_STRIP_PAD = 4;   // the stride of the separator level that goes through the wave's LDS strip (the third)
 constexpr int BLK_STRIP_W = BLK_STRIP_PAD + BLK_LANES + BLK_STRIP_PAD;
 // dynamic LDS of the blocked stepper: the separator tables (value pairs per lane), then per wave a strip [3][W] of fp64
 __host__ __device__ constexpr size_t blk_lds_bytes(int ls) {
     return size_t(blk_sep_vals(ls) + 1) / 2 * 2 * BLK_LANES * sizeof(double) + size_t(4) * 3 * BLK_STRIP_W * sizeof(double);
 }
-template <typename T, int LS, int EM, typename KPT>
+// TW: the instance whose interiors are solved about their centre nodes (crb_step_lean_twist_kernel below; plans whose node
+// blocks have the mirror structure, crb_blocked.h: blocked_mirrored)
+template <typename T, int LS, int EM, bool TW, typename KPT>
 __device__ __forceinline__ void lean_blocked_body(KPT kp) {
     static_assert(sizeof(T) == 8, "the blocked stepper is fp64");
     static_assert(LS == 3 && (1 << (LS - 1)) == BLK_STRIP_PAD, "the strip carries the third separator level, stride 4");
@@ -370,6 +397,18 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
     // the separator tables read at immediate offsets from this lane's LDS byte address, laundered per level in place,
     // instead of through the laundered lane index (a new index every time, scaled again every time)
     constexpr bool SEPADDR = CRB_BLK_SEP_ADDR;
+    // the lane's interior solved about its centre node (crb_blocked.h: blk_twist_interior_solve; the plan's twisted table behind
+    // the shared form's constants, blk_twist_offset) instead of by block Thomas: 29 fp64 instructions against 35, depth 3 against 5
+    constexpr bool TWIST = TW;
+    // the two things a stage fetches from lane+1 -- the left halves of its first element, which enter nothing but the separator's
+    // right-hand side, and its y_0 -- in ONE exchange: lane+1 forms h = fl[0] + C_s y_0, and g = (-fr[3] [+ drag]) - A_s y_2 - hR
+    // (tip: lane 63 is shifted a 0, and C_s there only ever met a 0.  Written for the +f3 form, CRB_BLK_F3_PLUS.
+    //  The linear instance keeps both exchanges: its code, and with it its output, stays its parent's bit for bit)
+    constexpr bool ONER = CRB_BLK_ONE_RIGHT && F3PLUS && REGROUP;
+    static_assert(!TW || EM == EM_NONLINEAR, "the twisted instance is built for the nonlinear element");
+    // the table offsets of the form at hand
+    constexpr int O_WL = TWIST ? int(BT_WL) : int(BU_WL), O_WR = TWIST ? int(BT_WR) : int(BU_WR),
+                  O_AS = TWIST ? int(BT_AS) : int(BU_AS), O_CS = TWIST ? int(BT_CS) : int(BU_CS);
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef const __attribute__((address_space(4))) SlotConst<T>* CS;
     typedef const __attribute__((address_space(4))) T* CK;
@@ -418,10 +457,15 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
     // broadcast copies of the nine constants that multiply without adding (the first product of each blk_mul sum)
     T tab[BLK_TAB_REGS];
 #pragma unroll
-    for (int i = 0; i < BLK_TAB_REGS; ++i) tab[i] = p.blocked[blk_tab_index(i, lane)];
-    const T cD2[3] = {blk_bc_copy<BU_D2>(tab), blk_bc_copy<BU_D2 + 2>(tab), blk_bc_copy<BU_D2 + 4>(tab)};
-    const T cD1[3] = {blk_bc_copy<BU_U1>(tab), blk_bc_copy<BU_D1 + 2>(tab), blk_bc_copy<BU_D1 + 4>(tab)};
-    const T cD0[3] = {blk_bc_copy<BU_U0>(tab), blk_bc_copy<BU_D0 + 2>(tab), blk_bc_copy<BU_D0 + 4>(tab)};
+    for (int i = 0; i < BLK_TAB_REGS; ++i)
+        tab[i] = TWIST ? p.blocked[blk_twist_offset(LS) + BLK_TAB_ROW * i + (lane & (BLK_TAB_ROW - 1))] : p.blocked[blk_tab_index(i, lane)];
+    // (TWIST: six copies, cD0 = the diagonal of B^-1 and cD1 = that of Dc^-1; there is no cD2)
+    constexpr int O_C0u = TWIST ? int(BT_BI) : int(BU_U0), O_C0w = TWIST ? BT_BI + 1 : BU_D0 + 2, O_C0p = TWIST ? BT_BI + 2 : BU_D0 + 4;
+    constexpr int O_C1u = TWIST ? int(BT_DI) : int(BU_U1), O_C1w = TWIST ? BT_DI + 1 : BU_D1 + 2, O_C1p = TWIST ? BT_DI + 2 : BU_D1 + 4;
+    [[maybe_unused]] T cD2[3] = {T(0), T(0), T(0)};
+    if constexpr (!TWIST) { cD2[0] = blk_bc_copy<BU_D2>(tab); cD2[1] = blk_bc_copy<BU_D2 + 2>(tab); cD2[2] = blk_bc_copy<BU_D2 + 4>(tab); }
+    const T cD1[3] = {blk_bc_copy<O_C1u>(tab), blk_bc_copy<O_C1w>(tab), blk_bc_copy<O_C1p>(tab)};
+    const T cD0[3] = {blk_bc_copy<O_C0u>(tab), blk_bc_copy<O_C0w>(tab), blk_bc_copy<O_C0p>(tab)};
     __syncthreads();   // (the only barrier: the waves walk over their beams independently from here on)
     const int n_groups = (p.B + 3) / 4;
     for (int grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
@@ -572,7 +616,9 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                     fl[0][0] = cW[0] - f2[0];
 #pragma unroll
                     for (int k = 0; k + 1 < NP; ++k) fr[k][0] = f2[k] - f2[k + 1];
-                    fr[NP - 1][0] = dpp_from_higher(fl[0][0]);   // (-f2(3) - this below: the impulse's -amp lands on either term alike)
+                    // (-f2(3) - this below: the impulse's -amp lands on either term alike.  ONER: f1 of lane+1 arrives inside hR in
+                    //  the solve, and the impulse's -amp lands on the local f2(3), negated below)
+                    fr[NP - 1][0] = ONER ? f2[NP - 1] : dpp_from_higher(fl[0][0]);
                 }
                 // -- the impulse: fr - amp on its one (node, dof), so that r = (amp - fr) - fl there and -fr - fl everywhere else
                 //    (REGROUP, axial dof: fr[k][0] is the difference / the shifted-in f1 above, entering r with the same sign),
@@ -589,7 +635,7 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                     const int kon = imp_on ? kimp : -1, dof = HOLD ? dof_held : q.imp_dof;
                     // (F3PLUS: the transverse left half of lane+1's first element, for the last node's right-hand side below)
                     [[maybe_unused]] T flR1 = T(0);
-                    if constexpr (F3PLUS) flR1 = dpp_from_higher(fl[0][1]);
+                    if constexpr (F3PLUS && !ONER) flR1 = dpp_from_higher(fl[0][1]);
 #if defined(__HIP_DEVICE_COMPILE__)
                     // (SGN1: the sign of amp on the transverse dof -- "-" on fr[k][1] = -f3, "" on +f3 carried through, F3PLUS)
 #define CRB_BLK_IMPULSE(SGN1)                                                                  \
@@ -617,7 +663,8 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                             // (node k's transverse right-hand side directly behind its block: it is the last reader of
                             //  fl[k + 1][1], the very f3 that the next block takes in/out -- dead by then, it needs no copy)
                             CRB_BLK_IMPULSE("");
-                            r[k][1] = (fr[k][1] + drag_force<T>(dragc, sv[k][1])) - ((k + 1 < NP) ? fl[k + 1][1] : flR1);
+                            r[k][1] = fr[k][1] + drag_force<T>(dragc, sv[k][1]);
+                            if (k + 1 < NP || !ONER) r[k][1] -= (k + 1 < NP) ? fl[k + 1][1] : flR1;   // (ONER: the last node's is in hR)
                         } else CRB_BLK_IMPULSE("-");
                     }
 #undef CRB_BLK_IMPULSE
@@ -629,8 +676,10 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                             else fr[k][c] -= ac;
                         }
                     if constexpr (F3PLUS)
-                        for (int k = 0; k < NP; ++k)
-                            r[k][1] = (fr[k][1] + drag_force<T>(dragc, sv[k][1])) - ((k + 1 < NP) ? fl[k + 1][1] : flR1);
+                        for (int k = 0; k < NP; ++k) {
+                            r[k][1] = fr[k][1] + drag_force<T>(dragc, sv[k][1]);
+                            if (k + 1 < NP || !ONER) r[k][1] -= (k + 1 < NP) ? fl[k + 1][1] : flR1;
+                        }
 #endif
                 }
                 CRB_SETPRIO(P_TAIL);
@@ -639,16 +688,16 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                 for (int c = 0; c < 3; ++c) {
                     if (REGROUP && c == 0) {   // r_u[k] = (f2(k+1) - f2(k)) - cA1 W(k+1); the last node's -f2(3) - f1 of lane+1
 #pragma unroll
-                        for (int k = 0; k < NP; ++k) r[k][0] = (k + 1 < NP) ? (-fr[k][0] - cW[k + 1]) : (-f2[k] - fr[k][0]);
+                        for (int k = 0; k < NP; ++k) r[k][0] = (k + 1 < NP) ? (-fr[k][0] - cW[k + 1]) : (ONER ? fr[k][0] : (-f2[k] - fr[k][0]));   // (ONER: the last node's NEGATED, as its moment below: see the solve)
                         continue;
                     }
                     if (F3PLUS && c == 1) continue;   // (formed behind the impulse blocks, above)
-                    const T flR = dpp_from_higher(fl[0][c]);
+                    const T flR = ONER ? T(0) : dpp_from_higher(fl[0][c]);   // (ONER: inside hR in the solve)
 #pragma unroll
                     for (int k = 0; k < NP; ++k) {
                         T h = -fr[k][c];
                         if (c == 1) h += drag_force<T>(dragc, sv[k][1]);
-                        r[k][c] = h - ((k + 1 < NP) ? fl[k + 1][c] : flR);
+                        r[k][c] = (ONER && k + 1 == NP) ? ((c == 1) ? h : fr[k][c]) : h - ((k + 1 < NP) ? fl[k + 1][c] : flR);
                     }
                 }
                 // -- AHEAD: the polynomial constants of the NEXT stage (stage 3: of the next step's stage 0), requested where this
@@ -667,7 +716,8 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                 //    constant is a row broadcast of `tab` inside a multiply-add (66 per stage), or one of the nine copies; each
                 //    sum in the order the compiler contracts blk_interior_solve's (crb_blocked.h) with scalar operands: a blk_mul
                 //    row is fma(m1, v1, m2 v2), and the axial row of a blk_mul / blk_sub_mul pair is fma(d, v, -(u w))
-                T y[3][3], z1[3], z2[3], g[3], y0R[3];
+                T y[3][3], z1[3], g[3], y0R[3];
+                [[maybe_unused]] T z2[3];
                 // (the first separator level's table is requested here, under the interior solve, which has no wait of its own:
                 //  what the reads are addressed by is laundered through the right-hand side, so that they are issued where the solve
                 //  starts.  SEPADDR: that is the lane's table address, laundered in place -- the old value is dead, so nothing is
@@ -686,26 +736,54 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
                     cf0[i] = e[0]; cf0[i + 1] = e[1];
                 }
 #pragma unroll
-                for (int c = 0; c < 3; ++c) { z1[c] = r[1][c]; z2[c] = r[2][c]; g[c] = r[NP - 1][c]; }
-                blk_bc_sub_mul<BU_L1>(tab, r[0], z1);
-                blk_bc_sub_mul<BU_L2>(tab, z1, z2);
-                y[2][0] = cD2[0] * z2[0];                       // y_2 = D2 z_2
-                y[2][1] = cD2[1] * z2[2]; blk_bc_fma<BU_D2 + 1>(tab, z2[1], y[2][1]);
-                y[2][2] = cD2[2] * z2[2]; blk_bc_fma<BU_D2 + 3>(tab, z2[1], y[2][2]);
-                y[1][0] = -(cD1[0] * y[2][0]); blk_bc_fma<BU_D1>(tab, z1[0], y[1][0]);   // y_1 = D1 z_1 - U1 y_2
-                y[1][1] = cD1[1] * z1[2]; blk_bc_fma<BU_D1 + 1>(tab, z1[1], y[1][1]);
-                y[1][2] = cD1[2] * z1[2]; blk_bc_fma<BU_D1 + 3>(tab, z1[1], y[1][2]);
-                blk_bc_fnma<BU_U1 + 1>(tab, y[2][1], y[1][1]); blk_bc_fnma<BU_U1 + 2>(tab, y[2][2], y[1][1]);
-                blk_bc_fnma<BU_U1 + 3>(tab, y[2][1], y[1][2]); blk_bc_fnma<BU_U1 + 4>(tab, y[2][2], y[1][2]);
-                y[0][0] = -(cD0[0] * y[1][0]); blk_bc_fma<BU_D0>(tab, r[0][0], y[0][0]);   // y_0 = D0 r_0 - U0 y_1
-                y[0][1] = cD0[1] * r[0][2]; blk_bc_fma<BU_D0 + 1>(tab, r[0][1], y[0][1]);
-                y[0][2] = cD0[2] * r[0][2]; blk_bc_fma<BU_D0 + 3>(tab, r[0][1], y[0][2]);
-                blk_bc_fnma<BU_U0 + 1>(tab, y[1][1], y[0][1]); blk_bc_fnma<BU_U0 + 2>(tab, y[1][2], y[0][1]);
-                blk_bc_fnma<BU_U0 + 3>(tab, y[1][1], y[0][2]); blk_bc_fnma<BU_U0 + 4>(tab, y[1][2], y[0][2]);
+                for (int c = 0; c < 3; ++c) { z1[c] = r[1][c]; if (!TWIST) z2[c] = r[2][c]; g[c] = r[NP - 1][c]; }
+                if constexpr (TWIST) {
+                    // z_1 = r_1 - (A1 B^-1) r_0 - (C1 B^-1) r_2; y_1 = Dc^-1 z_1; y_0 = B^-1 r_0 - (B^-1 C0) y_1; y_2 = B^-1 r_2 - (B^-1 A2) y_1
+                    blk_bc_sub_mul<BT_P>(tab, r[0], z1);
+                    blk_bc_sub_mul<BT_Q>(tab, r[2], z1);
 #pragma unroll
-                for (int c = 0; c < 3; ++c) y0R[c] = dpp_from_higher(y[0][c]);
-                blk_bc_sub_mul<BU_AS>(tab, y[2], g);
-                blk_bc_sub_mul<BU_CS>(tab, y0R, g);
+                    for (int c = 0; c < 3; ++c) { y[0][c] = cD0[c] * r[0][c]; y[2][c] = cD0[c] * r[2][c]; y[1][c] = cD1[c] * z1[c]; }
+                    blk_bc_sub_mul<BT_U>(tab, y[1], y[0]);
+                    blk_bc_sub_mul<BT_V>(tab, y[1], y[2]);
+                } else {
+                    blk_bc_sub_mul<BU_L1>(tab, r[0], z1);
+                    blk_bc_sub_mul<BU_L2>(tab, z1, z2);
+                    y[2][0] = cD2[0] * z2[0];                       // y_2 = D2 z_2
+                    y[2][1] = cD2[1] * z2[2]; blk_bc_fma<BU_D2 + 1>(tab, z2[1], y[2][1]);
+                    y[2][2] = cD2[2] * z2[2]; blk_bc_fma<BU_D2 + 3>(tab, z2[1], y[2][2]);
+                    y[1][0] = -(cD1[0] * y[2][0]); blk_bc_fma<BU_D1>(tab, z1[0], y[1][0]);   // y_1 = D1 z_1 - U1 y_2
+                    y[1][1] = cD1[1] * z1[2]; blk_bc_fma<BU_D1 + 1>(tab, z1[1], y[1][1]);
+                    y[1][2] = cD1[2] * z1[2]; blk_bc_fma<BU_D1 + 3>(tab, z1[1], y[1][2]);
+                    blk_bc_fnma<BU_U1 + 1>(tab, y[2][1], y[1][1]); blk_bc_fnma<BU_U1 + 2>(tab, y[2][2], y[1][1]);
+                    blk_bc_fnma<BU_U1 + 3>(tab, y[2][1], y[1][2]); blk_bc_fnma<BU_U1 + 4>(tab, y[2][2], y[1][2]);
+                    y[0][0] = -(cD0[0] * y[1][0]); blk_bc_fma<BU_D0>(tab, r[0][0], y[0][0]);   // y_0 = D0 r_0 - U0 y_1
+                    y[0][1] = cD0[1] * r[0][2]; blk_bc_fma<BU_D0 + 1>(tab, r[0][1], y[0][1]);
+                    y[0][2] = cD0[2] * r[0][2]; blk_bc_fma<BU_D0 + 3>(tab, r[0][1], y[0][2]);
+                    blk_bc_fnma<BU_U0 + 1>(tab, y[1][1], y[0][1]); blk_bc_fnma<BU_U0 + 2>(tab, y[1][2], y[0][1]);
+                    blk_bc_fnma<BU_U0 + 3>(tab, y[1][1], y[0][2]); blk_bc_fnma<BU_U0 + 4>(tab, y[1][2], y[0][2]);
+                }
+                if constexpr (ONER) {
+                    // h = fl[0] + C_s y_0, what this lane owes the separator of lane-1; g (so far without the left halves of
+                    // lane+1's first element) takes lane+1's whole in one exchange: the tip is shifted a 0
+                    blk_bc_add_mul<O_CS>(tab, y[0], fl[0]);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) y0R[c] = dpp_from_higher(fl[0][c]);
+                    // (the axial and the moment component arrive negated -- a bare negation would be an instruction, inside the
+                    //  last subtraction it is a source modifier -- so A_s y_2 is added to them; the roundings are the mirror images)
+                    blk_bc_fma<O_AS + 0>(tab, y[2][0], g[0]);
+                    blk_bc_fnma<O_AS + 1>(tab, y[2][1], g[1]);
+                    blk_bc_fnma<O_AS + 2>(tab, y[2][2], g[1]);
+                    blk_bc_fma<O_AS + 3>(tab, y[2][1], g[2]);
+                    blk_bc_fma<O_AS + 4>(tab, y[2][2], g[2]);
+                    g[0] = -g[0] - y0R[0];
+                    g[1] = g[1] - y0R[1];
+                    g[2] = -g[2] - y0R[2];
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) y0R[c] = dpp_from_higher(y[0][c]);
+                    blk_bc_sub_mul<O_AS>(tab, y[2], g);
+                    blk_bc_sub_mul<O_CS>(tab, y0R, g);
+                }
 #pragma unroll
                 for (int l = 0; l < LS; ++l) {
                     // (the table address -- without SEPADDR the lane index -- is laundered through this level's input, so that
@@ -754,12 +832,12 @@ __device__ __forceinline__ void lean_blocked_body(KPT kp) {
 #pragma unroll
                     for (int c = 0; c < 3; ++c) a[k][c] = y[k][c];
                 static_assert(NP == 4, "three interior nodes, written out: the table offsets are template arguments");
-                blk_bc_sub_mul<BU_WL>(tab, xsL, a[0]);
-                blk_bc_sub_mul<BU_WR>(tab, xs, a[0]);
-                blk_bc_sub_mul<BU_WL + BLK_PACK>(tab, xsL, a[1]);
-                blk_bc_sub_mul<BU_WR + BLK_PACK>(tab, xs, a[1]);
-                blk_bc_sub_mul<BU_WL + 2 * BLK_PACK>(tab, xsL, a[2]);
-                blk_bc_sub_mul<BU_WR + 2 * BLK_PACK>(tab, xs, a[2]);
+                blk_bc_sub_mul<O_WL>(tab, xsL, a[0]);
+                blk_bc_sub_mul<O_WR>(tab, xs, a[0]);
+                blk_bc_sub_mul<O_WL + BLK_PACK>(tab, xsL, a[1]);
+                blk_bc_sub_mul<O_WR + BLK_PACK>(tab, xs, a[1]);
+                blk_bc_sub_mul<O_WL + 2 * BLK_PACK>(tab, xsL, a[2]);
+                blk_bc_sub_mul<O_WR + 2 * BLK_PACK>(tab, xs, a[2]);
 #pragma unroll
                 for (int c = 0; c < 3; ++c) a[NP - 1][c] = xs[c];
                 // -- RK4 bookkeeping
@@ -878,7 +956,7 @@ crb_step_lean_kernel(const KParams<T> p_formal) {
 #endif
     if constexpr (NPL > 1) {
         static_assert(NPL == BLK_NPL && LOGNW == 2 && !GRAV && !HELD && !PACK && !FB, "the blocked form is the plain 256-slot stepper");
-        lean_blocked_body<T, LV, EM>(kp);
+        lean_blocked_body<T, LV, EM, false>(kp);
         return;
     }
     KParams<T> p = CRB_PARAMS(kp);
@@ -1267,6 +1345,22 @@ crb_step_lean_kernel(const KParams<T> p_formal) {
     }
 #undef CRB_FRESH
 #undef CRB_PARAMS
+}
+
+// The register-blocked stepper (crb_step_lean_kernel<double, LS, 2, false, EM, ..., NPL = 4>) with every lane's interior solved
+// about its centre node (lean_blocked_body<..., TW = true>; CRB_BLK_TWIST): the instance that blocked plans of nonlinear elements run when their node
+// blocks have the mirror structure of equal elements bitwise (crb_blocked.h: blocked_mirrored); the others run the block-Thomas
+// instance above.  Four independent one-wave beams per workgroup, two waves per SIMD.
+template <typename T, int LS, int EM>
+__global__ void __launch_bounds__(256, 2) crb_step_lean_twist_kernel(const KParams<T> p_formal) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const __attribute__((address_space(4))) KParams<T>* KP;
+    KP kp = (KP)__builtin_amdgcn_kernarg_segment_ptr();   // (as crb_step_lean_kernel reads its parameters)
+    (void)p_formal;
+#else
+    const KParams<T>* kp = &p_formal;
+#endif
+    lean_blocked_body<T, LS, EM, true>(kp);
 }
 
 // ------------------------------------------------------------------ lean stage kernel

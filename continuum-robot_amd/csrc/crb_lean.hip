@@ -112,10 +112,14 @@ hipError_t launch_lean_grav(const KParams<T>& k, int n_beams, int levels, int lo
 
 #if CRB_LEAN_PART == 0 || CRB_LEAN_PART == 1
 namespace {
-template <int LS, int EM>
+template <int LS, int EM, bool TW>
 hipError_t one_blocked(const KParams<T>& k, int n_beams, hipStream_t st) {
     // NPL = 4: a wave is a beam, a workgroup four of them; shared-table plans only, so the workgroups walk over groups of beams
-    constexpr auto kernel = crb_step_lean_kernel<T, LS, 2, false, EM, false, false, false, BLK_NPL>;
+    // (TW: the instance with the twisted interior solve)
+    constexpr auto kernel = [] {
+        if constexpr (TW) return crb_step_lean_twist_kernel<T, LS, EM>;
+        else return crb_step_lean_kernel<T, LS, 2, false, EM, false, false, false, BLK_NPL>;
+    }();
     const size_t smem = blk_lds_bytes(LS);   // the separator tables and the waves' strips
     const int groups = (n_beams + 3) / 4;
     const int grid = env_set("CRB_LEAN_NO_WALK") ? groups : walking_grid<kernel>(groups, 256, smem);
@@ -123,16 +127,24 @@ hipError_t one_blocked(const KParams<T>& k, int n_beams, hipStream_t st) {
     return hipGetLastError();
 }
 }  // namespace
-hipError_t launch_lean_blocked(const KParams<T>& k, int n_beams, int levels, int elem_mode, hipStream_t st) {
-    if (!k.blocked) return hipErrorInvalidValue;
-#ifdef CRB_FAST_BUILD   // (make fast: the config-3 instance)
+hipError_t launch_lean_blocked(const KParams<T>& k, int n_beams, int levels, int elem_mode, bool twist, hipStream_t st) {
+    if (!k.blocked || (twist && !CRB_BLK_TWIST)) return hipErrorInvalidValue;
+#ifdef CRB_FAST_BUILD   // (make fast: the config-3 instance, in both forms of the interior solve)
     if constexpr (F64)
-        if (levels == 3 && elem_mode == EM_NONLINEAR) return one_blocked<3, EM_NONLINEAR>(k, n_beams, st);
+        if (levels == 3 && elem_mode == EM_NONLINEAR) {
+            if constexpr (CRB_BLK_TWIST)
+                if (twist) return one_blocked<3, EM_NONLINEAR, true>(k, n_beams, st);
+            return one_blocked<3, EM_NONLINEAR, false>(k, n_beams, st);
+        }
     return hipErrorInvalidValue;
 #else
     return with_int<0, MAX_LV>(levels, [&](auto ls) { return with_elem_mode(elem_mode, [&](auto e) {
-        if constexpr (lean_blocked_built(F64, ls, e)) return one_blocked<ls, e>(k, n_beams, st);
-        else return hipErrorInvalidValue;
+        if constexpr (lean_blocked_built(F64, ls, e)) {
+            if constexpr (CRB_BLK_TWIST && e == EM_NONLINEAR)
+                if (twist) return one_blocked<ls, e, true>(k, n_beams, st);
+            if (twist) return hipErrorInvalidValue;
+            return one_blocked<ls, e, false>(k, n_beams, st);
+        } else return hipErrorInvalidValue;
     }); });
 #endif
 }

@@ -43,8 +43,9 @@ constexpr bool lean_implicit_pack_sched_built(bool f64, int levels) { return lea
 hipError_t launch_lean(const KParams<double>& k, int n_beams, int levels, int lognw, bool grav, int elem_mode, hipStream_t st);
 hipError_t launch_lean(const KParams<float>& k, int n_beams, int levels, int lognw, bool grav, int elem_mode, hipStream_t st);
 // launches the register-blocked stepper crb_step_lean_kernel<double, levels, 2, false, elem_mode, ..., NPL = 4> (one wave per
-// 256-slot beam, four beams per workgroup; k.blocked = the plan's blocked tables; lean_blocked_built)
-hipError_t launch_lean_blocked(const KParams<double>& k, int n_beams, int levels, int elem_mode, hipStream_t st);
+// 256-slot beam, four beams per workgroup; k.blocked = the plan's blocked tables; lean_blocked_built); twist: its form with the
+// interiors solved about their centre nodes, crb_step_lean_twist_kernel<double, levels, elem_mode>, whose table the plan then holds
+hipError_t launch_lean_blocked(const KParams<double>& k, int n_beams, int levels, int elem_mode, bool twist, hipStream_t st);
 // launches the packed one-wave stepper with the LQR feedback inside its stages (crb_step_lean_kernel<..., FB>): k.G >= 2 beams
 // per wave, gain / reference / reduced map in k (lean_feedback_built)
 hipError_t launch_lean_feedback(const KParams<double>& k, int n_beams, int levels, bool grav, hipStream_t st);

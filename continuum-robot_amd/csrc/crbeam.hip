@@ -136,6 +136,7 @@ struct crb_plan {
     // the register-blocked stepper's tables (crb_blocked.h; fp64 uniform 256-slot beams with one table set, else nullptr)
     double* d_blocked = nullptr;
     int blocked_levels = 0;
+    bool blocked_twist = false;   // the blocked tables hold the twisted interior's table: the plan runs that instance
     int32_t* d_free_index = nullptr;
     int32_t* d_col_off = nullptr;  // [2n] reduced state index -> offset in a beam's state record
     int32_t* d_row_off = nullptr;  // [n]  reduced position index -> offset in a beam's force record
@@ -377,14 +378,28 @@ int device_assemble(crb_plan* p, const crb_beam_desc* descs, int nd, const std::
                       std::memcmp(&hs[j].drag, &hs[0].drag, sizeof(T)) == 0 && hs[j].mask[0] == T(1) && hs[j].mask[1] == T(1) &&
                       hs[j].mask[2] == T(1);
         if (uniform) {
-            std::vector<double> tab(size_t(blk_share_offset(BLK_MAX_LV)) + SK_N);
-            double norms[BLK_MAX_LV];
-            const int lv = blocked_factor(blk.data(), d->length[0], tab.data(), tab.data() + BU_N, norms);
+            // (CRB_BLK_TWIST: the twisted interior's table behind them, for node blocks that have the mirror structure it needs
+            //  bitwise; the others -- the device assembly contracts B's off-diagonal differences into fused multiply-adds, which
+            //  leave a rounding residue at some element lengths -- run the block-Thomas instance)
+            std::vector<double> tab(size_t(blk_twist_offset(BLK_MAX_LV)) + BT_TAB);
+            double norms[BLK_MAX_LV], tw[BT_TAB];
+            //  (nonlinear elements: the linear instance is not built in that form)
+            const bool twist_ok = CRB_BLK_TWIST && hs[0].elem.kind == KIND_NONLINEAR && blocked_mirrored(blk.data());
+            bool twist = twist_ok;
+            int lv = blocked_factor(blk.data(), d->length[0], tab.data(), tab.data() + BU_N, norms, twist ? tw : nullptr);
+            if (lv < 0 && twist) {   // (the twisted constants differ between lanes: the block-Thomas instance, if its own do not)
+                twist = false;
+                lv = blocked_factor(blk.data(), d->length[0], tab.data(), tab.data() + BU_N, norms);
+            }
             if (lv >= 1) {
                 // nonlinear elements: the force polynomials' folded constants behind the tables (crb_math.h: elem_fold_build),
                 // and behind those the constants of the form that shares the membrane combinations (elem_share_build)
                 const bool fold = hs[0].elem.kind == KIND_NONLINEAR;
-                const size_t n = fold ? size_t(blk_share_offset(lv)) + SK_N : size_t(blk_fold_offset(lv));
+                size_t n = fold ? size_t(blk_share_offset(lv)) + SK_N : size_t(blk_fold_offset(lv));
+                if (twist) {
+                    n = size_t(blk_twist_offset(lv)) + BT_TAB;
+                    std::memcpy(tab.data() + blk_twist_offset(lv), tw, sizeof(tw));
+                }
                 if (fold) {
                     ElemCoef<double> ecd;
                     for (int i = 0; i < 6; ++i) ecd.c[i] = double(hs[0].elem.c[i]);
@@ -394,6 +409,7 @@ int device_assemble(crb_plan* p, const crb_beam_desc* descs, int nd, const std::
                 HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p->d_blocked), n * sizeof(double)));
                 HIP_TRY(hipMemcpy(p->d_blocked, tab.data(), n * sizeof(double), hipMemcpyHostToDevice));
                 p->blocked_levels = lv;
+                p->blocked_twist = twist;
             }
         }
     }
@@ -836,8 +852,10 @@ extern "C" int crb_plan_get_beam_free_index(const crb_plan* p, int beam, int32_t
 // Host restatement of the register-blocked stepper's mass solve (crb_blocked.h), for the test suite: blocks = the 256 node rows
 // of M as [a_ax, b_ax, c_ax, A[4], B[4], C[4]], Lc the length that scales rotations in the level norms.  x = M^-1 r ([256][3]),
 // *levels the separator levels the solve keeps, norms[6] every separator level's largest multiplier.
-extern "C" int crb_blocked_solve_host(const double* blocks, double Lc, const double* r, double* x, int32_t* levels, double* norms) {
-    if (!blocks || !r || !x) return fail(CRB_EINVAL, "crb_blocked_solve_host: null argument");
+namespace {
+int blocked_solve_host_impl(const char* who, bool twist, const double* blocks, double Lc, const double* r, double* x, int32_t* levels,
+                            double* norms) {
+    if (!blocks || !r || !x) return fail(CRB_EINVAL, std::string(who) + ": null argument");
     std::vector<NodeBlocks> blk(BLK_S);
     for (int j = 0; j < BLK_S; ++j) {
         const double* b = blocks + size_t(j) * 15;
@@ -845,12 +863,30 @@ extern "C" int crb_blocked_solve_host(const double* blocks, double Lc, const dou
         for (int k = 0; k < 4; ++k) { blk[j].A[k] = b[3 + k]; blk[j].B[k] = b[7 + k]; blk[j].C[k] = b[11 + k]; }
     }
     std::vector<double> tab(BU_N + size_t(blk_sep_vals(BLK_MAX_LV)) * BLK_LANES);
-    double nrm[BLK_MAX_LV];
-    const int lv = blocked_factor(blk.data(), Lc, tab.data(), tab.data() + BU_N, nrm);
-    if (lv < 0) return fail(CRB_EUNSUPPORTED, "crb_blocked_solve_host: the lane interiors of this mass matrix are not uniform");
-    blocked_solve_host(tab.data(), tab.data() + BU_N, lv, r, x);
+    double nrm[BLK_MAX_LV], tw[BT_TAB];
+    const bool mirrored = !twist || blocked_mirrored(blk.data());
+    const int lv = blocked_factor(blk.data(), Lc, tab.data(), tab.data() + BU_N, nrm, twist && mirrored ? tw : nullptr);
+    if (lv >= 0 && !mirrored)
+        return fail(CRB_EUNSUPPORTED, std::string(who) + ": the lane interiors of this mass matrix lack the mirror structure of equal elements");
+    if (lv < 0) return fail(CRB_EUNSUPPORTED, std::string(who) + ": the lane interiors of this mass matrix are not uniform");
+    blocked_solve_host(tab.data(), tab.data() + BU_N, lv, r, x, twist ? tw : nullptr);
     if (levels) *levels = lv;
     if (norms) std::memcpy(norms, nrm, sizeof(nrm));
+    return CRB_OK;
+}
+}  // namespace
+extern "C" int crb_blocked_solve_host(const double* blocks, double Lc, const double* r, double* x, int32_t* levels, double* norms) {
+    return blocked_solve_host_impl("crb_blocked_solve_host", false, blocks, Lc, r, x, levels, norms);
+}
+// ... with the interiors solved about their centre nodes, as the blocked stepper does (CRB_BLK_TWIST)
+extern "C" int crb_blocked_twist_solve_host(const double* blocks, double Lc, const double* r, double* x, int32_t* levels, double* norms) {
+    return blocked_solve_host_impl("crb_blocked_twist_solve_host", true, blocks, Lc, r, x, levels, norms);
+}
+
+extern "C" int crb_plan_get_blocked_form(const crb_plan* p, int32_t* form, int32_t* levels) {
+    if (!p) return fail(CRB_EINVAL, "null argument");
+    if (form) *form = !p->d_blocked ? 0 : (p->blocked_twist ? 2 : 1);
+    if (levels) *levels = p->d_blocked ? p->blocked_levels : 0;
     return CRB_OK;
 }
 
@@ -1358,7 +1394,7 @@ int step_rk4_impl(const crb_plan* p, void* x, double t0, double dt, int n_steps,
     if constexpr (sizeof(T) == 8) {
         if (blocked_step_ok(p, k.u_held)) {
             k.blocked = p->d_blocked;
-            HIP_TRY(crb::launch_lean_blocked(k, p->B, p->blocked_levels, p->elem_mode, st));
+            HIP_TRY(crb::launch_lean_blocked(k, p->B, p->blocked_levels, p->elem_mode, p->blocked_twist, st));
             return CRB_OK;
         }
     }

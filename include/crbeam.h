@@ -164,6 +164,15 @@ int crb_plan_get_slot_tables(const crb_plan* plan, double* drag, double* half_ma
  * levels kept, norms[6] = each separator level's largest multiplier (either may be NULL).  CRB_EUNSUPPORTED when the lane
  * interiors (4 nodes per lane) are not bitwise uniform. */
 int crb_blocked_solve_host(const double* blocks, double Lc, const double* r, double* x, int32_t* levels, double* norms);
+/* The same with every lane's interior solved about its centre node, the form the blocked stepper runs (crb_blocked.h:
+ * blk_twist_interior_solve).  CRB_EUNSUPPORTED also when the lanes are uniform but an interior lacks the mirror structure of
+ * equal elements (diagonal B, C = J A J with J = diag(1, -1) on (w, phi)); the message then names the mirror structure. */
+int crb_blocked_twist_solve_host(const double* blocks, double Lc, const double* r, double* x, int32_t* levels, double* norms);
+/* Which tables of the register-blocked stepper the plan holds: *form = 0 none (the plan never runs it), 1 the block-Thomas
+ * interior solve, 2 the interior solve twisted about each lane's centre node (nonlinear plans whose node blocks have the mirror
+ * structure of equal elements bitwise); *levels = its separator levels (0 for form 0).  Either may be NULL.  The plan's
+ * fixed-step RK4 calls without gravity and held input run that form unless CRB_DISABLE_BLOCKED is set. */
+int crb_plan_get_blocked_form(const crb_plan* plan, int32_t* form, int32_t* levels);
 /* Dense reduced mass matrix as assembled by the plan, [n_free][n_free] host fp64
  * (EulerBernoulliBeam.get_mass_matrix, euler_bernoulli_beam.py:358-362). */
 int crb_plan_get_mass(const crb_plan* plan, double* M);
